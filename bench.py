@@ -1,12 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the poly search hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): k-mers hashed / s through mash.Sketch on
 configs[1] -- 1,000,000 synthetic 10 kb reads, k=21, s=1000, per GPU.
 A "step" is one pass of K1 (polyhip_mash_sketch_batch_dev) over the whole
 read set, inputs already resident in HBM.
+
+A plain run sets up, runs W untimed and exactly K timed steps, writes the
+last step's sketches if --dump-outputs is given (dump_outputs()), and prints
+the line: the headline legs `value` / `roofline` below, from the timed steps
+alone.  Everything else -- strong scaling, the oracle spot checks, the
+secondary kernels (`extra`), the CPU baselines, the full-record side file --
+runs only with --full.
 
 Ranks.  `--gpus N` ALWAYS means N ranks, one per GPU.  Started under
 torch.distributed.run (WORLD_SIZE set) the script is one of those ranks and
@@ -21,6 +28,7 @@ Legs in the one JSON line:
                 (disjoint slice of one splitmix64 stream, no data-path
                 collective); timed region = barrier + synchronize on both
                 sides, MAX over ranks.
+With --full also:
   strong        (N > 1) the SAME 1M reads of configs[1] split over the ranks
                 (sharding.shard_range), timed the same way.
   extra         N = 1: secondary rates of every other kernel (SW cell updates/s,
@@ -52,6 +60,8 @@ SKETCH = 1000
 SEED = 0xC2
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec
 WATCHDOG_S = 240      # the N > 1 all-gather leg may not hold the line hostage for longer
+DUMP_ROWS = 4096      # --dump-outputs: sketches sampled (4096 x 1000 float64 = 33 MB in all)
+DUMP_SEED = 0xD0
 
 
 def parse():
@@ -60,17 +70,24 @@ def parse():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reads", type=int, default=1_000_000, help="reads per GPU (config: 1,000,000)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed sample of the last step's sketches to DIR/*.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: strong scaling (N > 1), the oracle spot checks, the "
+                         "secondary kernels, the CPU baselines, and write the full record to --full-out")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-reads", type=int, default=400, help="reads per core in the CPU-baseline sample")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary kernels")
-    ap.add_argument("--full-out", default=os.path.join(ROOT, "gpurun_out", "bench_extra.json")
-                    if os.path.isdir(os.path.join(ROOT, "gpurun_out")) else os.path.join(ROOT, "bench_extra.json"),
-                    help="where the FULL record goes (every leg's workload text, roofline, counter sources, CPU samples); "
-                         "stdout carries only the compact line (poly_amd/bench_line.py, at most 8 kB)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary kernels")
+    ap.add_argument("--full-out", default=os.path.join(ROOT, "bench_extra.json"),
+                    help="with --full: where the FULL record goes (every leg's workload text, roofline, counter sources, "
+                         "CPU samples); stdout carries only the compact line (poly_amd/bench_line.py, at most 8 kB)")
     ap.add_argument("--host-devices", type=int, default=0,
                     help="N > 0: the PCIe-inclusive host-pointer legs (extra.e2e_host_pointers) run on the library's device list "
                          "0..N-1 (polyhip_set_devices: ONE host call fanned out over N GPUs; ids wrap around the visible devices)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.reads < 1:
+        ap.error("--steps and --reads must be at least 1, --warmup at least 0")
+    return args
 
 
 def self_launch(args) -> int:
@@ -86,20 +103,21 @@ def self_launch(args) -> int:
     return subprocess.call(cmd, env=env)
 
 
-def emit(full: dict, json_fd: int, full_out: str) -> None:
-    """The full record -> side file + stderr; the compact line (<= bench_line.LIMIT bytes, json round-trip checked) ->
-    the original stdout as the LAST thing written."""
+def emit(full: dict, json_fd: int, full_out: str | None) -> None:
+    """The full record -> side file (if `full_out`) + stderr; the compact line (<= bench_line.LIMIT bytes, json round-trip
+    checked) -> the original stdout as the LAST thing written."""
     from poly_amd import bench_line
     try:
         text_full = bench_line.render_full(full)
     except Exception as e:  # the line must still go out
         text_full = json.dumps({"error": f"full record not serialisable: {type(e).__name__}: {e}"})
-    try:
-        with open(full_out, "w") as f:
-            f.write(text_full + "\n")
-        full = dict(full, full=os.path.relpath(full_out, ROOT) if full_out.startswith(ROOT) else full_out)
-    except OSError as e:
-        sys.stderr.write(f"bench.py: could not write {full_out}: {e}\n")
+    if full_out:
+        try:
+            with open(full_out, "w") as f:
+                f.write(text_full + "\n")
+            full = dict(full, full=os.path.relpath(full_out, ROOT) if full_out.startswith(ROOT) else full_out)
+        except OSError as e:
+            sys.stderr.write(f"bench.py: could not write {full_out}: {e}\n")
     sys.stderr.write("bench.py full record: " + text_full + "\n")
     sys.stderr.flush()
     try:
@@ -343,6 +361,23 @@ def timed_steps(step, steps: int, warmup: int, sync_all, world: int, dev):
     kern_ms = sum(ts) / max(1, steps)
     timed_steps.last_median_ms = 0.5 * (ts[(steps - 1) // 2] + ts[steps // 2]) if steps else 0.0
     return elapsed, kern_ms
+
+
+def dump_outputs(path: str, out, rank: int, world: int) -> None:
+    """--dump-outputs: what the timed path returned in its last step, the (reads x s) sketch matrix of uint32 hashes, for
+    a fixed sample of reads -- the first, the last and up to DUMP_ROWS / world more drawn with DUMP_SEED -- as float64
+    (exact for 32-bit values): DIR/sketches.npy (rows in read order) and DIR/sketch_reads.npy (the read of each row).
+    At N ranks every rank writes its own reads' sample with the suffix _rank<r>; all files together stay under 64 MB."""
+    import numpy as np
+    import torch
+    n = out.shape[0]
+    k = min(n, max(1, DUMP_ROWS // world))
+    pick = np.unique(np.concatenate([[0, n - 1], np.random.default_rng(DUMP_SEED).choice(n, k, replace=False)]))
+    rows = out[torch.from_numpy(pick).to(out.device)].cpu().numpy().view(np.uint32)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, f"sketches{sfx}.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, f"sketch_reads{sfx}.npy"), pick.astype(np.float64))
 
 
 def allgather_distance(dev, rank: int, world: int, one_gpu_test: bool = False):
@@ -594,14 +629,16 @@ def main() -> int:
     value = world * kmers_per_step * args.steps / elapsed
     alg_bytes = n * (READ_LEN + 4 * SKETCH)  # per launch: reads in, sketches out
     achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
 
-    # parity spot check inside the bench (rank 0 only): 8 reads against the oracle's FAITHFUL variant -- the first read, the
+    # --full: parity spot check inside the bench (rank 0 only): 8 reads against the oracle's FAITHFUL variant -- the first read, the
     # LAST one (the slab kernel's persistent workgroups stride to it) and six drawn from the whole batch by a seed that
     # changes with the date and --steps, so that successive runs look at different reads (round-4 verdict: reads 0..7 of
     # one stream, the same eight every round, said nothing about read 999,999).  The reads are taken from the device
     # buffer the kernel read; that the buffer IS the stream's bytes is checked on the first read.
-    parity = None
-    if rank == 0:
+    parity, parity_detail = None, None
+    if rank == 0 and args.full:
         import datetime
         import numpy as np
         import oracle as orc
@@ -616,9 +653,9 @@ def main() -> int:
         parity = bool((got == want).all()) and stream_ok
         parity_detail = {"reads": [int(r) for r in pick], "seed": int(spot_seed), "oracle": "orc_mash_sketch faithful=1"}
 
-    # strong scaling: the SAME n reads of configs[1] (stream positions 0 .. n*READ_LEN) split over the ranks
+    # --full: strong scaling, the SAME n reads of configs[1] (stream positions 0 .. n*READ_LEN) split over the ranks
     strong = None
-    if world > 1:
+    if world > 1 and args.full:
         lo, hi = sharding.shard_range(n, rank, world)
         m_loc = hi - lo
         mash.synth_dna_dev(SEED, seqs[:m_loc * READ_LEN], first=lo * READ_LEN)
@@ -665,7 +702,7 @@ def main() -> int:
                      "valu_issue": valu_issue_ceiling(kmers_per_step / (kern_ms * 1e-3))},
         "parity_spot_check": parity,
     }
-    if rank == 0:
+    if parity_detail is not None:
         line["roofline"]["parity_spot_check_reads"] = parity_detail
     if strong is not None:
         line["strong"] = strong
@@ -673,7 +710,7 @@ def main() -> int:
     # free the headline's buffers before the secondary kernels allocate theirs
     del seqs, out, offs
     torch.cuda.empty_cache()
-    if world > 1 and not args.no_extra:
+    if world > 1 and args.full and not args.no_extra:
         # BASELINE configs[3] sharded: every rank aligns its own 1M reads against the shared reference
         # (pairs split N/G, no collective); the slowest rank sets the time
         r, sw_err = None, None
@@ -736,7 +773,7 @@ def main() -> int:
         dog.cancel()
         if rank == 0:
             line["extra"]["mash_distance_allgather"] = line_extra
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         if not args.no_extra:
             try:
                 from poly_amd import bench_extra
@@ -796,7 +833,7 @@ def main() -> int:
                            "sw_valu_frac": ((line.get("secondary") or {}).get("roofline") or {}).get("frac"),
                            "parity_spot_check": line.get("parity_spot_check")}
         sys.stdout.flush()
-        emit(line, json_fd, args.full_out)
+        emit(line, json_fd, args.full_out if args.full else None)
     if world > 1:
         dist.destroy_process_group()
     return 0

@@ -3,7 +3,7 @@
 bench.py measures a lot (fifteen secondary legs, each with its workload text, roofline, counter sources, CPU sample).
 Round 5's line carrying all of it was 20 kB and the driver's parser gave up on it.  So there are two artefacts now:
 
-  full      everything, prose included -> a side file (bench_extra.json beside bench.py, or --full-out) and stderr
+  full      everything, prose included -> stderr and, with --full, a side file (bench_extra.json beside bench.py, or --full-out)
   the line  compact(full): the contract keys, `roofline` and `cpu_baseline` reduced to numbers and one short sample
             string, `secondary` (the metric's SW half), one `[value, frac, traffic_ratio]` triple per secondary leg, the
             spot checks and the summary.  LIMIT bytes at most (tests/test_bench_line_cpu.py holds it to that for the

@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 run() { # tag, rocprof args..., -- cmd
   tag=$1; shift
   out=$ROOT/gpurun_out/prof_$tag; rm -rf $out; mkdir -p $out
-  ( cd $ROOT && rocprofv3 "$@" ) > $out/run.log 2>&1
+  ( cd $ROOT && rocprofv3 -d $out "$@" ) > $out/run.log 2>&1
   f=$(find $out -name "*results.db" | head -1)
   if [ -n "$f" ]; then ( cd $ROOT && python scripts/rocpd_summary.py $f "$tag" > gpurun_out/$tag.md 2>&1 ); else echo "no db for $tag"; tail -5 $out/run.log; fi
 }
@@ -18,7 +18,7 @@ BENCH="python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extra"
 # kernel stats of the headline command (default steps/warmup, without the secondary kernels so that the
 # K1 average is the timed region's), and of the full default command
 run ${R}_bench_stats --kernel-trace --stats -d $ROOT/gpurun_out/prof_${R}_bench_stats -o x -- python bench.py --no-extra --no-cpu-baseline
-run ${R}_bench_full_stats --kernel-trace --stats -d $ROOT/gpurun_out/prof_${R}_bench_full_stats -o x -- python bench.py --no-cpu-baseline
+run ${R}_bench_full_stats --kernel-trace --stats -o x -- python bench.py --full --no-cpu-baseline
 run ${R}_bench_fetch --pmc FETCH_SIZE --kernel-trace -d $ROOT/gpurun_out/prof_${R}_bench_fetch -o x -- $BENCH
 run ${R}_bench_write --pmc WRITE_SIZE --kernel-trace -d $ROOT/gpurun_out/prof_${R}_bench_write -o x -- $BENCH
 run ${R}_calib_fetch --pmc FETCH_SIZE --kernel-trace -d $ROOT/gpurun_out/prof_${R}_calib_fetch -o x -- scripts/ubench/hbm_calib

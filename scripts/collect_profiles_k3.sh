@@ -7,11 +7,11 @@ cd /tmp && export TMPDIR=/tmp
 run() { # tag, rocprof args..., -- cmd
   tag=$1; shift
   out=$ROOT/gpurun_out/prof_$tag; rm -rf $out; mkdir -p $out
-  ( cd $ROOT && rocprofv3 "$@" ) > $out/run.log 2>&1
+  ( cd $ROOT && rocprofv3 -d $out "$@" ) > $out/run.log 2>&1
   f=$(find $out -name "*results.db" | head -1)
   if [ -n "$f" ]; then ( cd $ROOT && python scripts/rocpd_summary.py $f "$tag" > gpurun_out/$tag.md 2>&1 ); else echo "no db for $tag"; tail -5 $out/run.log; fi
 }
-run ${R}_bench_full_stats --kernel-trace --stats -d $ROOT/gpurun_out/prof_${R}_bench_full_stats -o x -- python bench.py --no-cpu-baseline
+run ${R}_bench_full_stats --kernel-trace --stats -o x -- python bench.py --full --no-cpu-baseline
 run ${R}_k3_stats --kernel-trace --stats -d $ROOT/gpurun_out/prof_${R}_k3_stats -o x -- python scripts/quick_k3tb.py
 run ${R}_k3_250bp_stats --kernel-trace --stats -d $ROOT/gpurun_out/prof_${R}_k3_250bp_stats -o x -- python scripts/quick_k3tb.py 400000 250 5000
 run ${R}_k3_1kb_stats --kernel-trace --stats -d $ROOT/gpurun_out/prof_${R}_k3_1kb_stats -o x -- python scripts/quick_k3tb.py 20000 1000 5000

@@ -6,14 +6,14 @@ cd /tmp && export TMPDIR=/tmp
 run() { # tag, rocprof args..., -- cmd
   tag=$1; shift
   out=$ROOT/gpurun_out/prof_$tag; rm -rf $out; mkdir -p $out
-  ( cd $ROOT && rocprofv3 "$@" ) > $out/run.log 2>&1
+  ( cd $ROOT && rocprofv3 -d $out "$@" ) > $out/run.log 2>&1
   f=$(find $out -name "*results.db" | head -1)
   if [ -n "$f" ]; then ( cd $ROOT && python scripts/rocpd_summary.py $f "$tag" > gpurun_out/$tag.md 2>&1 ); else echo "no db for $tag"; tail -5 $out/run.log; fi
   rm -rf $out
 }
 BENCH="python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extra"
 run ${R}_bench_stats --kernel-trace --stats -d $ROOT/gpurun_out/prof_${R}_bench_stats -o x -- python bench.py --no-extra --no-cpu-baseline
-run ${R}_bench_full_stats --kernel-trace --stats -d $ROOT/gpurun_out/prof_${R}_bench_full_stats -o x -- python bench.py --no-cpu-baseline
+run ${R}_bench_full_stats --kernel-trace --stats -o x -- python bench.py --full --no-cpu-baseline
 run ${R}_bench_fetch --pmc FETCH_SIZE --kernel-trace -d $ROOT/gpurun_out/prof_${R}_bench_fetch -o x -- $BENCH
 run ${R}_bench_write --pmc WRITE_SIZE --kernel-trace -d $ROOT/gpurun_out/prof_${R}_bench_write -o x -- $BENCH
 run ${R}_k1_issue --pmc SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_INSTS_VALU --kernel-trace -d $ROOT/gpurun_out/prof_${R}_k1_issue -o x -- python scripts/quick_k1.py

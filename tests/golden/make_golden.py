@@ -94,8 +94,27 @@ def clone_parts():
     print("clone_parts.json", {k: len(v) for k, v in out.items()})
 
 
+def fork_declarations():
+    """for every rename of go/fork.sh: the 1-based numbers of the lines of the reference file that start with the
+    declaration prefix it renames (tests/test_go_binding_cpu.py checks fork.sh against these)"""
+    import json
+    fork = open(os.path.join(HERE, "..", "..", "go", "fork.sh")).read()
+    out = {}
+    for m in re.finditer(r"^ren\s+(\S+)\s+'([^']*)'\s+'([^']*)'", fork, flags=re.M):
+        path, old = m.group(1), m.group(2).replace("\\*", "*")
+        with open(os.path.join(REF, path)) as f:
+            hits = [i + 1 for i, line in enumerate(f) if line.startswith(old)]
+        assert hits, f"{path}: no line starts with `{old}`"
+        out.setdefault(path, {})[old] = hits
+    with open(os.path.join(HERE, "fork_declarations.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("fork_declarations.json", sum(len(v) for v in out.values()))
+
+
 if __name__ == "__main__":
     copy_fastq()
     clone_example_output()
     clone_parts()
+    fork_declarations()
     sys.exit(main())

@@ -7,6 +7,7 @@ package's own Go signatures and the reference's declaration lines.
    declared number of arguments;
 3. go/fork.sh renames exactly the declarations the overlays re-supply, and every *CPU function an overlay calls is
    produced by one of those renames."""
+import json
 import os
 import re
 
@@ -217,6 +218,11 @@ def _renames():
 def test_fork_renames_match_overlays_and_reference():
     ren = _renames()
     assert len(ren) == 10
+    # where each renamed declaration sits in the reference, recorded by tests/golden/make_golden.py
+    with open(os.path.join(ROOT, "tests", "golden", "fork_declarations.json")) as f:
+        decl = json.load(f)
+    assert sorted((p, o) for p, d in decl.items() for o in d) == sorted((p, o) for p, o, _ in ren), \
+        "go/fork.sh renames other declarations than tests/golden/fork_declarations.json records; rerun make_golden.py"
     produced = {}
     for path, old, new in ren:
         oldname = re.search(r"(\w+)\($", old).group(1)
@@ -228,9 +234,8 @@ def test_fork_renames_match_overlays_and_reference():
         text = "".join(open(os.path.join(pkg, f)).read() for f in os.listdir(pkg) if f.endswith("_hip.go"))
         assert re.search(r"^func\s+(\([^)]*\)\s+)?" + oldname + r"\(", text, flags=re.M), f"{pkg}: no overlay declares {oldname}"
         assert re.search(r"\b" + newname + r"\(", text), f"{pkg}: the overlay never calls {newname} (no small-input path)"
-        ref = os.path.join("/root/reference", path)
-        if os.path.exists(ref):   # in the authoring container only: the declaration line really exists in the reference
-            assert any(line.startswith(old) for line in open(ref)), f"{path}: `{old}` is not a declaration of the reference"
+        # the declaration line really exists in the reference
+        assert decl[path][old] and all(n >= 1 for n in decl[path][old]), f"{path}: `{old}` is not a declaration of the reference"
     # every *CPU identifier an overlay calls comes from a rename of ITS package
     for path in _overlay_files():
         pkg = os.path.relpath(os.path.dirname(path), GO)
