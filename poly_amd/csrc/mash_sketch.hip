@@ -56,9 +56,6 @@
 #ifndef PH_ABL
 #define PH_ABL 0
 #endif
-#ifndef PH_SELBINS
-#define PH_SELBINS 0 // EXPERIMENT (round 6, lever (a)): n > 0 = the slab pass counts the bottom-s's 2^n bins while it selects
-#endif
 #ifndef PH_SEL_ATOMIC
 #define PH_SEL_ATOMIC 0 // EXPERIMENT (round 6): 1 = a survivor's slot from a returning LDS increment on the wave's own counter
 #endif                  // (compare + shift per hash) instead of its ballot rank (compare + two mbcnt + shift-add)
@@ -80,7 +77,7 @@
 #define PH_SLAB_CF 0u // 0: the tile pass's capf
 #endif
 #ifndef PH_SLAB_WPE
-#define PH_SLAB_WPE PH_WPE
+#define PH_SLAB_WPE 8 // eight workgroups per CU fit its LDS (18.5 KB at k = 21, s = 1000)
 #endif
 
 namespace polyhip {
@@ -152,6 +149,10 @@ struct Smem {
     uint32_t *binned; // counting-sort scratch
     uint32_t *misc;   // [0] count  [1] tau  [3] survivors  [4..8) wave totals
     uint32_t *lut;    // [256] premix(byte) ^ k for a single tail byte (k % 4 == 1)
+    // bottom_s_fast only: its 16-bit bins, and the list of big bins (listcap entries)
+    uint32_t *bins;
+    uint32_t *biglist;
+    uint32_t listcap;
 };
 
 // ---- exact bottom-s ------------------------------------------------------------------
@@ -168,8 +169,8 @@ struct Smem {
 constexpr uint32_t BIG_BIN = 32;
 constexpr uint32_t BIG_LIST_CAP = 512; // the list lives in seqb (>= WAVES * WTW / 4 dwords); more big bins than that: per-element ranking
 
-template <class Emit>
-__device__ __attribute__((noinline)) void rank_big_bins(const uint32_t *__restrict__ binned, const uint32_t *__restrict__ bins,
+template <class Bin, class Emit>
+__device__ __attribute__((noinline)) void rank_big_bins(const uint32_t *__restrict__ binned, const Bin *__restrict__ bins,
                                               const uint32_t *__restrict__ biglist, uint32_t nbig, uint32_t s, Emit emit)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -556,89 +557,95 @@ constexpr uint32_t BS_MARGIN = (PH_BS_WIN + 3u) & ~3u; // dwords kept free befor
         if (PH_ABL != 21)      \
             __syncthreads();   \
     } while (0)
-template <bool FIN, bool SELB = false>
+// The bins are 16-BIT counters, two per dword (bin b in half b & 1 of dword b >> 1, i.e. element b of a uint16_t view):
+// there is no 16-bit LDS atomic, so a count adds 1 << 16 * (b & 1) to the dword.  Exact because no count and no bin
+// end exceeds C <= capf < 65,536 (s <= 8192 here), so a half never carries into its neighbour.  2048 bins are 4 KB,
+// which lets the slab pass keep its whole bottom-s inside the LDS its rings leave free after the last slab.
+template <bool FIN>
 __device__ void bottom_s_fast(const Smem &sm, uint32_t s, uint32_t tau, uint32_t C, uint32_t nbf_log2,
                               uint32_t *__restrict__ outp, const uint32_t *__restrict__ src, uint32_t first,
-                              uint32_t step, uint32_t cnt, uint32_t *__restrict__ selbins = nullptr)
+                              uint32_t step, uint32_t cnt)
 {
     const int tid = threadIdx.x;
     auto fin = [](uint32_t h) { return FIN ? h ^ (h >> 16) : h; };
-    uint32_t *bins = sm.P;
-    const uint32_t nbf = 1u << nbf_log2; // 1024 or 2048 bins, whatever fits in the P region
+    uint32_t *bins = sm.bins;
+    const uint16_t *bins16 = reinterpret_cast<const uint16_t *>(bins);
     const int sig = 32 - __builtin_clz(tau | 1u);
     const int shift = sig > (int)nbf_log2 ? sig - (int)nbf_log2 : 0;
-    // a thread owns `per` = 4 or 8 consecutive bins = one or two 16-byte words (the caller's barrier freed P)
-    uint4 *bins4 = reinterpret_cast<uint4 *>(bins);
-    const int q4 = (int)(nbf / (4 * THREADS)); // 1 or 2
-    if (!SELB) {
-        for (int q = 0; q < q4; ++q)
-            bins4[q4 * tid + q] = make_uint4(0, 0, 0, 0);
-        if (tid == 0)
-            sm.misc[8] = 0; // bins with more than BIG_BIN values
-    }
+    auto one = [](uint32_t b) { return 1u << ((b & 1u) << 4); }; // +1 on bin b's half of its dword
+    // a thread owns nbf / THREADS = 8 or 4 consecutive bins (2048 or 1024 bins) = one 16- or 8-byte word
+    const bool wide = nbf_log2 == 11u;
+    if (wide)
+        reinterpret_cast<uint4 *>(bins)[tid] = make_uint4(0, 0, 0, 0);
+    else
+        reinterpret_cast<uint2 *>(bins)[tid] = make_uint2(0, 0);
+    if (tid == 0)
+        sm.misc[8] = 0; // bins with more than BIG_BIN values
     if (PH_BS_WIN) { // the window pass below reads PH_BS_WIN entries on either side of binned[0, C): nothing there may count
         if (tid < PH_BS_WIN)
             sm.binned[-1 - tid] = 0u;
         else if (tid < 2 * PH_BS_WIN)
             sm.binned[C + (uint32_t)tid - PH_BS_WIN] = 0xFFFFFFFFu;
     }
-    if (!SELB) // (SELB: the select counted the bins, the caller zeroed misc[8] before its barrier; the margins are read two barriers on)
-        BS_SYNC();
+    BS_SYNC();
     // the loops over candidates are unrolled (PH_BS_U) so that the LDS round trips of a thread's elements overlap instead of
     // queueing behind each other.  A wave's segment holds ~300 survivors and the sorted buffer ~1200, i.e. 4.7 per lane / per
     // thread, so by four every loop runs a second, nearly empty trip -- but by five or six the kernel measures the same
     // (1.46-1.50 ms per 100k reads all three, profiles/r05_k1_bottom_s_unroll.log): the bottom-s is its five barriers and
     // the atomics' round trips, not its instruction count.
-    if (!SELB) {
-        for (uint32_t i0 = first; i0 < cnt; i0 += BSU * step) {
-            uint32_t h[BSU];
+    for (uint32_t i0 = first; i0 < cnt; i0 += BSU * step) {
+        uint32_t h[BSU];
 #pragma unroll
-            for (int u = 0; u < BSU; ++u)
-                h[u] = i0 + u * step < cnt ? fin(src[i0 + u * step]) : 0u;
+        for (int u = 0; u < BSU; ++u)
+            h[u] = i0 + u * step < cnt ? fin(src[i0 + u * step]) : 0u;
 #pragma unroll
-            for (int u = 0; u < BSU; ++u)
-                if (i0 + u * step < cnt)
-                    atomicAdd(&bins[h[u] >> shift], 1u);
-        }
-        BS_SYNC();
+        for (int u = 0; u < BSU; ++u)
+            if (i0 + u * step < cnt) {
+                const uint32_t b = h[u] >> shift;
+                atomicAdd(&bins[b >> 1], one(b));
+            }
     }
+    BS_SYNC();
     {
-        uint4 v[2];
-        uint32_t sum = 0;
-        uint4 *cnt4 = SELB ? reinterpret_cast<uint4 *>(selbins) : bins4;
-        for (int q = 0; q < 2; ++q) {
-            v[q] = q < q4 ? cnt4[q4 * tid + q] : make_uint4(0, 0, 0, 0);
-            if (SELB && q < q4)
-                cnt4[q4 * tid + q] = make_uint4(0, 0, 0, 0); // ready for the next read's select
-            sum += v[q].x + v[q].y + v[q].z + v[q].w;
+        uint32_t w[4];
+        if (wide) {
+            const uint4 t = reinterpret_cast<const uint4 *>(bins)[tid];
+            w[0] = t.x, w[1] = t.y, w[2] = t.z, w[3] = t.w;
+        } else {
+            const uint2 t = reinterpret_cast<const uint2 *>(bins)[tid];
+            w[0] = t.x, w[1] = t.y, w[2] = 0u, w[3] = 0u;
+        }
+        uint32_t c[8], sum = 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            c[i] = (w[i >> 1] >> (16 * (i & 1))) & 0xFFFFu;
+            sum += c[i];
         }
         const uint32_t incl = wave_incl_scan(sum);
         if ((tid & 63) == 63)
             sm.misc[4 + (tid >> 6)] = incl;
         BS_SYNC();
         uint32_t run = incl - sum;
-        for (int w = 0; w < (tid >> 6); ++w)
-            run += sm.misc[4 + w];
-        for (int q = 0; q < 2; ++q) {
-            if (q < q4) {
-                uint4 o; // start of each bin
-                o.x = run;
-                o.y = o.x + v[q].x;
-                o.z = o.y + v[q].y;
-                o.w = o.z + v[q].z;
-                run = o.w + v[q].w;
-                bins4[q4 * tid + q] = o;
-                if (max(max(v[q].x, v[q].y), max(v[q].z, v[q].w)) > BIG_BIN) { // rare: repeated k-mers
-                    const uint32_t cnt4[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
+        for (int w8 = 0; w8 < (tid >> 6); ++w8)
+            run += sm.misc[4 + w8];
+        const uint32_t b0 = (uint32_t)tid << (wide ? 3 : 2);
 #pragma unroll
-                    for (int c = 0; c < 4; ++c)
-                        if (cnt4[c] > BIG_BIN) {
-                            const uint32_t slot = atomicAdd(&sm.misc[8], 1u);
-                            if (slot < BIG_LIST_CAP)
-                                sm.seqb[slot] = (uint32_t)(4 * (q4 * tid + q) + c);
-                        }
+        for (int i = 0; i < 4; ++i) { // start of each bin
+            w[i] = run | ((run + c[2 * i]) << 16);
+            run += c[2 * i] + c[2 * i + 1];
+        }
+        if (wide)
+            reinterpret_cast<uint4 *>(bins)[tid] = make_uint4(w[0], w[1], w[2], w[3]);
+        else
+            reinterpret_cast<uint2 *>(bins)[tid] = make_uint2(w[0], w[1]);
+        if (max(max(max(c[0], c[1]), max(c[2], c[3])), max(max(c[4], c[5]), max(c[6], c[7]))) > BIG_BIN) { // rare: repeated k-mers
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+                if (c[i] > BIG_BIN) {
+                    const uint32_t slot = atomicAdd(&sm.misc[8], 1u);
+                    if (slot < sm.listcap)
+                        sm.biglist[slot] = b0 + (uint32_t)i;
                 }
-            }
         }
     }
     BS_SYNC();
@@ -649,8 +656,10 @@ __device__ void bottom_s_fast(const Smem &sm, uint32_t s, uint32_t tau, uint32_t
             h[u] = i0 + u * step < cnt ? fin(src[i0 + u * step]) : 0u;
 #pragma unroll
         for (int u = 0; u < BSU; ++u)
-            if (i0 + u * step < cnt)
-                at[u] = atomicAdd(&bins[h[u] >> shift], 1u);
+            if (i0 + u * step < cnt) {
+                const uint32_t b = h[u] >> shift;
+                at[u] = (atomicAdd(&bins[b >> 1], one(b)) >> ((b & 1u) << 4)) & 0xFFFFu;
+            }
 #pragma unroll
         for (int u = 0; u < BSU; ++u)
             if (i0 + u * step < cnt)
@@ -658,12 +667,12 @@ __device__ void bottom_s_fast(const Smem &sm, uint32_t s, uint32_t tau, uint32_t
     }
     BS_SYNC();
     const uint32_t nbig = sm.misc[8];
-    const bool by_waves = nbig <= BIG_LIST_CAP; // else the list is incomplete: rank every element the slow way
+    const bool by_waves = nbig <= sm.listcap; // else the list is incomplete: rank every element the slow way
     // an element against its whole bin: start of the bin + the values of the bin that sort before it (ties by slot:
     // duplicates keep distinct ranks)
     auto rank_in_bin = [&](uint32_t j, uint32_t hv) {
         const uint32_t b = hv >> shift;
-        const uint32_t start = b ? bins[b - 1] : 0u, end = bins[b];
+        const uint32_t start = b ? bins16[b - 1] : 0u, end = bins16[b];
         if (start >= s || (by_waves && end - start > BIG_BIN)) // (a whole wave places a big bin's values: rank_big_bins)
             return;
         uint32_t pos = start;
@@ -713,8 +722,8 @@ __device__ void bottom_s_fast(const Smem &sm, uint32_t s, uint32_t tau, uint32_t
         rank_in_bin(j, sm.binned[j]);
 #endif
     if (by_waves && nbig) // rare: keep it out of line (and out of the common path's register budget)
-        rank_big_bins(sm.binned, bins, sm.seqb, nbig, s, [outp](uint32_t pos, uint32_t hv) { outp[pos] = hv; }); // by VALUE: a reference would
-                                                                                                            // park `outp` in scratch, per read
+        rank_big_bins(sm.binned, bins16, sm.biglist, nbig, s, [outp](uint32_t pos, uint32_t hv) { outp[pos] = hv; }); // by VALUE: a reference
+                                                                                                                   // would park `outp` in scratch, per read
 }
 
 struct ReadView {
@@ -756,6 +765,9 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(PH_WPE,
     sm.binned = sm.cand + capf + BS_MARGIN; // (bottom_s_fast's window reads BS_MARGIN entries on either side)
     sm.misc = sm.binned + capf + BS_MARGIN;
     sm.lut = sm.misc + 16;
+    sm.bins = sm.P;      // 16-bit bins in P
+    sm.biglist = sm.seqb; // seqb is idle while the candidates are sorted
+    sm.listcap = BIG_LIST_CAP;
 
     const uint32_t k = KS > 0 ? (uint32_t)KS : k_rt;
     const int tid = threadIdx.x;
@@ -837,7 +849,6 @@ template <int KS> struct Slabs {
     static constexpr int DUPD = NBLK + 2; // dwords [0, DUPD) of the ring live again at [128, 128 + DUPD)
     const uint32_t *__restrict__ gdw;
     uint32_t gsh;
-    int64_t gbytes;
     uint32_t *__restrict__ seqb; // physical index = ring index + 1; [0] repeats ring dword 127
     uint32_t *__restrict__ P;    // quads [0, 128) + quads [0, NBLK) again at [128, 128 + NBLK)
     const uint32_t *__restrict__ lut;
@@ -847,6 +858,7 @@ template <int KS> struct Slabs {
     // u is wave-uniform, so the slab's base is a scalar pointer and the lane adds a constant offset.  Slabs below
     // `u_inside` lie, with one dword beyond them, inside the read: no per-lane guard.
     uint32_t u_inside;
+    uint32_t gb32; // gbytes mod 2^32
     __device__ __forceinline__ void gload(uint32_t u, uint32_t &lo, uint32_t &hi) const
     {
         const uint32_t *__restrict__ slab = gdw + (uint64_t)u * 64;
@@ -856,10 +868,12 @@ template <int KS> struct Slabs {
             if (gsh)
                 hi = slab[lane + 1];
         } else {
-            const int64_t left = gbytes - (int64_t)u * 256; // bytes of the view from this slab on (may be <= 0)
-            lo = (int64_t)lane * 4 < left ? slab[lane] : 0u;
+            // bytes of the view from this slab on (may be <= 0).  Past u_inside it lies within a few hundred of 0, so
+            // it is exact in 32 bits (wrapping), and no 64-bit per-lane value has to stay live across the slab loop
+            const int left = (int)(gb32 - u * 256u);
+            lo = lane * 4 < left ? slab[lane] : 0u;
             if (gsh)
-                hi = (int64_t)(lane + 1) * 4 < left ? slab[lane + 1] : 0u;
+                hi = (lane + 1) * 4 < left ? slab[lane + 1] : 0u;
         }
     }
 
@@ -917,9 +931,12 @@ template <int KS> struct Slabs {
             asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(off[1]) : "v"(two), "v"(tb));
             asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(off[2]) : "v"(two), "v"(tb));
             asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3" : "=v"(off[3]) : "v"(two), "v"(tb));
+            // The table is the first thing in the dynamic LDS, which starts at address 0 because the kernel has no static
+            // LDS (tests/test_k1_slab_resources_cpu.py checks both).  Addressed from 0 rather than from `lut`, whose address
+            // hipcc only learns at link time and so adds as a v_add_u32 of 0 in front of every read
 #pragma unroll
             for (int c = 0; c < 4; ++c)
-                h[c] ^= *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(lut) + off[c]);
+                h[c] ^= *reinterpret_cast<const __attribute__((address_space(3))) uint32_t *>((uintptr_t)off[c]);
         } else if (TAIL) {
             constexpr uint32_t tailmask = 0xFFFFFFFFu >> (32 - 8 * (TAIL ? TAIL : 1));
             const uint32_t d0 = t[0], d1 = t[1];
@@ -949,8 +966,7 @@ template <int KS> struct Slabs {
 // survivors of the lane's 4 hashes -> the wave's own segment; `cnt` is wave-uniform (kept in a scalar register)
 template <bool PARTIAL>
 __device__ __forceinline__ void append_own(uint32_t *__restrict__ seg, uint32_t capw, uint32_t &cnt, const uint32_t (&h)[4],
-                                           uint32_t nvalid, uint32_t tauq, uint32_t *__restrict__ selbins = nullptr,
-                                           uint32_t selshift = 0)
+                                           uint32_t nvalid, uint32_t tauq)
 {
     bool a[4];
     uint64_t m[4];
@@ -984,11 +1000,8 @@ __device__ __forceinline__ void append_own(uint32_t *__restrict__ seg, uint32_t 
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             uint32_t *__restrict__ at = seg + base; // scalar: the lane only adds its rank among the survivors
-            if (a[c]) {
+            if (a[c])
                 at[__builtin_amdgcn_mbcnt_hi((uint32_t)(m[c] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m[c], 0u))] = h[c];
-                if (PH_SELBINS) // the bin is in the top 16 bits, which fmix32's last xor-shift leaves alone
-                    atomicAdd(&selbins[h[c] >> selshift], 1u);
-            }
             base += n[c];
         }
     }
@@ -997,14 +1010,12 @@ __device__ __forceinline__ void append_own(uint32_t *__restrict__ seg, uint32_t 
 // all slabs of one read; returns this wave's survivor count (wave-uniform; > capw: the segment overflowed)
 template <int KS>
 __device__ __forceinline__ uint32_t run_slabs(const Smem &sm, const ReadView &rv, uint32_t n_seq_dw, uint32_t n_P_w,
-                                              uint32_t *__restrict__ seg, uint32_t capw, uint32_t tauq,
-                                              uint32_t *__restrict__ selbins = nullptr, uint32_t selshift = 0)
+                                              uint32_t *__restrict__ seg, uint32_t capw, uint32_t tauq)
 {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); // scalar: slab indices and ring bases stay in SGPRs
     Slabs<KS> S;
     S.gdw = rv.gdw;
     S.gsh = rv.gsh;
-    S.gbytes = rv.gbytes;
     S.seqb = sm.seqb + wave * n_seq_dw;
     S.P = sm.P + wave * n_P_w;
     S.lut = sm.lut;
@@ -1014,6 +1025,9 @@ __device__ __forceinline__ uint32_t run_slabs(const Smem &sm, const ReadView &rv
     const uint32_t spw = (nslab + WAVES - 1) / WAVES;
     const uint32_t a = (uint32_t)wave * spw, b = a + spw < nslab ? a + spw : nslab; // this wave hashes slabs [a, b)
     S.u_inside = rv.gbytes >= 65 * 4 ? (uint32_t)(((rv.gbytes >> 2) - 65) >> 6) + 1u : 0u;
+    S.gb32 = (uint32_t)rv.gbytes;
+    // slabs [0, nfull) hold 256 windows each; the last one, if any, holds rem (1..255)
+    const uint32_t nfull = (uint32_t)(rv.nwin >> 8), rem = (uint32_t)rv.nwin & 255u;
     uint32_t cnt = 0;
 #if PH_SEL_ATOMIC
     capw -= 1u; // the last entry of the segment is the wave's slot counter
@@ -1056,42 +1070,44 @@ __device__ __forceinline__ uint32_t run_slabs(const Smem &sm, const ReadView &rv
             wave_sync();
             S.template hash<0>(h);
         }
-        const int64_t left = rv.nwin - ((int64_t)i << 8); // windows of the read from this slab on
         if (PH_ABL == 11) { // keeps the hashes alive, stores (almost) never
             if ((h[0] ^ h[1] ^ h[2] ^ h[3]) == 0x12345u)
                 seg[0] = h[0];
-        } else if (__builtin_expect(left >= 256, 1)) {
-            append_own<false>(seg, capw, cnt, h, 4u, tauq, selbins, selshift);
+        } else if (__builtin_expect(i < nfull, 1)) { // (scalar compare: 32-bit, so that no 64-bit count lives in VGPRs)
+            append_own<false>(seg, capw, cnt, h, 4u, tauq);
         } else {
-            const int64_t mine = left - 4 * S.lane;
-            append_own<true>(seg, capw, cnt, h, mine <= 0 ? 0u : (mine < 4 ? (uint32_t)mine : 4u), tauq, selbins, selshift);
+            const int mine = (int)rem - 4 * S.lane;
+            append_own<true>(seg, capw, cnt, h, mine <= 0 ? 0u : (mine < 4 ? (uint32_t)mine : 4u), tauq);
         }
         wave_sync(); // the rings are rewritten by the next step
     }
     return cnt;
 }
 
+// LDS (dwords): lut [256] | span [n_span] | misc [16] | WAVES candidate segments [capw].  The span holds the WAVES byte
+// rings and the WAVES premix rings while the slabs run, and the bottom-s after the last one: 2^nbf_log2 16-bit bins,
+// binned[capf] with its margins, and the big-bin list in what is left.  At k = 21, s = 1000 that is 18,944 B: eight
+// workgroups per CU, which the kernel's registers (<= 64 VGPRs, <= 80 SGPRs) allow too.
 template <int KS>
 __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(PH_SLAB_WPE, 8))) void sketch_slab_kernel(
     const uint8_t *__restrict__ seqs, const uint64_t *__restrict__ offs, uint64_t nseq, uint32_t s, uint32_t *__restrict__ out,
-    uint32_t n_seq_dw, uint32_t n_P_w, uint32_t n_P, uint32_t capw, uint32_t capf, uint32_t nbf_log2)
+    uint32_t n_seq_dw, uint32_t n_P_w, uint32_t n_span, uint32_t capw, uint32_t capf, uint32_t nbf_log2)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem_raw[];
     Smem sm;
     sm.lut = smem_raw;                 // first, so that a tail byte's entry is at LDS address 4 * byte (no base to add)
     sm.seqb = smem_raw + 256;          // WAVES rings of n_seq_dw
-    sm.P = sm.seqb + WAVES * n_seq_dw; // WAVES rings of n_P_w (whole region doubles as `bins`)
-    sm.cand = sm.P + n_P;              // WAVES segments of capw
-    sm.binned = sm.cand + WAVES * capw + BS_MARGIN;
-    sm.misc = sm.binned + capf + BS_MARGIN;
+    sm.P = sm.seqb + WAVES * n_seq_dw; // WAVES rings of n_P_w
+    sm.bins = sm.seqb;                 // after the slabs
+    sm.binned = sm.bins + ((1u << nbf_log2) >> 1) + BS_MARGIN;
+    sm.biglist = sm.binned + capf + BS_MARGIN;
+    sm.listcap = (uint32_t)(sm.seqb + n_span - sm.biglist); // >= capf / (BIG_BIN + 1) + 1 (plan()): the list cannot overflow
+    sm.misc = sm.seqb + n_span;
+    sm.cand = sm.misc + 16;            // WAVES segments of capw
     constexpr uint32_t k = (uint32_t)KS;
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     sm.lut[tid] = premix((uint32_t)tid) ^ k; // THREADS == 256; visible after the first barrier
     uint32_t *seg = sm.cand + wave * capw;
-    uint32_t *selbins = sm.misc + 16; // (PH_SELBINS only: 2^nbf_log2 counters behind everything else)
-    if (PH_SELBINS)
-        for (uint32_t b = tid; b < (1u << nbf_log2); b += THREADS)
-            selbins[b] = 0u;
 
     for (uint64_t r = blockIdx.x; r < nseq; r += gridDim.x) {
         const ReadView rv = view(seqs, offs, r, k);
@@ -1108,14 +1124,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(PH_SLAB
                 tauq = (uint32_t)((target << 32) / (uint64_t)rv.nwin) | 0xFFFFu;
         }
         __syncthreads(); // the previous read is done with LDS
-        uint32_t selshift = 0;
-        if (PH_SELBINS) {
-            const int sig = 32 - __builtin_clz(tauq | 1u);
-            selshift = sig > (int)nbf_log2 ? (uint32_t)(sig - (int)nbf_log2) : 0u; // bottom_s_fast's shift (experiment: needs >= 16)
-            if (tid == 0)
-                sm.misc[8] = 0;
-        }
-        const uint32_t cw = PH_ABL == 14 ? tauq >> 31 : run_slabs<KS>(sm, rv, n_seq_dw, n_P_w, seg, capw, tauq, selbins, selshift);
+        const uint32_t cw = PH_ABL == 14 ? tauq >> 31 : run_slabs<KS>(sm, rv, n_seq_dw, n_P_w, seg, capw, tauq);
         if ((tid & 63) == 0)
             sm.misc[10 + wave] = cw;
         __syncthreads();
@@ -1128,15 +1137,10 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(PH_SLAB
         const uint32_t C = c0 + c1 + c2 + c3;
         const bool ok = max(max(c0, c1), max(c2, c3)) <= capw - (PH_SEL_ATOMIC ? 1u : 0u) && C >= s && C <= capf; // enough survivors, none lost
         if (ok)
-            bottom_s_fast<true, PH_SELBINS != 0>(sm, s, tauq, C, nbf_log2, outp, seg, (uint32_t)(tid & 63), 64u, cw, selbins);
-        else {
-            if (PH_SELBINS) // (a read that is handed on leaves its counts behind)
-                for (uint32_t b = tid; b < (1u << nbf_log2); b += THREADS)
-                    selbins[b] = 0u;
-            if (tid == 0) {
-                outp[0] = MARK0;
-                outp[1] = MARK1;
-            }
+            bottom_s_fast<true>(sm, s, tauq, C, nbf_log2, outp, seg, (uint32_t)(tid & 63), 64u, cw);
+        else if (tid == 0) {
+            outp[0] = MARK0;
+            outp[1] = MARK1;
         }
     }
 }
@@ -1371,7 +1375,7 @@ __global__ __launch_bounds__(THREADS) void sketch_tiny_kernel(const uint8_t *__r
 }
 
 struct Launch {
-    uint32_t n_seq_dw, n_P_w, n_P, n_P_fast, nbf_log2, nbf_log2_slab, capf, cap, capw, capf_slab;
+    uint32_t n_seq_dw, n_P_w, n_P, n_P_fast, nbf_log2, nbf_log2_slab, capf, cap, capw, capf_slab, n_span;
     size_t smem_fast, smem_general, smem_slab;
 };
 
@@ -1409,12 +1413,15 @@ static Launch plan(uint32_t k, uint32_t s)
         L.capw = (exp_w + PH_SLAB_CW * rw + 8u + 63u) & ~63u;
         L.capf_slab = PH_SLAB_CF ? ((target + PH_SLAB_CF * rt + 8u + 63u) & ~63u) : L.capf;
     }
-    L.smem_slab = ((size_t)WAVES * L.n_seq_dw + L.n_P_fast + 16 + 256 + (size_t)WAVES * L.capw + (size_t)L.capf_slab + 2 * BS_MARGIN) * 4;
-    L.nbf_log2_slab = L.nbf_log2;
-    if (PH_SELBINS) {
-        L.nbf_log2_slab = PH_SELBINS;
-        L.smem_slab += (size_t)4 << PH_SELBINS;
+    // the span: the rings, or after the slabs 2048 16-bit bins + binned[capf_slab] and its margins + a big-bin list long
+    // enough for every bin of more than BIG_BIN of the <= capf_slab survivors, whichever is larger
+    L.nbf_log2_slab = 11;
+    {
+        const uint32_t rings = WAVES * (L.n_seq_dw + L.n_P_w);
+        const uint32_t sorted = ((1u << L.nbf_log2_slab) >> 1) + L.capf_slab + 2 * BS_MARGIN + L.capf_slab / (BIG_BIN + 1) + 1;
+        L.n_span = rings > sorted ? rings : sorted;
     }
+    L.smem_slab = ((size_t)256 + L.n_span + 16 + (size_t)WAVES * L.capw) * 4;
 #ifdef PH_LDS_PAD
     L.smem_slab += PH_LDS_PAD; // occupancy probe
 #endif
@@ -1444,7 +1451,7 @@ static int launch(const uint8_t *d_seqs, const uint64_t *d_offs, uint64_t n, uin
             PH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(slab), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)L.smem_slab));
             hipLaunchKernelGGL(slab, dim3(persistent_grid(L.smem_slab, n)), dim3(THREADS), L.smem_slab, st, d_seqs, d_offs, n, s,
-                               d_out, L.n_seq_dw, L.n_P_w, L.n_P_fast, L.capw, L.capf_slab, L.nbf_log2_slab);
+                               d_out, L.n_seq_dw, L.n_P_w, L.n_span, L.capw, L.capf_slab, L.nbf_log2_slab);
         }
     }
     if (!slabs) {

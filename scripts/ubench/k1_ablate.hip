@@ -33,6 +33,6 @@ int main()
     static const char *what[] = {"full kernel", "no premix", "1 chain block of 5", "no tail/fmix", "no select stores", "no bottom_s", "no global loads", "2 workgroups per CU",
                                  "", "", "", "slab: stage + premix + hash only", "slab: no bottom-s", "", "slab: per-read prologue + barriers only", "slab: no premix", "slab: 1 chain block of 5", "slab: fmix32 cut to one multiply"};
     const char *w = PH_ABL < (int)(sizeof what / sizeof what[0]) ? what[PH_ABL] : PH_ABL == 21 ? "slab: bottom-s without barriers" : PH_ABL == 22 ? "slab: bottom-s without its rank pass" : "";
-    printf("PH_ABL=%d PH_BS_WIN=%d PH_SELBINS=%d %-40s %.3f ms per 100k reads\n", PH_ABL, PH_BS_WIN, PH_SELBINS, w, ms);
+    printf("PH_ABL=%d PH_BS_WIN=%d %-40s %.3f ms per 100k reads\n", PH_ABL, PH_BS_WIN, w, ms);
     return 0;
 }
