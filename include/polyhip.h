@@ -474,7 +474,7 @@ int polyhip_sw_last_packed_lanes(void);
  * 257..1024 symbols with its sweep on a BYTE PROFILE of the pair in LDS (eight instructions per cell instead of sixteen):
  * gap <= -1, smax - gap <= 127, smin - gap >= -128, the planes of four pairs fit 64 KB (shared or per-pair B;
  * POLYHIP_TB_WAVE8=0: path 4 instead; testing aid).  Paths 4 and 7 walk out of the wave's registers on the scalar unit
- * (reads of at most 1024 symbols; POLYHIP_TB_WALKREG=0: a global load per step as before; testing aid). */
+ * (reads of at most 1024 symbols). */
 int polyhip_sw_traceback_last_path(void);
 /* 1 when that call's byte-profile kernel (path 1) ran in its half-float form (gfx950: packed halves, two bands of rows
  * per lane, nine instructions per cell pair instead of eighteen) -- taken under the packed score pass's condition

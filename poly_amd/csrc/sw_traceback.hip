@@ -45,6 +45,10 @@ namespace k3t {
 
 constexpr int THREADS = 256;
 
+// the bits of the traceback kernels' `wide` argument
+constexpr int TB_WIDE = 1;     // the conservative per-pair window for every pair (POLYHIP_TB_WIDE=1, testing aid)
+constexpr int TB_DEFERRED = 2; // the caller is the fused entry point, whose score pass may have deferred end cells
+
 static thread_local int g_tb_last_path = 0;
 static thread_local int g_tb_last_half = 0;
 static thread_local int g_nw_last_path = 0;
@@ -181,7 +185,7 @@ __global__ __launch_bounds__(THREADS) void tb_kernel(const uint8_t *__restrict__
         }
     }
     const bool work = active && eA > 0 && eB > 0 && lenA <= RA;
-    const uint32_t mycols = work ? pair_window(wcols, eA, score ? score[pair] : 0, smax, gap, wide) : 0u;
+    const uint32_t mycols = work ? pair_window(wcols, eA, score ? score[pair] : 0, smax, gap, wide & TB_WIDE) : 0u;
     const uint32_t c_s = (work && eB > mycols) ? eB - mycols + 1u : 1u; // first column (1-based) of my window
     const uint32_t ncol = work ? eB - c_s + 1u : 0u;
 
@@ -369,12 +373,12 @@ __global__ __launch_bounds__(THREADS) void tb_prof_kernel(
     // The score pass may have left the end cell to this kernel (k3p::SW_END_DEFERRED): eB is then the last column of
     // the ONE block of four columns that holds the maximum, and the first cell worth M in row-major order is found
     // while that block -- the last of the window -- is swept.  The window is sized with lenA for the unknown end row.
-    // `wide` bit 1: the caller is the fused entry point, whose score pass may have deferred end cells; without it the
+    // TB_DEFERRED: the caller is the fused entry point, whose score pass may have deferred end cells; without it the
     // end arrays are the caller's read-only input, a sentinel (or any row beyond the read) there means "no alignment"
-    const bool locate = active && (wide & 2) && eA == k3p::SW_END_DEFERRED;
+    const bool locate = active && (wide & TB_DEFERRED) && eA == k3p::SW_END_DEFERRED;
     const uint32_t rowsA = locate ? lenA : eA;
     const bool work = active && rowsA > 0 && rowsA <= lenA && eB > 0 && M > 0 && lenA <= RA;
-    const uint32_t mycols = work ? min(wcols + 4u, pair_window(wcols, rowsA, M, smax, gap, wide & 1) + (locate ? 4u : 0u)) : 0u;
+    const uint32_t mycols = work ? min(wcols + 4u, pair_window(wcols, rowsA, M, smax, gap, wide & TB_WIDE) + (locate ? 4u : 0u)) : 0u;
     const uint32_t c_s = (work && eB > mycols) ? eB - mycols + 1u : 1u; // first column (1-based) of my window
     const uint32_t jb0 = (c_s - 1u) & ~3u;                               // 0-based, on a block boundary
     const uint32_t nblk = work ? (eB - jb0 + TBU - 1) / TBU : 0u;        // <= nblk_alloc
@@ -706,10 +710,10 @@ typedef uint32_t tbf_u32x2 __attribute__((ext_vector_type(2)));
 
 // The walk over the half-float kernels' direction words (tb_prof16_kernel: LP = 1 lane per pair, two bands; tb_prof16x2_kernel:
 // LP = 2, four bands): `dirw` = the pair's (first) lane's piece inside its wave's buffer, jb0 / lag = where the pair's
-// window began and how many iterations its wave started ahead of it.  COHERENT: the words were stored by this very wave a
-// moment ago (agent-scope loads); else by a kernel that has finished (plain loads: a block's four columns are one 32-byte
-// piece, the second to fourth step of a diagonal hit L1).  P16 / codeL may live in LDS or in global memory.
-template <int RB, int LP, bool COHERENT, bool BYTAB = false> // BYTAB: P16 = halves [code of a][byte of b] (every pair its own B)
+// window began and how many iterations its wave started ahead of it.  The words were stored by this very wave a moment ago,
+// so they are read with agent-scope loads.  P16 / codeL may live in LDS or in global memory.  (The walk as a kernel of its
+// own behind each sweep was measured slower: 9.4 against 8.5 ms per 1M config-4 reads, profiles/r04_tb_walk.log.)
+template <int RB, int LP, bool BYTAB = false> // BYTAB: P16 = halves [code of a][byte of b] (every pair its own B)
 __device__ __forceinline__ uint32_t tbf_walk(const uint32_t *__restrict__ dirw, uint32_t jb0, uint32_t lag, uint32_t eA, uint32_t eB,
                                              int M, int gap, int ncp, const uint16_t *P16, const uint8_t *codeL,
                                              const uint8_t *__restrict__ ap, const uint8_t *__restrict__ B,
@@ -737,19 +741,11 @@ __device__ __forceinline__ uint32_t tbf_walk(const uint32_t *__restrict__ dirw, 
         const uint32_t key = (tt * NG + g) * 2u + (LP == 2 ? (band >> 1) : 0u);
         if (key != pkey) {
             const uint32_t *pp = dirw + (LP == 2 ? (band >> 1) * 8u : 0u) + ((size_t)tt * NG + g) * (64 * 8);
-            if (COHERENT) { // stored by this very wave a moment ago
-                const uint64_t *p8 = reinterpret_cast<const uint64_t *>(pp);
-                pc0 = __hip_atomic_load(p8 + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                pc1 = __hip_atomic_load(p8 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                pc2 = __hip_atomic_load(p8 + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                pc3 = __hip_atomic_load(p8 + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else {
-                const uint4 q0 = reinterpret_cast<const uint4 *>(pp)[0], q1 = reinterpret_cast<const uint4 *>(pp)[1];
-                pc0 = (uint64_t)q0.x | ((uint64_t)q0.y << 32);
-                pc1 = (uint64_t)q0.z | ((uint64_t)q0.w << 32);
-                pc2 = (uint64_t)q1.x | ((uint64_t)q1.y << 32);
-                pc3 = (uint64_t)q1.z | ((uint64_t)q1.w << 32);
-            }
+            const uint64_t *p8 = reinterpret_cast<const uint64_t *>(pp);
+            pc0 = __hip_atomic_load(p8 + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            pc1 = __hip_atomic_load(p8 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            pc2 = __hip_atomic_load(p8 + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            pc3 = __hip_atomic_load(p8 + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             pkey = key;
         }
         const uint32_t ar = a0 + r;
@@ -794,34 +790,6 @@ __device__ __forceinline__ uint32_t tbf_walk(const uint32_t *__restrict__ dirw, 
     return len;
 }
 
-// The walk as a kernel of its own (round 4; POLYHIP_TB_SPLITWALK=1 -- it lost, see traceback_impl): a thread per pair, no
-// LDS, under 30 registers, eight waves per SIMD.  The sweep kernel leaves (jb0, lag) per pair in `walkinfo` ((0 | 1, ~0):
-// nothing to walk, alnLen = 0 | ~0).
-template <int RB, int LP>
-__global__ __launch_bounds__(256) void tb_walk16_kernel(const uint8_t *__restrict__ A, const uint64_t *__restrict__ offA, uint64_t pair0,
-                                                       uint64_t pair1, const uint8_t *__restrict__ B,
-                                                       const uint16_t *__restrict__ prof16, const uint8_t *__restrict__ codeA, int ncodes,
-                                                       int gap, const uint32_t *__restrict__ endA, const uint32_t *__restrict__ endB,
-                                                       const int64_t *__restrict__ score, uint32_t nblk_alloc,
-                                                       const uint32_t *__restrict__ dirbuf, const uint2 *__restrict__ walkinfo,
-                                                       uint8_t *__restrict__ alnA, uint8_t *__restrict__ alnB,
-                                                       uint32_t *__restrict__ alnLen, uint32_t stride)
-{
-    constexpr int NG = (RB + 15) / 16;
-    constexpr uint32_t PPW = 64 / LP; // pairs of one sweep wave
-    const uint64_t pl = (uint64_t)blockIdx.x * 256 + threadIdx.x, pair = pair0 + pl;
-    if (pair >= pair1)
-        return;
-    const uint2 info = walkinfo[pl];
-    if (info.y == 0xFFFFFFFFu) {
-        alnLen[pair] = info.x ? 0xFFFFFFFFu : 0u;
-        return;
-    }
-    const uint32_t *dirw = dirbuf + (pl / PPW) * ((size_t)nblk_alloc * TBU * NG * 2 * 64) + (uint32_t)(pl % PPW) * (LP * 8u);
-    alnLen[pair] = tbf_walk<RB, LP, false>(dirw, info.x, info.y, endA[pair], endB[pair], (int)score[pair], gap, ncodes + 1, prof16, codeA,
-                                           A + offA[pair], B, alnA + pair * stride, alnB + pair * stride, stride);
-}
-
 template <int RB>
 __global__ __launch_bounds__(THREADS, 2) void tb_prof16_kernel(
     const uint8_t *__restrict__ A, const uint64_t *__restrict__ offA, uint64_t pair0, uint64_t pair1,
@@ -829,7 +797,7 @@ __global__ __launch_bounds__(THREADS, 2) void tb_prof16_kernel(
     const uint8_t *__restrict__ codeA, int ncodes, int gap, uint32_t *__restrict__ endA,
     uint32_t *__restrict__ endB, uint32_t *__restrict__ err, const int64_t *__restrict__ score, int smax,
     uint32_t wcols, int wide, uint32_t nblk_alloc, uint32_t *__restrict__ dirbuf, uint8_t *__restrict__ alnA,
-    uint8_t *__restrict__ alnB, uint32_t *__restrict__ alnLen, uint32_t stride, uint2 *__restrict__ walkinfo)
+    uint8_t *__restrict__ alnB, uint32_t *__restrict__ alnLen, uint32_t stride)
 {
     static_assert(RB % 4 == 0 && RB <= 76, "RB");
     constexpr int RA = 2 * RB;
@@ -863,10 +831,10 @@ __global__ __launch_bounds__(THREADS, 2) void tb_prof16_kernel(
             M = score[pair];
         }
     }
-    const bool locate = active && (wide & 2) && eA == k3p::SW_END_DEFERRED; // as tb_prof_kernel
+    const bool locate = active && (wide & TB_DEFERRED) && eA == k3p::SW_END_DEFERRED; // as tb_prof_kernel
     const uint32_t rowsA = locate ? lenA : eA;
     const bool work = active && rowsA > 0 && rowsA <= lenA && eB > 0 && M > 0 && lenA <= RA;
-    const uint32_t mycols = work ? min(wcols + 4u, pair_window(wcols, rowsA, M, smax, gap, wide & 1) + (locate ? 4u : 0u)) : 0u;
+    const uint32_t mycols = work ? min(wcols + 4u, pair_window(wcols, rowsA, M, smax, gap, wide & TB_WIDE) + (locate ? 4u : 0u)) : 0u;
     const uint32_t c_s = (work && eB > mycols) ? eB - mycols + 1u : 1u;
     const uint32_t jb0 = (c_s - 1u) & ~3u;
     const uint32_t nblk = work ? (eB - jb0 + TBU - 1) / TBU : 0u; // <= nblk_alloc - 1
@@ -1039,14 +1007,10 @@ __global__ __launch_bounds__(THREADS, 2) void tb_prof16_kernel(
         endA[pair] = 0u;
         endB[pair] = 0u;
     }
-    if (walkinfo) { // the walk is a kernel of its own (tb_walk16_kernel)
-        walkinfo[pair - pair0] = (work && !lost) ? make_uint2(jb0, lag) : make_uint2((rowsA > 0 && lenA > RA) ? 1u : 0u, 0xFFFFFFFFu);
-        return;
-    }
-    if (work && !lost && !(wide & 4)) { // (wide & 4: POLYHIP_TB_NOWALK=1, ablation probe -- what does the sweep cost on its own?)
+    if (work && !lost) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); // my own stores, read back by me
-        len = tbf_walk<RB, 1, true>(dirw, jb0, lag, eA, eB, (int)M, gap, ncp, reinterpret_cast<const uint16_t *>(P), codeL, ap, B,
-                                    alnA + pair * stride, alnB + pair * stride, stride);
+        len = tbf_walk<RB, 1>(dirw, jb0, lag, eA, eB, (int)M, gap, ncp, reinterpret_cast<const uint16_t *>(P), codeL, ap, B,
+                              alnA + pair * stride, alnB + pair * stride, stride);
     }
     alnLen[pair] = (active && rowsA > 0 && lenA > RA) ? 0xFFFFFFFFu : len;
 }
@@ -1069,7 +1033,6 @@ __global__ __launch_bounds__(THREADS, 2) void tb_pair16_kernel(
 {
     static_assert(RB % 4 == 0 && RB <= 76, "RB");
     constexpr uint32_t SLOT = 56; // bytes per lane and slot: seven codes (ncodes + the pad code <= 7)
-    uint2 *const walkinfo = nullptr;
     constexpr int RA = 2 * RB;
     constexpr int NG = (RB + 15) / 16;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_tbf[];
@@ -1111,10 +1074,10 @@ __global__ __launch_bounds__(THREADS, 2) void tb_pair16_kernel(
             M = score[pair];
         }
     }
-    const bool locate = active && (wide & 2) && eA == k3p::SW_END_DEFERRED; // as tb_prof_kernel
+    const bool locate = active && (wide & TB_DEFERRED) && eA == k3p::SW_END_DEFERRED; // as tb_prof_kernel
     const uint32_t rowsA = locate ? lenA : eA;
     const bool work = active && rowsA > 0 && rowsA <= lenA && eB > 0 && eB <= lenB && M > 0 && lenA <= RA;
-    const uint32_t mycols = work ? min(wcols + 4u, pair_window(wcols, rowsA, M, smax, gap, wide & 1) + (locate ? 4u : 0u)) : 0u;
+    const uint32_t mycols = work ? min(wcols + 4u, pair_window(wcols, rowsA, M, smax, gap, wide & TB_WIDE) + (locate ? 4u : 0u)) : 0u;
     const uint32_t c_s = (work && eB > mycols) ? eB - mycols + 1u : 1u;
     const uint32_t jb0 = (c_s - 1u) & ~3u;
     const uint32_t nblk = work ? (eB - jb0 + TBU - 1) / TBU : 0u; // <= nblk_alloc - 1
@@ -1307,14 +1270,10 @@ __global__ __launch_bounds__(THREADS, 2) void tb_pair16_kernel(
         endA[pair] = 0u;
         endB[pair] = 0u;
     }
-    if (walkinfo) { // the walk is a kernel of its own (tb_walk16_kernel)
-        walkinfo[pair - pair0] = (work && !lost) ? make_uint2(jb0, lag) : make_uint2((rowsA > 0 && lenA > RA) ? 1u : 0u, 0xFFFFFFFFu);
-        return;
-    }
-    if (work && !lost && !(wide & 4)) { // (wide & 4: POLYHIP_TB_NOWALK=1, ablation probe -- what does the sweep cost on its own?)
+    if (work && !lost) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); // my own stores, read back by me
-        len = tbf_walk<RB, 1, true, true>(dirw, jb0, lag, eA, eB, (int)M, gap, ncp, H16, codeL, ap, B, alnA + pair * stride,
-                                          alnB + pair * stride, stride);
+        len = tbf_walk<RB, 1, true>(dirw, jb0, lag, eA, eB, (int)M, gap, ncp, H16, codeL, ap, B, alnA + pair * stride,
+                                    alnB + pair * stride, stride);
     }
     alnLen[pair] = (active && rowsA > 0 && lenA > RA) ? 0xFFFFFFFFu : len;
 }
@@ -1337,7 +1296,7 @@ __global__ __launch_bounds__(THREADS, 2) void tb_prof16x2_kernel(
     const uint8_t *__restrict__ codeA, int ncodes, int gap, uint32_t *__restrict__ endA,
     uint32_t *__restrict__ endB, uint32_t *__restrict__ err, const int64_t *__restrict__ score, int smax,
     uint32_t wcols, int wide, uint32_t nblk_alloc, uint32_t *__restrict__ dirbuf, uint8_t *__restrict__ alnA,
-    uint8_t *__restrict__ alnB, uint32_t *__restrict__ alnLen, uint32_t stride, uint2 *__restrict__ walkinfo)
+    uint8_t *__restrict__ alnB, uint32_t *__restrict__ alnLen, uint32_t stride)
 {
     static_assert(RB % 16 == 0 && RB <= 64, "RB");
     constexpr int RL = 2 * RB; // rows per lane
@@ -1374,10 +1333,10 @@ __global__ __launch_bounds__(THREADS, 2) void tb_prof16x2_kernel(
         }
     }
     // everything below is the same in both lanes of a pair (its rows apart)
-    const bool locate = active && (wide & 2) && eA == k3p::SW_END_DEFERRED; // as tb_prof_kernel
+    const bool locate = active && (wide & TB_DEFERRED) && eA == k3p::SW_END_DEFERRED; // as tb_prof_kernel
     const uint32_t rowsA = locate ? lenA : eA;
     const bool work = active && rowsA > 0 && rowsA <= lenA && eB > 0 && M > 0 && lenA <= RA;
-    const uint32_t mycols = work ? min(wcols + 4u, pair_window(wcols, rowsA, M, smax, gap, wide & 1) + (locate ? 4u : 0u)) : 0u;
+    const uint32_t mycols = work ? min(wcols + 4u, pair_window(wcols, rowsA, M, smax, gap, wide & TB_WIDE) + (locate ? 4u : 0u)) : 0u;
     const uint32_t c_s = (work && eB > mycols) ? eB - mycols + 1u : 1u;
     const uint32_t jb0 = (c_s - 1u) & ~3u;
     const uint32_t nblk = work ? (eB - jb0 + TBU - 1) / TBU : 0u; // <= nblk_alloc - 3
@@ -1558,14 +1517,10 @@ __global__ __launch_bounds__(THREADS, 2) void tb_prof16x2_kernel(
         endA[pair] = 0u;
         endB[pair] = 0u;
     }
-    if (walkinfo) { // the walk is a kernel of its own (tb_walk16_kernel)
-        walkinfo[pair - pair0] = (work && !lost) ? make_uint2(jb0, lag) : make_uint2((rowsA > 0 && lenA > RA) ? 1u : 0u, 0xFFFFFFFFu);
-        return;
-    }
-    if (work && !lost && !(wide & 4)) {
+    if (work && !lost) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); // this wave's own stores (my partner's included), read back by me
-        len = tbf_walk<RB, 2, true>(dirw, jb0, lag, eA, eB, (int)M, gap, ncp, reinterpret_cast<const uint16_t *>(P), codeL, ap, B,
-                                    alnA + pair * stride, alnB + pair * stride, stride);
+        len = tbf_walk<RB, 2>(dirw, jb0, lag, eA, eB, (int)M, gap, ncp, reinterpret_cast<const uint16_t *>(P), codeL, ap, B,
+                              alnA + pair * stride, alnB + pair * stride, stride);
     }
     alnLen[pair] = (rowsA > 0 && lenA > RA) ? 0xFFFFFFFFu : len;
 }
@@ -1644,8 +1599,8 @@ __global__ __launch_bounds__(THREADS) void tb_wave_kernel(
         // The score pass may have left the end cell to this kernel (k3p::SW_END_DEFERRED, byte-profile form only): eB is then
         // the last column of the only 4-column block that holds the maximum, the window is sized for the whole read (the end
         // row is not known yet) and four columns longer, and the sweep notes the first cell worth M in row-major order
-        const bool locate = P8 && LOC && (wide & 2) && eA == k3p::SW_END_DEFERRED;
-        const uint32_t mycols = min(wcols + 4u, pair_window(wcols, locate ? lenA : eA, M, smax, gap, wide & 1) + (locate ? 4u : 0u));
+        const bool locate = P8 && LOC && (wide & TB_DEFERRED) && eA == k3p::SW_END_DEFERRED;
+        const uint32_t mycols = min(wcols + 4u, pair_window(wcols, locate ? lenA : eA, M, smax, gap, wide & TB_WIDE) + (locate ? 4u : 0u));
         const uint32_t c_s = eB > mycols ? eB - mycols + 1u : 1u; // first column (1-based) of the window
         const uint32_t ncol = eB - c_s + 1u;
         uint32_t besti = 0xFFFFFFFFu, bestj = 0u; // locate: the smallest row with a cell worth M, its first column (window-relative)
@@ -1886,8 +1841,7 @@ __global__ __launch_bounds__(THREADS) void tb_wave_kernel(
         uint32_t i = eA, j = eB;
         int h = (int)M;
         const uint32_t *dbase = dirbuf + wslot * ((size_t)(wcols + 67u) * 64 * NWL);
-        if (wide & 4) { // POLYHIP_TB_NOWALK=1: ablation probe -- what does the sweep cost on its own?
-        } else if (R <= 16 && !(wide & 8)) {
+        if constexpr (R <= 16) {
             // Round 5: the walk out of the wave's REGISTERS, steered by the scalar unit.  A step of the plain walk below is
             // one dependent HBM round trip (272 KB of direction words per 1 kb pair: nothing of it stays in a cache) and
             // ~60 vector instructions that every lane executes for lane 0's two bytes.  Here the wave fetches, in ONE
@@ -1989,47 +1943,40 @@ __global__ __launch_bounds__(THREADS) void tb_wave_kernel(
                 outB[stride - 1 - pos] = (uint8_t)myb;
             }
             len = wlen;
-        } else
-        while (h > 0 && i > 0 && j >= c_s && len < stride) {
-            const uint32_t r = i - 1u, l = r / R, k = r % R;
-            const uint32_t s = (j - c_s) + l;
-            const uint32_t *wp = dbase + ((size_t)(R <= 16 ? s / WavePack<R>::SP : s) * 64 + l) * NWL;
-            uint32_t gbit, lbit;
-            if (R <= 16) {
-                const uint32_t w = __hip_atomic_load(wp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >>
-                                   ((s % WavePack<R>::SP) * WavePack<R>::FB);
-                gbit = (w >> (R - 1 - k)) & 1u;
-                lbit = (w >> (WavePack<R>::BITS + R - 1 - k)) & 1u;
-            } else {
+        } else { // R > 16: the plain walk, one dependent load of direction words per step
+            while (h > 0 && i > 0 && j >= c_s && len < stride) {
+                const uint32_t r = i - 1u, l = r / R, k = r % R;
+                const uint32_t s = (j - c_s) + l;
+                const uint32_t *wp = dbase + ((size_t)s * 64 + l) * NWL;
                 const uint32_t g = k >> 5, bit = 31u - (k & 31u);
-                gbit = (__hip_atomic_load(wp + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> bit) & 1u;
-                lbit = (__hip_atomic_load(wp + NG + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> bit) & 1u;
+                const uint32_t gbit = (__hip_atomic_load(wp + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> bit) & 1u;
+                const uint32_t lbit = (__hip_atomic_load(wp + NG + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> bit) & 1u;
+                const uint8_t sa = ap[r], sb = B[j - 1u];
+                uint8_t ca, cb;
+                if (gbit == 0u) { // align.go:215-219
+                    const uint32_t ka = cA[sa], kb = cB[sb];
+                    h -= T[(ka == 0xFFu ? (uint32_t)(na - 1) : ka) * (uint32_t)nb + (kb == 0xFFu ? (uint32_t)(nb - 1) : kb)];
+                    ca = sa;
+                    cb = sb;
+                    --i;
+                    --j;
+                } else if (lbit == 0u) { // :220-223
+                    h -= gap;
+                    ca = sa;
+                    cb = '-';
+                    --i;
+                } else { // :224-227
+                    h -= gap;
+                    ca = '-';
+                    cb = sb;
+                    --j;
+                }
+                if (lane == 0) {
+                    outA[stride - 1 - len] = ca;
+                    outB[stride - 1 - len] = cb;
+                }
+                ++len;
             }
-            const uint8_t sa = ap[r], sb = B[j - 1u];
-            uint8_t ca, cb;
-            if (gbit == 0u) { // align.go:215-219
-                const uint32_t ka = cA[sa], kb = cB[sb];
-                h -= T[(ka == 0xFFu ? (uint32_t)(na - 1) : ka) * (uint32_t)nb + (kb == 0xFFu ? (uint32_t)(nb - 1) : kb)];
-                ca = sa;
-                cb = sb;
-                --i;
-                --j;
-            } else if (lbit == 0u) { // :220-223
-                h -= gap;
-                ca = sa;
-                cb = '-';
-                --i;
-            } else { // :224-227
-                h -= gap;
-                ca = '-';
-                cb = sb;
-                --j;
-            }
-            if (lane == 0) {
-                outA[stride - 1 - len] = ca;
-                outB[stride - 1 - len] = cb;
-            }
-            ++len;
         }
     }
     if (lane == 0)
@@ -2063,7 +2010,7 @@ __global__ __launch_bounds__(THREADS) void tb_generic_kernel(
     }
     uint32_t len = 0;
     if (eA > 0 && eB > 0) {
-        const uint32_t mycols = pair_window(wcols, eA, score ? score[pair] : 0, smax, gap, wide);
+        const uint32_t mycols = pair_window(wcols, eA, score ? score[pair] : 0, smax, gap, wide & TB_WIDE);
         const uint32_t c_s = eB > mycols ? eB - mycols + 1u : 1u;
         const uint32_t ncol = eB - c_s + 1u;
         int32_t *Hc = hbuf + local;
@@ -2652,6 +2599,64 @@ static Plan plan(const polyhip_scoring *sc, uint32_t max_lenA, uint64_t lenB)
     return p;
 }
 
+// The traceback kernels by their public path numbers (polyhip_sw_traceback_last_path, KernelChoice::tb_path)
+enum TbPath {
+    PATH_PROF = 1,    // one reference, byte profile, a lane per pair (tb_prof_kernel; its half-float form tb_prof16_kernel)
+    PATH_TABLE = 2,   // <= 256 rows on the score table, a lane per pair (tb_kernel)
+    PATH_GENERIC = 3, // any length (tb_generic_kernel)
+    PATH_WAVE = 4,    // 153..4096 rows, one wave per pair on the score table (tb_wave_kernel<R>)
+    PATH_HALF2 = 5,   // 153..256 rows, one reference, packed halves, two lanes per pair (tb_prof16x2_kernel)
+    PATH_PAIR16 = 6,  // <= 152 rows, every pair its own B, packed halves (tb_pair16_kernel)
+    PATH_WAVE8 = 7,   // 257..1024 rows, one wave per pair on a byte profile of the pair (tb_wave_kernel<R, true>)
+};
+
+struct TbChoice {
+    int path;        // TbPath
+    bool half;       // on packed halves: paths 5 and 6, and path 1's half-float form
+    bool wide;       // the conservative per-pair window (POLYHIP_TB_WIDE=1)
+    bool overlap_ok; // chunks may alternate between two streams (not POLYHIP_TB_OVERLAP=0)
+    // only these kernels locate an end cell the score pass deferred (k3p::SW_END_DEFERRED)
+    bool finds_deferred() const { return path == PATH_PROF || path == PATH_HALF2 || path == PATH_WAVE8; }
+};
+
+// The kernel that traces a batch back, and the only place the traceback's testing aids are read.  shared_B: one reference
+// for every pair (no offB); score_given / have_B: the caller passes the scores / the B symbols.
+static TbChoice choose(const Plan &p, bool shared_B, bool score_given, bool have_B)
+{
+    TbChoice c{};
+    const bool known = score_given && have_B, one_ref = known && shared_B;
+    const bool f16 = !env_is("POLYHIP_TB_F16", '0'), prof = !env_is("POLYHIP_TB_PROF", '0');
+    // 153..256 rows: one wave per pair beats both lane-per-pair kernels (400k x 250 bp vs 5 kb: 34.9 ms against the
+    // byte-profile kernel's 44.0 at one wave per SIMD); they remain for tables too large for the wave kernel's LDS
+    const bool wave_ok = p.wave_r != 0 && known && !env_is("POLYHIP_TB_WAVE", '0'); // testing aid: no one-wave-per-pair traceback
+    if (one_ref && p.prof_ok && p.half2_ok && prof && f16 && !env_is("POLYHIP_TB_HALF2", '0'))
+        c.path = PATH_HALF2; // 400k x 250 bp vs 5 kb 34.5 ms -> see DESIGN.md (POLYHIP_TB_HALF2=0 or _F16=0: the wave kernel)
+    else if (one_ref && p.prof_ok && !(p.ra == 256 && wave_ok) && prof) // (POLYHIP_TB_PROF=0: the table kernel)
+        c.path = PATH_PROF;
+    else if ((p.ra == 0 || p.ra == 256) && wave_ok)
+        c.path = p.wave8_ok && !env_is("POLYHIP_TB_WAVE8", '0') ? PATH_WAVE8 : PATH_WAVE; // (POLYHIP_TB_WAVE8=0: path 4)
+    else if (known && !shared_B && p.pair16_ok && f16 && !env_is("POLYHIP_TB_PAIR16", '0')) // (_PAIR16=0 or _F16=0: the table kernel)
+        c.path = PATH_PAIR16;
+    else
+        c.path = p.ra ? PATH_TABLE : PATH_GENERIC;
+    // path 1's half-float two-band form (POLYHIP_TB_F16=0: the 32-bit one)
+    c.half = c.path == PATH_HALF2 || c.path == PATH_PAIR16 || (c.path == PATH_PROF && p.half_ok && f16);
+    c.wide = env_is("POLYHIP_TB_WIDE", '1');
+    c.overlap_ok = !env_is("POLYHIP_TB_OVERLAP", '0');
+    return c;
+}
+
+// sets the kernel's dynamic-LDS limit, launches it on workgroups of THREADS and returns the launch's error
+template <typename... Params, typename... Args>
+static hipError_t launch(void (*kern)(Params...), unsigned blocks, size_t smem, hipStream_t st, Args... args)
+{
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(THREADS), smem, st, args...);
+    return hipGetLastError();
+}
+
 // NW workspace per pair: the larger of the generic layout (2-bit codes + the H column) and the
 // register-tiled one (G and L words per 32 rows of RA)
 static inline int nw_ra(uint32_t max_lenA) { return max_lenA <= 64 ? 64 : 0; } // beyond: one wave per pair
@@ -2846,7 +2851,7 @@ size_t polyhip_sw_traceback_workspace_bytes(const polyhip_scoring *sc, uint64_t 
     // enough for every pair in one launch, capped at 8 GiB (the entry point loops over chunks);
     // never less than one workgroup's worth
     const uint64_t padded = (npairs + k3t::THREADS - 1) / k3t::THREADS * k3t::THREADS;
-    uint64_t want = padded * (p.per_pair + 8); // (+ 8: what the half-float kernels hand to their walk kernel per pair)
+    uint64_t want = padded * (p.per_pair + 8); // (+ 8 bytes per pair of slack, which callers' buffer and chunk sizes count on)
     const uint64_t cap = 8ull << 30, floor_ = (uint64_t)k3t::THREADS * (p.per_pair + 8);
     if (want > cap)
         want = cap / floor_ * floor_;
@@ -2855,105 +2860,63 @@ size_t polyhip_sw_traceback_workspace_bytes(const polyhip_scoring *sc, uint64_t 
     return (size_t)want + 256 + p.prof_bytes;
 }
 
-// would polyhip_sw_traceback_dev take the byte-profile kernel for this batch (score given, one shared reference)?
-// Only that kernel can find a deferred end cell.
-static bool traceback_uses_prof(const polyhip_scoring *sc, uint32_t max_lenA, uint64_t lenB)
-{
-    const k3t::Plan p = k3t::plan(sc, max_lenA, lenB);
-    const bool wave_ok = p.wave_r != 0 && !env_is("POLYHIP_TB_WAVE", '0');
-    if (p.prof_ok && p.half2_ok && !env_is("POLYHIP_TB_PROF", '0') && !env_is("POLYHIP_TB_F16", '0') && !env_is("POLYHIP_TB_HALF2", '0'))
-        return true; // its two-lanes-per-pair form (153..256 rows)
-    if (p.ra == 0 && wave_ok && p.wave8_ok && !env_is("POLYHIP_TB_WAVE8", '0'))
-        return true; // 257..1024 rows: the one-wave-per-pair kernel on a byte profile of the pair (path 7)
-    return p.prof_ok && !(p.ra == 256 && wave_ok) && !env_is("POLYHIP_TB_PROF", '0');
-}
-
 // endA / endB / err are rewritten only for pairs whose end cell the score pass deferred (k3p::SW_END_DEFERRED)
-static int traceback_impl(const polyhip_scoring *sc, const uint8_t *d_A, const uint64_t *d_offA, uint64_t npairs,
-                          uint32_t max_lenA, const uint8_t *d_B, const uint64_t *d_offB, uint64_t lenB,
-                          uint32_t *d_endA, uint32_t *d_endB, uint32_t *d_err,
-                          const int64_t *d_score, uint8_t *d_alnA,
-                          uint8_t *d_alnB, uint32_t *d_alnLen, uint32_t aln_stride, void *d_work, size_t work_bytes,
-                          polyhip_stream_t stream, int deferred)
+static int traceback_impl(const polyhip_scoring *sc, const k3t::Plan &p, const k3t::TbChoice &c, const uint8_t *d_A,
+                          const uint64_t *d_offA, uint64_t npairs, uint32_t max_lenA, const uint8_t *d_B,
+                          const uint64_t *d_offB, uint64_t lenB, uint32_t *d_endA, uint32_t *d_endB, uint32_t *d_err,
+                          const int64_t *d_score, uint8_t *d_alnA, uint8_t *d_alnB, uint32_t *d_alnLen, uint32_t aln_stride,
+                          void *d_work, size_t work_bytes, polyhip_stream_t stream, int deferred)
 {
-    PH_REQUIRE(sc, "polyhip_sw_traceback: null scoring");
+    using namespace k3t;
     if (npairs == 0)
         return POLYHIP_OK;
     PH_REQUIRE(d_offA && d_endA && d_endB && d_err && d_alnA && d_alnB && d_alnLen && d_work,
                "polyhip_sw_traceback: null pointer");
-    const k3t::Plan p = k3t::plan(sc, max_lenA, lenB);
     PH_REQUIRE(aln_stride >= p.win.stride, "polyhip_sw_traceback: aln_stride %u < %u (polyhip_sw_traceback_stride)",
                aln_stride, p.win.stride);
-    // 153..256 rows: one wave per pair beats both lane-per-pair kernels (400k x 250 bp vs 5 kb: 34.9 ms against the
-    // byte-profile kernel's 44.0 at one wave per SIMD); they remain for tables too large for the wave kernel's LDS
-    const bool wave_ok = p.wave_r != 0 && d_score != nullptr && d_B != nullptr &&
-                         !env_is("POLYHIP_TB_WAVE", '0'); // testing aid: no one-wave-per-pair traceback
-    // 153..256 rows against one reference on packed halves, two lanes per pair (path 5; POLYHIP_TB_HALF2=0 or
-    // POLYHIP_TB_F16=0: the one-wave-per-pair kernel as before, testing aids): 400k x 250 bp vs 5 kb 34.5 ms -> see DESIGN.md
-    const bool use_half2 = p.prof_ok && p.half2_ok && d_offB == nullptr && d_score != nullptr && d_B != nullptr &&
-                           !env_is("POLYHIP_TB_PROF", '0') && !env_is("POLYHIP_TB_F16", '0') && !env_is("POLYHIP_TB_HALF2", '0');
-    const bool use_prof = !use_half2 && p.prof_ok && d_offB == nullptr && d_score != nullptr && d_B != nullptr &&
-                          !(p.ra == 256 && wave_ok) &&
-                          !env_is("POLYHIP_TB_PROF", '0'); // testing aid: the table kernel for a shared reference
-    const bool use_wave = !use_half2 && !use_prof && (p.ra == 0 || p.ra == 256) && wave_ok;
-    // every pair its own B, rows <= 152, on packed halves (path 6; POLYHIP_TB_PAIR16=0 or POLYHIP_TB_F16=0: the table kernel)
-    const bool use_pair16 = p.pair16_ok && d_offB != nullptr && d_score != nullptr && d_B != nullptr && !use_wave &&
-                            !env_is("POLYHIP_TB_F16", '0') && !env_is("POLYHIP_TB_PAIR16", '0');
-    // 257..1024 rows: the one-wave-per-pair kernel's sweep on a byte profile of the pair (path 7; POLYHIP_TB_WAVE8=0: path 4)
-    const bool use_wave8 = use_wave && p.wave8_ok && !env_is("POLYHIP_TB_WAVE8", '0');
-    k3t::g_tb_last_path = use_pair16 ? 6 : use_half2 ? 5 : use_prof ? 1 : use_wave8 ? 7 : use_wave ? 4 : (p.ra ? 2 : 3);
-    // only the byte-profile kernels know a deferred end cell: the fused entry point decided with traceback_uses_prof();
-    // should the two conditions ever drift apart, fail here instead of walking from row 4e9
-    PH_REQUIRE(!deferred || use_prof || use_half2 || use_wave8, "polyhip_sw_align_batch: end cells were deferred but the byte-profile traceback is not taken");
-    // bit 0: the conservative per-pair window (POLYHIP_TB_WIDE=1, testing aid); bit 1: deferred end cells allowed
-    const int wide = (env_is("POLYHIP_TB_WIDE", '1') ? 1 : 0) | (deferred ? 2 : 0) | (env_is("POLYHIP_TB_NOWALK", '1') ? 4 : 0) |
-                     (env_is("POLYHIP_TB_WALKREG", '0') ? 8 : 0); // bit 3: the one-wave-per-pair kernel's plain walk (testing aid)
+    g_tb_last_path = c.path;
+    // the fused entry point deferred end cells only after the same choice said that its kernel finds them
+    PH_REQUIRE(!deferred || c.finds_deferred(), "polyhip_sw_align_batch: end cells were deferred but the byte-profile traceback is not taken");
+    const int wide = (c.wide ? TB_WIDE : 0) | (deferred ? TB_DEFERRED : 0);
     PH_REQUIRE(work_bytes >= p.prof_bytes + 256, "polyhip_sw_traceback: workspace too small (%zu B)", work_bytes);
     const size_t usable = (work_bytes - p.prof_bytes) & ~(size_t)255;
     // (the two-lane kernel's direction words take a quarter of the one-wave-per-pair kernel's, which sizes the workspace of
     // its row class: its chunks are cut by its own figure, or they would fill a third of the chip)
-    // POLYHIP_TB_SPLITWALK=1 (a measured alternative, kept as a cross-check): the half-float kernels' walk as a kernel of its
-    // own behind each sweep (tb_walk16_kernel; 8 bytes per pair behind a chunk's direction words carry (window start, wave
-    // lag) over).  With a thread per pair and eight waves per SIMD every pair of a chunk walks at once -- and a million
-    // half-written output lines are in flight against 32 MB of L2: 9.4 ms per 1M config-4 reads against 8.5 ms with the
-    // walk at the end of the sweep kernel (profiles/r04_tb_walk.log).
-    const bool half_any = use_half2 || (use_prof && p.half_ok && !env_is("POLYHIP_TB_F16", '0'));
-    const bool split_walk = half_any && env_is("POLYHIP_TB_SPLITWALK", '1');
-    const size_t per_pair = (use_half2 ? p.half2_per_pair : p.per_pair) + (split_walk ? 8 : 0);
-    uint64_t chunk = usable / per_pair / k3t::THREADS * k3t::THREADS;
+    const size_t per_pair = c.path == PATH_HALF2 ? p.half2_per_pair : p.per_pair;
+    uint64_t chunk = usable / per_pair / THREADS * THREADS;
     // A batch that needs several chunks of the direction workspace: the byte-profile and the one-wave-per-pair kernels take them through the two
     // HALVES of the workspace on two streams (the caller's and one of the library's), so that the end of one chunk --
     // waves finish at different times, and the walk that closes a wave's work waits on memory, not on issue -- overlaps
     // the sweeps of the next (one chunk after the other: the waves of a chunk were resident 67 % of its time,
     // profiles/r02_tbh_pmc_a.md).  POLYHIP_TB_OVERLAP=0: one chunk after the other (testing aid).
     const size_t half_bytes = (usable / 2) & ~(size_t)255; // where the upper half starts
-    const uint64_t half_chunk = half_bytes / per_pair / k3t::THREADS * k3t::THREADS;
-    const bool overlap = (use_prof || use_wave || use_half2) && npairs > chunk && half_chunk >= 16384 && !env_is("POLYHIP_TB_OVERLAP", '0');
+    const uint64_t half_chunk = half_bytes / per_pair / THREADS * THREADS;
+    const bool overlap = (c.path == PATH_PROF || c.path == PATH_WAVE || c.path == PATH_WAVE8 || c.path == PATH_HALF2) &&
+                         npairs > chunk && half_chunk >= 16384 && c.overlap_ok;
     if (overlap)
         chunk = half_chunk;
-    else if (use_prof && chunk >= 131072)
+    else if (c.path == PATH_PROF && chunk >= 131072)
         chunk = chunk / 131072 * 131072; // whole rounds of 256 CUs x 2 workgroups x 256 pairs
-    else if (use_half2 && chunk >= 65536)
+    else if (c.path == PATH_HALF2 && chunk >= 65536)
         chunk = chunk / 65536 * 65536; // the same with 128 pairs per workgroup
-    PH_REQUIRE(chunk >= (uint64_t)k3t::THREADS, "polyhip_sw_traceback: workspace too small (%zu B; %zu B per pair, >= %d pairs)",
-               work_bytes, per_pair, k3t::THREADS);
+    PH_REQUIRE(chunk >= (uint64_t)THREADS, "polyhip_sw_traceback: workspace too small (%zu B; %zu B per pair, >= %d pairs)",
+               work_bytes, per_pair, THREADS);
     hipStream_t st = as_stream(stream);
     const int na = sc->ncodes + 1, nb = sc->ncodesB + 1;
     int8_t *prof = static_cast<int8_t *>(d_work);
     void *d_dir = static_cast<uint8_t *>(d_work) + p.prof_bytes;
-    // half-float two-band form of the byte-profile kernel (POLYHIP_TB_F16=0: the 32-bit one, testing aid)
-    const bool use_half = use_prof && p.half_ok && !env_is("POLYHIP_TB_F16", '0');
-    k3t::g_tb_last_half = (use_half || use_half2 || use_pair16) ? 1 : 0;
-    if (use_half || use_half2) {
+    g_tb_last_half = c.half ? 1 : 0;
+    if (c.path == PATH_HALF2 || (c.path == PATH_PROF && c.half)) {
         const uint32_t n16 = (p.lenB_pad / 4 + 1) * (uint32_t)(sc->ncodes + 1);
-        hipLaunchKernelGGL(k3t::tb_profile16_kernel, dim3((n16 + 255) / 256), dim3(256), 0, st, d_B, (uint32_t)lenB, p.lenB_pad,
+        hipLaunchKernelGGL(tb_profile16_kernel, dim3((n16 + 255) / 256), dim3(256), 0, st, d_B, (uint32_t)lenB, p.lenB_pad,
                            sc->d_lutc, sc->ncodes, sc->ncodes + 1, reinterpret_cast<uint2 *>(prof));
         PH_HIP(hipGetLastError());
-    } else if (use_prof) {
-        hipLaunchKernelGGL(k3t::tb_profile_kernel, dim3((p.lenB_pad + 255) / 256), dim3(256), 0, st, d_B, (uint32_t)lenB,
+    } else if (c.path == PATH_PROF) {
+        hipLaunchKernelGGL(tb_profile_kernel, dim3((p.lenB_pad + 255) / 256), dim3(256), 0, st, d_B, (uint32_t)lenB,
                            p.lenB_pad, sc->d_lutc, sc->ncodes, p.cp, prof);
         PH_HIP(hipGetLastError());
     }
+    const uint2 *prof16 = reinterpret_cast<const uint2 *>(prof);
     const hipStream_t caller_st = st;
     AuxStream &aux = aux_stream(st);
     // whatever way this function is left after the fork, the caller's stream waits for the library's
@@ -2974,170 +2937,70 @@ static int traceback_impl(const polyhip_scoring *sc, const uint8_t *d_A, const u
     uint64_t chunk_no = 0;
     for (uint64_t p0 = 0; p0 < npairs; p0 += chunk, ++chunk_no) {
         const uint64_t p1 = std::min(npairs, p0 + chunk);
-        const unsigned blocks = (unsigned)((p1 - p0 + k3t::THREADS - 1) / k3t::THREADS);
+        const unsigned blocks = (unsigned)((p1 - p0 + THREADS - 1) / THREADS);
         uint32_t *dirbuf = static_cast<uint32_t *>(d_dir);
         if (overlap) { // odd chunks: the library's stream and the upper half of the workspace
             st = (chunk_no & 1) ? aux.s : caller_st;
             if (chunk_no & 1)
                 dirbuf = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(d_dir) + half_bytes);
         }
-        if (use_pair16) {
-#define PH_TBQ_LAUNCH(RB_)                                                                                             \
-    do {                                                                                                               \
-        auto kern = k3t::tb_pair16_kernel<RB_>;                                                                        \
-        PH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                   (int)p.pair16_smem));                                                               \
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(k3t::THREADS), p.pair16_smem, st, d_A, d_offA, p0, p1, d_B, d_offB, \
-                           sc->d_lutc, sc->d_codeA, sc->ncodes, (int)sc->gap, d_endA, d_endB, d_err, d_score,          \
-                           (int)sc->smax, p.win.wcols, wide, p.pair16_nblk_alloc, dirbuf, d_alnA, d_alnB, d_alnLen,    \
-                           aln_stride);                                                                                \
-    } while (0)
-            if (p.ra == 64)
-                PH_TBQ_LAUNCH(32);
-            else
-                PH_TBQ_LAUNCH(76);
-#undef PH_TBQ_LAUNCH
-            PH_HIP(hipGetLastError());
-            continue;
+        switch (c.path) {
+        case PATH_PAIR16:
+            PH_HIP(launch(p.ra == 64 ? tb_pair16_kernel<32> : tb_pair16_kernel<76>, blocks, p.pair16_smem, st, d_A, d_offA, p0, p1,
+                          d_B, d_offB, sc->d_lutc, sc->d_codeA, sc->ncodes, (int)sc->gap, d_endA, d_endB, d_err, d_score,
+                          (int)sc->smax, p.win.wcols, wide, p.pair16_nblk_alloc, dirbuf, d_alnA, d_alnB, d_alnLen, aln_stride));
+            break;
+        case PATH_WAVE:
+        case PATH_WAVE8: {
+            const unsigned wblocks = (unsigned)((p1 - p0 + THREADS / 64 - 1) / (THREADS / 64));
+            const int r = p.wave_r;
+            auto kern = r == 2 ? tb_wave_kernel<2> : r == 3 ? tb_wave_kernel<3> : r == 4 ? tb_wave_kernel<4> : r == 8 ? tb_wave_kernel<8>
+                      : r == 16 ? tb_wave_kernel<16> : r == 32 ? tb_wave_kernel<32> : tb_wave_kernel<64>;
+            if (c.path == PATH_WAVE8 && deferred)
+                kern = r == 8 ? tb_wave_kernel<8, true, true> : tb_wave_kernel<16, true, true>;
+            else if (c.path == PATH_WAVE8)
+                kern = r == 8 ? tb_wave_kernel<8, true, false> : tb_wave_kernel<16, true, false>;
+            PH_HIP(launch(kern, wblocks, c.path == PATH_WAVE8 ? p.wave8_smem : p.smem, st, d_A, d_offA, p0, p1, d_B, d_offB,
+                          sc->d_codeA, sc->d_codeB, sc->d_lutcc, na, nb, (int)sc->gap, d_endA, d_endB, d_err, d_score,
+                          (int)sc->smax, p.win.wcols, wide, dirbuf, d_alnA, d_alnB, d_alnLen, aln_stride));
+            break;
         }
-        if (use_wave) {
-            const unsigned wblocks = (unsigned)((p1 - p0 + k3t::THREADS / 64 - 1) / (k3t::THREADS / 64));
-#define PH_TBW_LAUNCH(R_)                                                                                             \
-    do {                                                                                                              \
-        auto kern = k3t::tb_wave_kernel<R_>;                                                                          \
-        PH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                   (int)p.smem));                                                                     \
-        hipLaunchKernelGGL(kern, dim3(wblocks), dim3(k3t::THREADS), p.smem, st, d_A, d_offA, p0, p1, d_B, d_offB,     \
-                           sc->d_codeA, sc->d_codeB, sc->d_lutcc, na, nb, (int)sc->gap, d_endA, d_endB, d_err, d_score, \
-                           (int)sc->smax, p.win.wcols, wide, dirbuf, d_alnA, d_alnB, d_alnLen, aln_stride);           \
-    } while (0)
-#define PH_TBW8_LAUNCH(R_)                                                                                            \
-    do {                                                                                                              \
-        auto kern = deferred ? k3t::tb_wave_kernel<R_, true, true> : k3t::tb_wave_kernel<R_, true, false>;            \
-        PH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                   (int)p.wave8_smem));                                                               \
-        hipLaunchKernelGGL(kern, dim3(wblocks), dim3(k3t::THREADS), p.wave8_smem, st, d_A, d_offA, p0, p1, d_B, d_offB, \
-                           sc->d_codeA, sc->d_codeB, sc->d_lutcc, na, nb, (int)sc->gap, d_endA, d_endB, d_err, d_score, \
-                           (int)sc->smax, p.win.wcols, wide, dirbuf, d_alnA, d_alnB, d_alnLen, aln_stride);           \
-    } while (0)
-            if (use_wave8 && p.wave_r == 8)
-                PH_TBW8_LAUNCH(8);
-            else if (use_wave8)
-                PH_TBW8_LAUNCH(16);
-            else if (p.wave_r == 2)
-                PH_TBW_LAUNCH(2);
-            else if (p.wave_r == 3)
-                PH_TBW_LAUNCH(3);
-            else if (p.wave_r == 4)
-                PH_TBW_LAUNCH(4);
-            else if (p.wave_r == 8)
-                PH_TBW_LAUNCH(8);
-            else if (p.wave_r == 16)
-                PH_TBW_LAUNCH(16);
-            else if (p.wave_r == 32)
-                PH_TBW_LAUNCH(32);
-            else
-                PH_TBW_LAUNCH(64);
-#undef PH_TBW_LAUNCH
-#undef PH_TBW8_LAUNCH
-            PH_HIP(hipGetLastError());
-            continue;
+        case PATH_HALF2: {
+            const unsigned blocks2 = (unsigned)((p1 - p0 + THREADS / 2 - 1) / (THREADS / 2));
+            PH_HIP(launch(tb_prof16x2_kernel<64>, blocks2, p.half_smem, st, d_A, d_offA, p0, p1, d_B, p.lenB_pad, prof16,
+                          sc->d_codeA, sc->ncodes, (int)sc->gap, d_endA, d_endB, d_err, d_score, (int)sc->smax, p.win.wcols, wide,
+                          p.nblk_alloc2, dirbuf, d_alnA, d_alnB, d_alnLen, aln_stride));
+            break;
         }
-        // (chunk = the pairs a (half) workspace holds: its direction words first, then the walk's 8 bytes per pair)
-        uint2 *walkinfo = split_walk ? reinterpret_cast<uint2 *>(reinterpret_cast<uint8_t *>(dirbuf) + chunk * (per_pair - 8)) : nullptr;
-        const unsigned wblocks16 = (unsigned)((p1 - p0 + 255) / 256);
-        const bool walk_now = split_walk && !(wide & 4);
-        if (use_half2) {
-            const unsigned blocks2 = (unsigned)((p1 - p0 + k3t::THREADS / 2 - 1) / (k3t::THREADS / 2));
-            auto kern = k3t::tb_prof16x2_kernel<64>;
-            PH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)p.half_smem));
-            hipLaunchKernelGGL(kern, dim3(blocks2), dim3(k3t::THREADS), p.half_smem, st, d_A, d_offA, p0, p1, d_B, p.lenB_pad,
-                               reinterpret_cast<const uint2 *>(prof), sc->d_codeA, sc->ncodes, (int)sc->gap, d_endA, d_endB, d_err,
-                               d_score, (int)sc->smax, p.win.wcols, wide, p.nblk_alloc2, dirbuf, d_alnA, d_alnB, d_alnLen,
-                               aln_stride, walkinfo);
-            if (walk_now)
-                hipLaunchKernelGGL((k3t::tb_walk16_kernel<64, 2>), dim3(wblocks16), dim3(256), 0, st, d_A, d_offA, p0, p1, d_B,
-                                   reinterpret_cast<const uint16_t *>(prof), sc->d_codeA, sc->ncodes, (int)sc->gap, d_endA, d_endB,
-                                   d_score, p.nblk_alloc2, dirbuf, walkinfo, d_alnA, d_alnB, d_alnLen, aln_stride);
-            PH_HIP(hipGetLastError());
-            continue;
-        }
-        if (use_half) {
-#define PH_TBH_LAUNCH(RB_)                                                                                             \
-    do {                                                                                                               \
-        auto kern = k3t::tb_prof16_kernel<RB_>;                                                                        \
-        PH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                   (int)p.half_smem));                                                                 \
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(k3t::THREADS), p.half_smem, st, d_A, d_offA, p0, p1, d_B,          \
-                           p.lenB_pad, reinterpret_cast<const uint2 *>(prof), sc->d_codeA, sc->ncodes, (int)sc->gap,   \
-                           d_endA, d_endB, d_err, d_score, (int)sc->smax, p.win.wcols, wide, p.nblk_alloc, dirbuf,     \
-                           d_alnA, d_alnB, d_alnLen, aln_stride, walkinfo);                                            \
-        if (walk_now)                                                                                                  \
-            hipLaunchKernelGGL((k3t::tb_walk16_kernel<RB_, 1>), dim3(wblocks16), dim3(256), 0, st, d_A, d_offA, p0, p1, d_B, \
-                               reinterpret_cast<const uint16_t *>(prof), sc->d_codeA, sc->ncodes, (int)sc->gap, d_endA,  \
-                               d_endB, d_score, p.nblk_alloc, dirbuf, walkinfo, d_alnA, d_alnB, d_alnLen, aln_stride);   \
-    } while (0)
-            if (p.ra == 64)
-                PH_TBH_LAUNCH(32);
-            else
-                PH_TBH_LAUNCH(76);
-#undef PH_TBH_LAUNCH
-            PH_HIP(hipGetLastError());
-            continue;
-        }
-        if (use_prof) {
-#define PH_TBP_LAUNCH(RA_, CP_)                                                                                        \
-    do {                                                                                                               \
-        auto kern = k3t::tb_prof_kernel<RA_, CP_>;                                                                     \
-        PH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                   (int)p.prof_smem));                                                                 \
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(k3t::THREADS), p.prof_smem, st, d_A, d_offA, p0, p1, d_B,           \
-                           p.lenB_pad, prof, sc->d_codeA, sc->ncodes, (int)sc->gap, d_endA, d_endB, d_err, d_score,    \
-                           (int)sc->smax, p.win.wcols, wide, p.nblk_alloc, dirbuf, d_alnA, d_alnB, d_alnLen, aln_stride);     \
-    } while (0)
-            if (p.ra == 64 && p.cp == 8)
-                PH_TBP_LAUNCH(64, 8);
-            else if (p.ra == 64)
-                PH_TBP_LAUNCH(64, 32);
-            else if (p.ra == 152 && p.cp == 8)
-                PH_TBP_LAUNCH(152, 8);
-            else if (p.ra == 152)
-                PH_TBP_LAUNCH(152, 32);
-            else if (p.cp == 8)
-                PH_TBP_LAUNCH(256, 8);
-            else
-                PH_TBP_LAUNCH(256, 32);
-#undef PH_TBP_LAUNCH
-            PH_HIP(hipGetLastError());
-            continue;
-        }
-#define PH_TB_LAUNCH(RA_)                                                                                              \
-    do {                                                                                                               \
-        auto kern = k3t::tb_kernel<RA_>;                                                                               \
-        PH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                   (int)p.smem));                                                                      \
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(k3t::THREADS), p.smem, st, d_A, d_offA, p0, p1, d_B, d_offB, lenB,  \
-                           sc->d_codeA, sc->d_codeB, sc->d_lutcc, na, nb, (int)sc->gap, d_endA, d_endB, d_err,         \
-                           d_score, (int)sc->smax, p.win.wcols, wide, dirbuf, d_alnA, d_alnB, d_alnLen, aln_stride);   \
-    } while (0)
-        if (p.ra == 64)
-            PH_TB_LAUNCH(64);
-        else if (p.ra == 152)
-            PH_TB_LAUNCH(152);
-        else if (p.ra == 256)
-            PH_TB_LAUNCH(256);
-        else {
-            const size_t nl = (size_t)blocks * k3t::THREADS;
+        case PATH_PROF:
+            if (c.half) {
+                PH_HIP(launch(p.ra == 64 ? tb_prof16_kernel<32> : tb_prof16_kernel<76>, blocks, p.half_smem, st, d_A, d_offA, p0, p1,
+                              d_B, p.lenB_pad, prof16, sc->d_codeA, sc->ncodes, (int)sc->gap, d_endA, d_endB, d_err, d_score,
+                              (int)sc->smax, p.win.wcols, wide, p.nblk_alloc, dirbuf, d_alnA, d_alnB, d_alnLen, aln_stride));
+            } else {
+                auto kern = p.ra == 64 ? (p.cp == 8 ? tb_prof_kernel<64, 8> : tb_prof_kernel<64, 32>)
+                          : p.ra == 152 ? (p.cp == 8 ? tb_prof_kernel<152, 8> : tb_prof_kernel<152, 32>)
+                                        : (p.cp == 8 ? tb_prof_kernel<256, 8> : tb_prof_kernel<256, 32>);
+                PH_HIP(launch(kern, blocks, p.prof_smem, st, d_A, d_offA, p0, p1, d_B, p.lenB_pad, prof, sc->d_codeA, sc->ncodes,
+                              (int)sc->gap, d_endA, d_endB, d_err, d_score, (int)sc->smax, p.win.wcols, wide, p.nblk_alloc, dirbuf,
+                              d_alnA, d_alnB, d_alnLen, aln_stride));
+            }
+            break;
+        case PATH_TABLE:
+            PH_HIP(launch(p.ra == 64 ? tb_kernel<64> : p.ra == 152 ? tb_kernel<152> : tb_kernel<256>, blocks, p.smem, st, d_A, d_offA,
+                          p0, p1, d_B, d_offB, lenB, sc->d_codeA, sc->d_codeB, sc->d_lutcc, na, nb, (int)sc->gap, d_endA, d_endB,
+                          d_err, d_score, (int)sc->smax, p.win.wcols, wide, dirbuf, d_alnA, d_alnB, d_alnLen, aln_stride));
+            break;
+        default: { // PATH_GENERIC
+            const size_t nl = (size_t)blocks * THREADS;
             int32_t *hbuf = static_cast<int32_t *>(d_dir);
             uint32_t *dirg = reinterpret_cast<uint32_t *>(hbuf + nl * max_lenA);
-            hipLaunchKernelGGL(k3t::tb_generic_kernel, dim3(blocks), dim3(k3t::THREADS), 0, st, d_A, d_offA, p0, p1, d_B,
-                               d_offB, lenB, sc->d_lut, (int)sc->gap, d_endA, d_endB, d_err, d_score, (int)sc->smax,
-                               p.win.wcols, wide, max_lenA, hbuf,
-                               dirg, d_alnA, d_alnB, d_alnLen, aln_stride);
+            hipLaunchKernelGGL(tb_generic_kernel, dim3(blocks), dim3(THREADS), 0, st, d_A, d_offA, p0, p1, d_B, d_offB, lenB,
+                               sc->d_lut, (int)sc->gap, d_endA, d_endB, d_err, d_score, (int)sc->smax, p.win.wcols, wide,
+                               max_lenA, hbuf, dirg, d_alnA, d_alnB, d_alnLen, aln_stride);
+            PH_HIP(hipGetLastError());
         }
-#undef PH_TB_LAUNCH
-        PH_HIP(hipGetLastError());
+        }
     }
     if (overlap) { // the caller's stream continues after both
         joiner.armed = false;
@@ -3153,8 +3016,11 @@ int polyhip_sw_traceback_dev(const polyhip_scoring *sc, const uint8_t *d_A, cons
                              uint8_t *d_alnB, uint32_t *d_alnLen, uint32_t aln_stride, void *d_work, size_t work_bytes,
                              polyhip_stream_t stream)
 {
+    PH_REQUIRE(sc, "polyhip_sw_traceback: null scoring");
+    const k3t::Plan p = k3t::plan(sc, max_lenA, lenB);
+    const k3t::TbChoice c = k3t::choose(p, d_offB == nullptr, d_score != nullptr, d_B != nullptr);
     // deferred = 0: the kernels never write the end arrays (a sentinel or an end row beyond the read means "no alignment")
-    return traceback_impl(sc, d_A, d_offA, npairs, max_lenA, d_B, d_offB, lenB, const_cast<uint32_t *>(d_endA),
+    return traceback_impl(sc, p, c, d_A, d_offA, npairs, max_lenA, d_B, d_offB, lenB, const_cast<uint32_t *>(d_endA),
                           const_cast<uint32_t *>(d_endB), const_cast<uint32_t *>(d_err), d_score, d_alnA, d_alnB, d_alnLen,
                           aln_stride, d_work, work_bytes, stream, 0);
 }
@@ -3172,15 +3038,54 @@ int polyhip_sw_align_batch_dev(const polyhip_scoring *sc, const uint8_t *d_A, co
     PH_REQUIRE(sc, "polyhip_sw_align_batch: null scoring");
     if (npairs == 0)
         return POLYHIP_OK;
-    const int want_defer = d_offB == nullptr && d_B != nullptr && traceback_uses_prof(sc, max_lenA, lenB) &&
+    // one choice for both passes: the score pass defers end cells only to a traceback kernel that finds them
+    const k3t::Plan p = k3t::plan(sc, max_lenA, lenB);
+    const k3t::TbChoice c = k3t::choose(p, d_offB == nullptr, d_score != nullptr, d_B != nullptr);
+    const int want_defer = d_offB == nullptr && d_B != nullptr && c.finds_deferred() &&
                            !env_is("POLYHIP_SW_FUSE", '0'); // testing aid: the two separate passes
     int deferred = 0;
     int rc = polyhip::k3::score_pass(sc, d_A, d_offA, npairs, max_lenA, d_B, d_offB, lenB, d_score, d_endA, d_endB, d_err, d_work,
                                      work_bytes, stream, want_defer, &deferred);
     if (rc != POLYHIP_OK)
         return rc;
-    return traceback_impl(sc, d_A, d_offA, npairs, max_lenA, d_B, d_offB, lenB, d_endA, d_endB, d_err, d_score, d_alnA, d_alnB,
-                          d_alnLen, aln_stride, d_tb_work, tb_work_bytes, stream, deferred);
+    return traceback_impl(sc, p, c, d_A, d_offA, npairs, max_lenA, d_B, d_offB, lenB, d_endA, d_endB, d_err, d_score, d_alnA,
+                          d_alnB, d_alnLen, aln_stride, d_tb_work, tb_work_bytes, stream, deferred);
+}
+
+// Pairs per chunk of the host pipelines below.  Chunks go through two slots, each with its own stream, outputs and
+// workspaces: the strings of chunk c cross PCIe (1 GB for config 4, as long as the kernels take) while chunk c + 1 is
+// being aligned.  The reads and the reference are on the device already (PairStage); a chunk is a window of offA.  Shared
+// reference only -- per-pair references keep the single shot.  Chunk = a multiple of 262,144 pairs (one full round of
+// the packed pass: 512 workgroups of 512 pairs), at most eight chunks, none when the strings are below ~200 MB.
+static uint64_t host_chunk_pairs(uint64_t npairs, uint32_t aln_stride, bool shared_B)
+{
+    uint64_t per = npairs;
+    if (!shared_B)
+        return per;
+    const uint64_t out_bytes = npairs * (2ull * aln_stride + 24), unit = 262144;
+    if (out_bytes >= (192ull << 20) && npairs > unit)
+        per = ((npairs + 7) / 8 + unit - 1) / unit * unit;
+    if (const char *e = getenv("POLYHIP_SW_HOST_CHUNKS")) // testing aid: 0 / 1 = single shot, 2..8 = that many chunks
+        if (e[0] >= '0' && e[0] <= '8') {
+            const uint64_t want = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)(e[0] - '0'), npairs));
+            per = (npairs + want - 1) / want;
+        }
+    return per;
+}
+
+// Enqueues the compaction of n pairs' strings out of their stride-byte slots: the lengths' block sums, their scan, and the
+// copy to outA / outB with the pairs' offsets in off[0 .. n] (base / base_ptr: see pack_copy_kernel).  bsum holds
+// n / PACK_BLOCK + 2 words.
+static hipError_t pack_strings(hipStream_t st, const uint32_t *alnLen, uint64_t n, uint64_t *bsum, uint64_t base,
+                               const uint8_t *slotA, const uint8_t *slotB, uint32_t stride, uint64_t *off, uint8_t *outA,
+                               uint8_t *outB, const uint64_t *base_ptr)
+{
+    const unsigned nb = (unsigned)((n + k3t::PACK_BLOCK - 1) / k3t::PACK_BLOCK);
+    hipLaunchKernelGGL(k3t::pack_sums_kernel, dim3(nb), dim3(256), 0, st, alnLen, n, bsum);
+    hipLaunchKernelGGL(k3t::pack_scan_kernel, dim3(1), dim3(1024), 0, st, bsum, nb);
+    hipLaunchKernelGGL(k3t::pack_copy_kernel, dim3(nb), dim3(256), 0, st, alnLen, n, bsum, base, slotA, slotB, stride, off, outA,
+                       outB, base_ptr);
+    return hipGetLastError();
 }
 
 // the single-device body: the calling thread's current device (a fan-out worker's, or the caller's own)
@@ -3203,24 +3108,8 @@ static int sw_align_batch_one(const polyhip_scoring *sc, const uint8_t *A, const
         return rc0;
     }
     const uint64_t maxA = in.maxA, maxB = in.maxB;
-    // Chunks of pairs through two slots, each with its own stream, outputs and workspaces: the strings of chunk c cross
-    // PCIe (1 GB for config 4, as long as the kernels take) while chunk c + 1 is being aligned.  The reads and the
-    // reference are on the device already (PairStage); a chunk is a window of offA.  Shared reference only -- per-pair
-    // references keep the single shot.
-    // Chunk = a multiple of 262,144 pairs (one full round of the packed pass: 512 workgroups of 512 pairs), at most
-    // eight chunks, none when the strings are below ~200 MB.
-    const uint64_t out_bytes = npairs * (2ull * aln_stride + 24);
-    uint64_t per = npairs;
-    if (!offB) {
-        const uint64_t unit = 262144;
-        if (out_bytes >= (192ull << 20) && npairs > unit)
-            per = ((npairs + 7) / 8 + unit - 1) / unit * unit;
-        if (const char *e = getenv("POLYHIP_SW_HOST_CHUNKS")) // testing aid: 0 / 1 = single shot, 2..8 = that many chunks
-            if (e[0] >= '0' && e[0] <= '8') {
-                const uint64_t want = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)(e[0] - '0'), npairs));
-                per = (npairs + want - 1) / want;
-            }
-    }
+    // chunks of pairs through two slots, each with its own stream, outputs and workspaces
+    const uint64_t per = host_chunk_pairs(npairs, aln_stride, offB == nullptr);
     const uint64_t nchunks = (npairs + per - 1) / per;
     struct Slot {
         DevBuf dscore, dea, deb, derr, dwork, dalA, dalB, dlen, dtb;
@@ -3339,24 +3228,8 @@ static int sw_align_packed_one(const polyhip_scoring *sc, const uint8_t *A, cons
     }
     const uint64_t maxA = in.maxA, maxB = in.maxB;
     const uint32_t aln_stride = polyhip_sw_traceback_stride(sc, (uint32_t)maxA, maxB);
-    // Chunks of pairs through two slots, each with its own stream, outputs and workspaces: the strings of chunk c cross
-    // PCIe (1 GB for config 4, as long as the kernels take) while chunk c + 1 is being aligned.  The reads and the
-    // reference are on the device already (PairStage); a chunk is a window of offA.  Shared reference only -- per-pair
-    // references keep the single shot.
-    // Chunk = a multiple of 262,144 pairs (one full round of the packed pass: 512 workgroups of 512 pairs), at most
-    // eight chunks, none when the strings are below ~200 MB.
-    const uint64_t out_bytes = npairs * (2ull * aln_stride + 24);
-    uint64_t per = npairs;
-    if (!offB) {
-        const uint64_t unit = 262144;
-        if (out_bytes >= (192ull << 20) && npairs > unit)
-            per = ((npairs + 7) / 8 + unit - 1) / unit * unit;
-        if (const char *e = getenv("POLYHIP_SW_HOST_CHUNKS")) // testing aid: 0 / 1 = single shot, 2..8 = that many chunks
-            if (e[0] >= '0' && e[0] <= '8') {
-                const uint64_t want = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)(e[0] - '0'), npairs));
-                per = (npairs + want - 1) / want;
-            }
-    }
+    // chunks of pairs through two slots, each with its own stream, outputs and workspaces
+    const uint64_t per = host_chunk_pairs(npairs, aln_stride, offB == nullptr);
     const uint64_t nchunks = (npairs + per - 1) / per;
     struct Slot {
         DevBuf dscore, dea, deb, derr, dwork, dalA, dalB, dlen, dtb, dpA, dpB, doff, dbsum;
@@ -3432,13 +3305,8 @@ static int sw_align_packed_one(const polyhip_scoring *sc, const uint8_t *A, cons
             base += t;
         }
         // compact chunk c's strings behind everything before it
-        const unsigned nb = (unsigned)((m + k3t::PACK_BLOCK - 1) / k3t::PACK_BLOCK);
-        hipLaunchKernelGGL(k3t::pack_sums_kernel, dim3(nb), dim3(256), 0, S.st, S.dlen.as<uint32_t>(), m, S.dbsum.as<uint64_t>());
-        hipLaunchKernelGGL(k3t::pack_scan_kernel, dim3(1), dim3(1024), 0, S.st, S.dbsum.as<uint64_t>(), nb);
-        hipLaunchKernelGGL(k3t::pack_copy_kernel, dim3(nb), dim3(256), 0, S.st, S.dlen.as<uint32_t>(), m, S.dbsum.as<uint64_t>(), base,
-                           S.dalA.as<uint8_t>(), S.dalB.as<uint8_t>(), aln_stride, S.doff.as<uint64_t>(), S.dpA.as<uint8_t>(),
-                           S.dpB.as<uint8_t>());
-        PH_HIP(hipGetLastError());
+        PH_HIP(pack_strings(S.st, S.dlen.as<uint32_t>(), m, S.dbsum.as<uint64_t>(), base, S.dalA.as<uint8_t>(), S.dalB.as<uint8_t>(),
+                            aln_stride, S.doff.as<uint64_t>(), S.dpA.as<uint8_t>(), S.dpB.as<uint8_t>(), nullptr));
     }
     {
         uint64_t t = 0;
@@ -3513,13 +3381,8 @@ static int packed_shard_align(const polyhip_scoring *sc, const uint8_t *A, const
             (void)hipStreamSynchronize(st);
             return rc;
         }
-        const unsigned nb = (unsigned)((m + k3t::PACK_BLOCK - 1) / k3t::PACK_BLOCK);
-        hipLaunchKernelGGL(k3t::pack_sums_kernel, dim3(nb), dim3(256), 0, st, dlen.as<uint32_t>(), m, dbsum.as<uint64_t>());
-        hipLaunchKernelGGL(k3t::pack_scan_kernel, dim3(1), dim3(1024), 0, st, dbsum.as<uint64_t>(), nb);
-        hipLaunchKernelGGL(k3t::pack_copy_kernel, dim3(nb), dim3(256), 0, st, dlen.as<uint32_t>(), m, dbsum.as<uint64_t>(), (uint64_t)0,
-                           dalA.as<uint8_t>(), dalB.as<uint8_t>(), aln_stride, doff.as<uint64_t>() + i0, sh.dpA.as<uint8_t>(),
-                           sh.dpB.as<uint8_t>(), doff.as<uint64_t>() + i0);
-        PH_HIP(hipGetLastError());
+        PH_HIP(pack_strings(st, dlen.as<uint32_t>(), m, dbsum.as<uint64_t>(), 0, dalA.as<uint8_t>(), dalB.as<uint8_t>(), aln_stride,
+                            doff.as<uint64_t>() + i0, sh.dpA.as<uint8_t>(), sh.dpB.as<uint8_t>(), doff.as<uint64_t>() + i0));
     }
     PH_HIP(hipMemcpyAsync(score, dscore.p, npairs * 8, hipMemcpyDeviceToHost, st));
     PH_HIP(hipMemcpyAsync(endA, dea.p, npairs * 4, hipMemcpyDeviceToHost, st));

@@ -19,10 +19,8 @@ for n, LA, LB in ((80_000, 1000, 5000), (160_000, 500, 5000), (40_000, 700, 3000
     stride = align.sw_traceback_stride(sc, LA, LB)
     tbw = torch.empty(align.sw_traceback_workspace_bytes(sc, n, LA, LB), dtype=torch.uint8, device=dev)
     res = {}
-    for tag, env in (("byte profile", {}), ("table", {"POLYHIP_TB_WAVE8": "0"}), ("plain walk", {"POLYHIP_TB_WALKREG": "0"}),
-                     ("no walk", {"POLYHIP_TB_NOWALK": "1"})):
-        for k in ("POLYHIP_TB_WAVE8", "POLYHIP_TB_WALKREG", "POLYHIP_TB_NOWALK"):
-            os.environ.pop(k, None)
+    for tag, env in (("byte profile", {}), ("table", {"POLYHIP_TB_WAVE8": "0"})):
+        os.environ.pop("POLYHIP_TB_WAVE8", None)
         os.environ.update(env)
         alnA = torch.zeros((n, stride), dtype=torch.uint8, device=dev)
         alnB = torch.zeros((n, stride), dtype=torch.uint8, device=dev)
@@ -35,11 +33,7 @@ for n, LA, LB in ((80_000, 1000, 5000), (160_000, 500, 5000), (40_000, 700, 3000
             torch.cuda.synchronize()
             ts.append((time.perf_counter() - t0) * 1e3)
         res[tag] = (alnA, alnB, ln, sorted(ts)[1], align.sw_traceback_last_path())
-    for k in ("POLYHIP_TB_WAVE8", "POLYHIP_TB_WALKREG", "POLYHIP_TB_NOWALK"):
-        os.environ.pop(k, None)
-    z = res["plain walk"]
-    print(f"   byte profile + plain walk {z[3]:.2f} ms (equal: {bool(torch.equal(z[2], res['byte profile'][2]) and torch.equal(z[0], res['byte profile'][0]) and torch.equal(z[1], res['byte profile'][1]))}), "
-          f"sweep alone {res['no walk'][3]:.2f} ms", flush=True)
+    os.environ.pop("POLYHIP_TB_WAVE8", None)
     x, y = res["byte profile"], res["table"]
     live = torch.arange(stride, device=dev)[None, :] >= (stride - x[2].long())[:, None]
     same = bool(torch.equal(x[2], y[2]) and bool(((x[0] == y[0]) | ~live).all()) and bool(((x[1] == y[1]) | ~live).all()))
