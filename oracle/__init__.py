@@ -182,7 +182,12 @@ class _CSubmat(C.Structure):
 
 
 class AlphabetError(Exception):
-    """alphabet/alphabet.go:14-22,38 -- 'Symbol X not in alphabet'."""
+    """alphabet/alphabet.go:14-22,38 -- 'Symbol X not in alphabet'.  ``side``: 1 when the symbol is the first
+    sequence's (checked first, matrix.go:29-32), 2 when it is the second's; ``symbol``: its byte."""
+
+    def __init__(self, message: str, side: int = 0, symbol: int = 0):
+        super().__init__(message)
+        self.side, self.symbol = side, symbol
 
 
 class SubstitutionMatrix:
@@ -234,7 +239,7 @@ def smith_waterman(a, b, mat: SubstitutionMatrix, gap: int):
     e = lib().orc_smith_waterman(da, len(da), db, len(db), mat.ptr(), gap, C.byref(score),
                                  bufA, bufB, C.byref(ea), C.byref(eb), C.byref(sym))
     if e:
-        raise AlphabetError(f"Symbol {chr(sym.value)} not in alphabet")
+        raise AlphabetError(f"Symbol {chr(sym.value)} not in alphabet", e, sym.value)
     return score.value, bufA.value.decode("latin-1"), bufB.value.decode("latin-1"), ea.value, eb.value
 
 
@@ -248,7 +253,7 @@ def needleman_wunsch(a, b, mat: SubstitutionMatrix, gap: int):
     e = lib().orc_needleman_wunsch(da, len(da), db, len(db), mat.ptr(), gap, C.byref(score),
                                    bufA, bufB, C.byref(sym))
     if e:
-        raise AlphabetError(f"Symbol {chr(sym.value)} not in alphabet")
+        raise AlphabetError(f"Symbol {chr(sym.value)} not in alphabet", e, sym.value)
     return score.value, bufA.value.decode("latin-1"), bufB.value.decode("latin-1")
 
 

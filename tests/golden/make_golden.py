@@ -13,6 +13,7 @@ committed so that nothing at test/bench time reads /root/reference.
                    seqhash.RotateSequence(Clones[0])): a 4.4 kb circular construct already at its least rotation
 
   clone_parts.json <- the clone.Part literals of clone/clone_test.go and clone/example_test.go
+  matrices.json <- search/align/matrix/matrices.go: every canned table as {name: {"alphabet", "scores"}}
 
 Extraction follows io/genbank/genbank.go:125,627-633: every line between
 ORIGIN and // with all non-letters removed, case preserved.
@@ -57,6 +58,34 @@ def copy_fastq():
         shutil.copy(f, dst)
     os.makedirs(os.path.join(HERE, "fasta"), exist_ok=True)
     shutil.copy(os.path.join(REF, "io", "fasta", "data", "base.fasta"), os.path.join(HERE, "fasta"))
+
+
+def matrices():
+    """every table of search/align/matrix/matrices.go -> matrices.json: {name: {"alphabet": "-ACGT", "scores": [[...]]}}.
+    A table's alphabet is its `/*  - A C G T */` header comment (rows and columns in that order); only names, alphabets
+    and integers are kept."""
+    import json
+    with open(os.path.join(REF, "search", "align", "matrix", "matrices.go")) as f:
+        src = f.read()
+    out = {}
+    for m in re.finditer(r"^\t(\w+) = \[\]\[\]int\{\n(.*?)^\t\}", src, flags=re.M | re.S):
+        name, body = m.group(1), m.group(2).split("\n")
+        alphabet = "".join(re.fullmatch(r"\s*/\*\s*(.*?)\s*\*/\s*", body[0]).group(1).split())
+        rows = []
+        for line in body[1:]:
+            r = re.fullmatch(r"\s*/\* (\S) \*/ \{([-\d, ]*)\},\s*", line)
+            if r is None:
+                assert not line.strip(), (name, line)
+                continue
+            assert r.group(1) == alphabet[len(rows)], (name, line)
+            rows.append([int(v) for v in r.group(2).split(",")])
+        assert len(rows) == len(alphabet) and all(len(r) == len(alphabet) for r in rows), name
+        out[name] = {"alphabet": alphabet, "scores": rows}
+    assert len(out) == 78, len(out)
+    with open(os.path.join(HERE, "matrices.json"), "w") as f:
+        json.dump(out, f, separators=(",", ":"))
+        f.write("\n")
+    print("matrices.json", len(out))
 
 
 def clone_example_output():
@@ -117,4 +146,5 @@ if __name__ == "__main__":
     clone_example_output()
     clone_parts()
     fork_declarations()
+    matrices()
     sys.exit(main())
