@@ -6,9 +6,10 @@
 // linear gap, arbitrary (possibly asymmetric) substitution matrix, argmax =
 // first maximum in row-major order (i over A outer, j over B inner).
 //
-// This file holds the entry points, the plan that picks a path (polyhip_sw_last_path), and three kernels; the
-// packed two-pairs-per-lane pass (the default at BASELINE config 4) lives in sw_packed.hip, the one-wave-per-pair
-// kernel (small batches, ties of the packed pass, reads of 257..4096 symbols) in sw_wave.hip.
+// This file holds the entry points, choose() -- the one function that picks a path (polyhip_sw_last_path) and reads the
+// score pass's testing aids -- and three kernels; the packed two-pairs-per-lane pass (the default at BASELINE config 4)
+// lives in sw_packed.hip, the one-wave-per-pair kernel (small batches, ties of the packed pass, reads of 257..4096
+// symbols) in sw_wave.hip.
 //
 //  sw_shared_kernel<RA, CP>  -- 32-bit lane-per-pair kernel (BASELINE config 4: 1M x 150 bp
 //    reads against ONE shared 5 kb reference).  Inter-sequence parallel: one
@@ -55,10 +56,6 @@ constexpr int JC_MAX = 1024;  // columns per LDS chunk (10 key bits)
 constexpr int SCORE_LIMIT = 1 << 14;
 constexpr uint64_t LONG_PACKED_ROWS = 8ull << 20; // pairs x rows from which the packed banded pass pays for reads > 256 (a quarter of the chip's lanes busy)
 constexpr uint64_t WAVE_BATCH = 49152; // below this many pairs the one-wave-per-pair kernel (2.5e12 cell updates/s flat) beats the ~15 ms floor of one lane-per-pair wave
-
-static thread_local int g_last_path = 0;
-static thread_local int g_last_half = 0;
-static thread_local int g_last_lanes = 0; // lanes that share a lane's two read pairs in the last packed score pass (0: not packed)
 
 // prof[j][c] = S(symA[c], b_j) as int8; pad columns / pad code = -128.
 // Also finds the first byte of B that is not in SecondAlphabet.
@@ -442,101 +439,113 @@ __global__ __launch_bounds__(256) void sw_generic_kernel(
     err[pair] = e;
 }
 
-struct Plan {
-    int path;      // 1 fast, 2 generic, 3 packed (sw_packed.hip) + wave kernel for its ties, 4 wave kernel (small batch),
-                   // 5 per-pair B register-tiled, 6 wave kernel for what the others cannot take (long reads, ...),
-                   // 7 long reads, shared B: packed banded pass (maximum + its block) + wave kernel in locate mode
-    int ra, cp;    // fast: template parameters
-    uint32_t lenB_pad, jc_max;
-    size_t work_bytes, smem_bytes;
-    size_t fast_bytes; // path 3: where the packed pass's workspace starts
-    k3p::PackedPlan pk;
+// The score-pass kernels by their public path numbers (polyhip_sw_last_path, KernelChoice::sw_path)
+enum SwPath {
+    PATH_FAST = 1,    // shared B, <= 256 rows, a lane per pair (sw_shared_kernel)
+    PATH_GENERIC = 2, // any length, tables too large for LDS (sw_generic_kernel)
+    PATH_PACKED = 3,  // shared B, <= 256 rows: packed pass (sw_packed.hip) + the wave kernel for its ties
+    PATH_SMALL = 4,   // what path 1 takes, too few pairs to fill the chip: one wave per pair (sw_wave.hip)
+    PATH_PAIR = 5,    // per-pair B, <= 64 rows (<= 256 where the wave kernel cannot): a lane per pair (sw_pair_kernel)
+    PATH_WAVE = 6,    // what the lane-per-pair kernels cannot take (reads of 257..4096, gap >= 0, wide scores): one wave per pair
+    PATH_LONG = 7,    // shared B, 257..2048 rows, many pairs: packed banded pass + the wave kernel in locate mode
+};
+
+constexpr uint64_t SUB = 262144; // path 3's sub-batches: one full round of the packed kernel
+
+struct SwChoice {
+    SwPath path;
+    int ra, cp;                // sw_shared_kernel / sw_pair_kernel: template parameters
+    uint32_t lenB_pad, jc_max; // sw_shared_kernel's columns and LDS chunk; path 1, 3, 4: the byte profile's columns
+    size_t smem_bytes;         // sw_shared_kernel's LDS
+    size_t pk_off;             // paths 3, 7: where the packed pass's workspace starts
+    k3p::PackedPlan pk;        // paths 3, 7: the packed pass
+    bool half;                 // paths 3, 7: the packed pass's half-float cell (polyhip_sw_last_packed_half)
+    int lanes;                 // paths 3, 7: lanes that share a lane's two read pairs (polyhip_sw_last_packed_lanes), else 0
+    bool wave8;                // path 7: the byte-profile locate kernel (k3w::wave8_ok)
+    bool split;                // path 3 in sub-batches of SUB pairs on two streams, each with its own slice of pk's workspace
+    k3p::PackedPlan sub;       // ... and the packed pass of one sub-batch
+    size_t work_bytes;
 };
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-static bool wave_kernel_off()
+// The kernels that score a batch, and the only place the score pass's testing aids are read.  shared: one reference
+// for every pair (no offB).
+static SwChoice choose(const polyhip_scoring *sc, uint64_t npairs, uint32_t max_lenA, uint64_t lenB, bool shared)
 {
-    return env_is("POLYHIP_SW_WAVE", '0'); // testing aid: no one-wave-per-pair kernel
-}
+    const bool wave_on = !env_is("POLYHIP_SW_WAVE", '0');       // =0: no one-wave-per-pair kernel (paths 4, 6, 7)
+    const bool pair_on = !env_is("POLYHIP_SW_PAIR", '0');       // =0: the generic kernel for per-pair B, not path 5
+    const bool wave8_on = !env_is("POLYHIP_SW_WAVE8", '0');     // =0: path 7 locates with the general wave kernel only
+    const bool overlap_on = !env_is("POLYHIP_SW_OVERLAP", '0'); // =0: path 3 takes the whole batch in one piece
+    k3p::PackedAids aids; // (the packed pass's aids: sw_scoring.h)
+    aids.packed = !env_is("POLYHIP_SW_PACKED", '0');
+    aids.tile64 = !env_is("POLYHIP_SW_TILE64", '0');
+    aids.f16 = !env_is("POLYHIP_SW_F16", '0');
+    aids.pk1 = !env_is("POLYHIP_SW_PK1", '0');
+    aids.pk1x2 = !env_is("POLYHIP_SW_PK1X2", '0');
+    aids.locate16 = !env_is("POLYHIP_SW_LOCATE16", '0');
 
-static bool pair_kernel_off()
-{
-    return env_is("POLYHIP_SW_PAIR", '0'); // testing aid: generic kernel for per-pair B
-}
-
-static Plan plan(const polyhip_scoring *sc, uint64_t npairs, uint32_t max_lenA, uint64_t lenB, bool shared)
-{
-    Plan p{};
+    SwChoice c{};
     const uint64_t minlen = std::min<uint64_t>(max_lenA, lenB);
+    const bool table_ok = table_fits(sc);
     const bool wave_possible = max_lenA > 0 && max_lenA <= k3w::WAVE_MAX_LENA && lenB > 0 && lenB < (1ull << 31) - 64 &&
-                               (size_t)(sc->ncodes + 1) * (sc->ncodesB + 1) * 4 + 512 <= 60 * 1024 && !wave_kernel_off();
+                               table_ok && wave_on;
     const bool fast = shared && sc->int8_ok && sc->gap <= -1 && max_lenA <= 256 && lenB < (1ull << 31) &&
                       sc->cp <= 32 && (uint64_t)std::max(sc->smax, 0) * minlen < (uint64_t)SCORE_LIMIT;
     if (fast) {
-        p.path = 1;
-        p.ra = max_lenA <= 64 ? 64 : max_lenA <= 152 ? 152 : 256;
-        p.cp = sc->cp <= 8 ? 8 : 32;
-        p.lenB_pad = (uint32_t)align_up(lenB, U);
-        p.jc_max = JC_MAX;
-        if (p.jc_max > p.lenB_pad)
-            p.jc_max = std::max<uint32_t>(p.lenB_pad, U);
-        p.smem_bytes = (size_t)p.jc_max * p.cp + 256;
-        p.work_bytes = 256 + align_up((size_t)p.lenB_pad * p.cp, 256);
-        p.fast_bytes = p.work_bytes;
-        const bool wave_ok = (size_t)(sc->ncodes + 1) * (sc->ncodesB + 1) * 4 + 512 <= 60 * 1024;
-        if (wave_ok && npairs < WAVE_BATCH && !wave_kernel_off()) {
-            p.path = 4; // too few pairs to fill the chip one per lane: one wave per pair (sw_wave.hip)
-        } else if (wave_ok && k3p::packed_plan(sc, npairs, max_lenA, lenB, &p.pk) && p.pk.ra == p.ra && p.cp == 8) {
-            p.path = 3;
-            p.work_bytes += p.pk.work_bytes;
+        c.path = PATH_FAST;
+        c.ra = max_lenA <= 64 ? 64 : max_lenA <= 152 ? 152 : 256;
+        c.cp = sc->cp <= 8 ? 8 : 32;
+        c.lenB_pad = (uint32_t)align_up(lenB, U);
+        c.jc_max = JC_MAX;
+        if (c.jc_max > c.lenB_pad)
+            c.jc_max = std::max<uint32_t>(c.lenB_pad, U);
+        c.smem_bytes = (size_t)c.jc_max * c.cp + 256;
+        c.work_bytes = 256 + align_up((size_t)c.lenB_pad * c.cp, 256);
+        c.pk_off = c.work_bytes;
+        if (table_ok && npairs < WAVE_BATCH && wave_on) {
+            c.path = PATH_SMALL;
+        } else if (table_ok && k3p::packed_plan(sc, npairs, max_lenA, lenB, aids, &c.pk) && c.pk.ra == c.ra && c.cp == 8) {
+            c.path = PATH_PACKED;
+            c.work_bytes += c.pk.work_bytes;
+            // sub-batches alternate between the caller's stream and the library's second one: the packed kernel's last, partly
+            // filled round and the short locate / tie kernels of one sub-batch run beside the packed kernel of the next
+            c.split = npairs >= 2 * SUB && overlap_on && k3p::packed_plan(sc, SUB, max_lenA, lenB, aids, &c.sub) &&
+                      c.sub.ra == c.pk.ra && c.sub.k == c.pk.k && 2 * (c.sub.work_bytes + 256) <= c.pk.work_bytes;
+            if (c.split) { // (same kernels as the whole batch would take; the tables are built once, in front of the loop)
+                c.sub.skip_rows = c.pk.skip_rows;
+                c.sub.x2_rb = c.pk.x2_rb;
+                c.sub.reuse_profiles = true;
+            }
         }
     } else if (!shared && (max_lenA <= 64 || (max_lenA <= 256 && !wave_possible)) && max_lenA > 0 && lenB > 0 &&
                lenB < (1ull << 31) && // beyond 64 rows the wave kernel is faster (200k pairs of 150 x 150: 2.7 vs 3.9 ms)
-               (size_t)(sc->ncodes + 1) * (sc->ncodesB + 1) * 4 + 512 <= 60 * 1024 &&
-               (size_t)(sc->ncodes + 1) * (sc->ncodesB + 1) < 65536 &&
-               (uint64_t)std::max(sc->smax, 0) * minlen < (uint64_t)SCORE_LIMIT && !pair_kernel_off()) {
-        p.path = 5; // per-pair B, register-tiled (sw_pair_kernel)
-        p.ra = max_lenA <= 64 ? 64 : max_lenA <= 152 ? 152 : 256;
-        p.work_bytes = 256;
-    } else if (shared && max_lenA > 256 && lenB < (1ull << 31) - 64 &&
-               (size_t)(sc->ncodes + 1) * (sc->ncodesB + 1) * 4 + 512 <= 60 * 1024 && !wave_kernel_off() &&
-               k3p::packed_plan(sc, npairs, max_lenA, lenB, &p.pk) && npairs * (uint64_t)p.pk.ra >= LONG_PACKED_ROWS) {
+               table_ok && (size_t)(sc->ncodes + 1) * (sc->ncodesB + 1) < 65536 &&
+               (uint64_t)std::max(sc->smax, 0) * minlen < (uint64_t)SCORE_LIMIT && pair_on) {
+        c.path = PATH_PAIR;
+        c.ra = max_lenA <= 64 ? 64 : max_lenA <= 152 ? 152 : 256;
+        c.work_bytes = 256;
+    } else if (shared && max_lenA > 256 && lenB < (1ull << 31) - 64 && table_ok && wave_on &&
+               k3p::packed_plan(sc, npairs, max_lenA, lenB, aids, &c.pk) && npairs * (uint64_t)c.pk.ra >= LONG_PACKED_ROWS) {
         // long reads against one reference, enough of them to fill the chip K lanes per pair: the packed banded
         // pass finds each pair's maximum and the block it sits in, the wave kernel then sweeps only the columns
         // that can reach it (a third of the reference for a read that aligns well)
-        p.path = 7;
-        p.fast_bytes = 256;
-        p.work_bytes = 256 + p.pk.work_bytes;
-    } else if (max_lenA > 0 && max_lenA <= k3w::WAVE_MAX_LENA && lenB > 0 && lenB < (1ull << 31) - 64 &&
-               (size_t)(sc->ncodes + 1) * (sc->ncodesB + 1) * 4 + 512 <= 60 * 1024 && !wave_kernel_off()) {
-        // whatever the lane-per-pair kernels cannot take (reads longer than 256, gap >= 0, wide scores), shared or
-        // per-pair B: one wave per pair, plain int32, up to 4096 rows (sw_wave.hip)
-        p.path = 6;
-        p.work_bytes = 256;
+        c.path = PATH_LONG;
+        c.pk_off = 256;
+        c.work_bytes = 256 + c.pk.work_bytes;
+        c.wave8 = k3w::wave8_ok(sc, max_lenA, wave8_on);
+    } else if (wave_possible) {
+        c.path = PATH_WAVE;
+        c.work_bytes = 256;
     } else {
-        p.path = 2;
-        p.work_bytes = align_up((size_t)npairs * (lenB + 1) * sizeof(int32_t), 256);
+        c.path = PATH_GENERIC;
+        c.work_bytes = align_up((size_t)npairs * (lenB + 1) * sizeof(int32_t), 256);
     }
-    return p;
-}
-
-template <int RA, int CP>
-static int launch_fast(const polyhip_scoring *sc, const Plan &p, const uint8_t *d_A, const uint64_t *d_offA,
-                       uint64_t npairs, const uint8_t *d_B, uint32_t lenB, int8_t *prof, uint32_t *binfo,
-                       int64_t *d_score, uint32_t *d_endA, uint32_t *d_endB, uint32_t *d_err, hipStream_t st,
-                       const uint32_t *list = nullptr, const uint32_t *count = nullptr)
-{
-    auto kern = sw_shared_kernel<RA, CP>;
-    if (p.smem_bytes > 48 * 1024)
-        PH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)p.smem_bytes));
-    const uint64_t blocks = (npairs + THREADS - 1) / THREADS;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(THREADS), p.smem_bytes, st, d_A, d_offA, npairs, d_B, lenB,
-                       p.lenB_pad, prof, p.jc_max, sc->d_codeA, binfo, sc->ncodes, (int)sc->gap, d_score, d_endA,
-                       d_endB, d_err, list, count);
-    PH_HIP(hipGetLastError());
-    return POLYHIP_OK;
+    if (c.path == PATH_PACKED || c.path == PATH_LONG) {
+        c.half = c.pk.f16;
+        c.lanes = c.pk.k > 1 ? c.pk.k : (c.pk.x2_rb ? 2 : 1);
+    }
+    return c;
 }
 
 } // namespace k3
@@ -680,26 +689,41 @@ size_t polyhip_sw_workspace_bytes(const polyhip_scoring *sc, uint64_t npairs, ui
 {
     if (!sc)
         return 0;
-    return k3::plan(sc, npairs, max_lenA, lenB, shared_B != 0).work_bytes;
+    return k3::choose(sc, npairs, max_lenA, lenB, shared_B != 0).work_bytes;
 }
 
+int polyhip_sw_last_path(void) { return kernel_choice().sw_path; }
+int polyhip_sw_last_packed_half(void) { return kernel_choice().sw_half; }
+int polyhip_sw_last_packed_lanes(void) { return kernel_choice().sw_lanes; }
+
 } // extern "C"
-void polyhip::k3::score_choice(int *path, int *half, bool set)
+
+polyhip::KernelChoice &polyhip::kernel_choice()
 {
-    if (set) {
-        g_last_path = *path;
-        g_last_half = *half;
-    } else {
-        *path = g_last_path;
-        *half = g_last_half;
-    }
+    static thread_local KernelChoice c;
+    return c;
 }
-extern "C" {
-int polyhip_sw_last_path(void) { return k3::g_last_path; }
-int polyhip_sw_last_packed_half(void) { return k3::g_last_half; }
-int polyhip_sw_last_packed_lanes(void) { return k3::g_last_lanes; }
 
-} // extern "C"
+// The packed pass on pairs [i0, i0 + m) through the workspace slice `wk`, then the one-wave-per-pair kernel on what it
+// leaves: up to 256 rows the packed pass locates each pair's end cell itself and leaves its ties on a list (path 3);
+// above, the wave kernel locates every pair from the maximum and block the packed pass found (path 7).  `defer`: see
+// score_pass.
+static int packed_then_wave(const polyhip_scoring *sc, const k3::SwChoice &c, const k3p::PackedPlan &pk, const uint8_t *d_A,
+                            const uint64_t *d_offA, uint64_t i0, uint64_t m, uint32_t max_lenA, const uint8_t *d_B, uint32_t lenB,
+                            const int8_t *prof, const uint32_t *binfo, uint8_t *wk, int64_t *d_score, uint32_t *d_endA,
+                            uint32_t *d_endB, uint32_t *d_err, hipStream_t st, int defer)
+{
+    uint32_t *list = nullptr, *count = nullptr;
+    const uint32_t *infoM = nullptr, *infoQ = nullptr;
+    const bool ties = pk.ra <= 256;
+    int rc = k3p::packed_run(sc, pk, d_A, d_offA + i0, m, d_B, lenB, prof, binfo, wk, d_score + i0, d_endA + i0, d_endB + i0,
+                             d_err + i0, &list, &count, st, &infoM, &infoQ, ties ? defer : 0);
+    if (rc == POLYHIP_OK)
+        rc = k3w::wave_run(sc, d_A, d_offA + i0, m, max_lenA, d_B, nullptr, lenB, binfo, ties ? list : nullptr,
+                           ties ? count : nullptr, m, d_score + i0, d_endA + i0, d_endB + i0, d_err + i0, st, infoM, infoQ,
+                           c.wave8, ties ? 0 : defer);
+    return rc;
+}
 
 // the score pass; `defer` != 0 asks the packed paths (3: reads of at most 256 rows; 7: 257..1024 rows with the byte-profile
 // locate kernel) to leave the end cell of a pair to the traceback kernel (k3p::SW_END_DEFERRED): *deferred says whether it did
@@ -719,140 +743,89 @@ int polyhip::k3::score_pass(const polyhip_scoring *sc, const uint8_t *d_A, const
         return set_error(POLYHIP_ERR_UNSUPPORTED, "polyhip_sw_batch: scores could overflow int32 (|s|max %d, lengths %u+%llu)",
                          sc->absmax, max_lenA, (unsigned long long)lenB);
     const bool shared = d_offB == nullptr;
-    const k3::Plan p = k3::plan(sc, npairs, max_lenA, lenB, shared);
-    PH_REQUIRE(d_work && work_bytes >= p.work_bytes, "polyhip_sw_batch: workspace too small (%zu < %zu)", work_bytes,
-               p.work_bytes);
+    const k3::SwChoice c = k3::choose(sc, npairs, max_lenA, lenB, shared);
+    PH_REQUIRE(d_work && work_bytes >= c.work_bytes, "polyhip_sw_batch: workspace too small (%zu < %zu)", work_bytes,
+               c.work_bytes);
     hipStream_t st = as_stream(stream);
-    k3::g_last_path = p.path;
-    k3::g_last_half = (p.path == 3 || p.path == 7) && p.pk.f16 ? 1 : 0;
-    k3::g_last_lanes = (p.path == 3 || p.path == 7) ? (p.pk.k > 1 ? p.pk.k : (p.pk.x2_rb ? 2 : 1)) : 0;
-    if (p.path == 1 || p.path == 3 || p.path == 4) {
-        uint32_t *binfo = static_cast<uint32_t *>(d_work);
-        int8_t *prof = static_cast<int8_t *>(d_work) + 256;
+    KernelChoice &kc = kernel_choice();
+    kc.sw_path = c.path;
+    kc.sw_half = c.half ? 1 : 0;
+    kc.sw_lanes = c.lanes;
+    uint8_t *work = static_cast<uint8_t *>(d_work);
+    uint32_t *binfo = nullptr;
+    int8_t *prof = nullptr;
+    if (c.path == k3::PATH_FAST || c.path == k3::PATH_PACKED || c.path == k3::PATH_SMALL) {
+        // the byte profile of the reference and its first byte outside SecondAlphabet
+        binfo = reinterpret_cast<uint32_t *>(work);
+        prof = reinterpret_cast<int8_t *>(work) + 256;
         PH_HIP(hipMemsetAsync(binfo, 0xFF, 256, st));
-        if (p.lenB_pad > 0) {
-            hipLaunchKernelGGL(k3::profile_kernel, dim3((p.lenB_pad + 255) / 256), dim3(256), 0, st, d_B,
-                               (uint32_t)lenB, p.lenB_pad, sc->d_lutc, sc->ncodes, p.cp, sc->d_validB, prof, binfo);
+        if (c.lenB_pad > 0) {
+            hipLaunchKernelGGL(k3::profile_kernel, dim3((c.lenB_pad + 255) / 256), dim3(256), 0, st, d_B, (uint32_t)lenB,
+                               c.lenB_pad, sc->d_lutc, sc->ncodes, c.cp, sc->d_validB, prof, binfo);
             PH_HIP(hipGetLastError());
         }
-        if (p.path == 4)
-            return k3w::wave_run(sc, d_A, d_offA, npairs, max_lenA, d_B, nullptr, (uint32_t)lenB, binfo, nullptr, nullptr,
-                                 npairs, d_score, d_endA, d_endB, d_err, st);
-        // packed pass first (two pairs per lane); the few pairs it leaves on its tie list go through the
-        // exact one-wave-per-pair kernel (a lane-per-pair kernel would take a full DP's time for them)
-        if (p.path == 3) {
-            const int do_defer = defer && p.pk.ra <= 256 ? 1 : 0;
-            if (deferred)
-                *deferred = do_defer;
-            // Sub-batches of 262,144 pairs (one full round of the packed kernel), alternating between the caller's stream
-            // and the library's second one, each with its own slice of the packed pass's workspace: the packed kernel's
-            // last, partly filled round and the short locate / tie kernels of one sub-batch run beside the packed kernel of
-            // the next.  POLYHIP_SW_OVERLAP=0: the whole batch in one piece (testing aid).
-            const uint64_t SUB = 262144;
-            k3p::PackedPlan ps{};
-            const bool split = npairs >= 2 * SUB && !env_is("POLYHIP_SW_OVERLAP", '0') &&
-                               k3p::packed_plan(sc, SUB, max_lenA, lenB, &ps) && ps.ra == p.pk.ra && ps.k == p.pk.k &&
-                               2 * (ps.work_bytes + 256) <= p.pk.work_bytes;
-            if (!split) {
-                uint32_t *list = nullptr, *count = nullptr;
-                const uint32_t *infoM = nullptr, *infoQ = nullptr;
-                const int rc = k3p::packed_run(sc, p.pk, d_A, d_offA, npairs, d_B, (uint32_t)lenB, prof, binfo,
-                                               static_cast<uint8_t *>(d_work) + p.fast_bytes, d_score, d_endA, d_endB, d_err,
-                                               &list, &count, st, &infoM, &infoQ, do_defer);
-                if (rc != POLYHIP_OK)
-                    return rc;
-                // (round 6: the tie list with the packed pass's M / first block / span -- a near tie is swept on its window,
-                // not over the whole reference: sw_wave_kernel's locate mode)
-                return k3w::wave_run(sc, d_A, d_offA, npairs, max_lenA, d_B, nullptr, (uint32_t)lenB, binfo, list, count,
-                                     npairs, d_score, d_endA, d_endB, d_err, st, infoM, infoQ);
-            }
-            ps.skip_rows = p.pk.skip_rows; // (same kernels as the whole batch would take)
-            ps.x2_rb = p.pk.x2_rb;
-            AuxStream &aux = aux_stream(st);
-            const size_t slice = (ps.work_bytes + 255) & ~(size_t)255;
-            // both slices' tables once, in front of the fork (a tiny kernel queued beside a full-chip one waits for it)
-            for (int q = 0; q < 2; ++q)
-                if (int rc = k3p::packed_profiles(sc, ps, d_B, (uint32_t)lenB, static_cast<uint8_t *>(d_work) + p.fast_bytes + q * slice, st))
-                    return rc;
-            ps.reuse_profiles = true;
-            PH_HIP(aux.fork(st)); // the byte profile and the tables are ready
-            uint64_t k = 0;
-            for (uint64_t i0 = 0; i0 < npairs; i0 += SUB, ++k) {
-                const uint64_t m = std::min(SUB, npairs - i0);
-                hipStream_t sk = (k & 1) ? aux.s : st;
-                uint8_t *wk = static_cast<uint8_t *>(d_work) + p.fast_bytes + (k & 1) * slice;
-                uint32_t *list = nullptr, *count = nullptr;
-                const uint32_t *infoM = nullptr, *infoQ = nullptr;
-                int rc = k3p::packed_run(sc, ps, d_A, d_offA + i0, m, d_B, (uint32_t)lenB, prof, binfo, wk, d_score + i0,
-                                         d_endA + i0, d_endB + i0, d_err + i0, &list, &count, sk, &infoM, &infoQ, do_defer);
-                if (rc == POLYHIP_OK)
-                    rc = k3w::wave_run(sc, d_A, d_offA + i0, m, max_lenA, d_B, nullptr, (uint32_t)lenB, binfo, list, count, m,
-                                       d_score + i0, d_endA + i0, d_endB + i0, d_err + i0, sk, infoM, infoQ);
-                if (rc != POLYHIP_OK) {
-                    (void)aux.join(st);
-                    return rc;
-                }
-            }
-            PH_HIP(aux.join(st));
-            return POLYHIP_OK;
-        }
-#define PH_SW_CASE(RA_, CP_)                                                                                       \
-    if (p.ra == RA_ && p.cp == CP_)                                                                                \
-        return k3::launch_fast<RA_, CP_>(sc, p, d_A, d_offA, npairs, d_B, (uint32_t)lenB, prof, binfo, d_score,     \
-                                         d_endA, d_endB, d_err, st);
-#ifndef PH_SW_FAST_LIST
-#define PH_SW_FAST_LIST(X) X(64, 8) X(152, 8) X(256, 8) X(64, 32) X(152, 32) X(256, 32)
-#endif
-        PH_SW_FAST_LIST(PH_SW_CASE)
-#undef PH_SW_CASE
-        return set_error(POLYHIP_ERR_UNSUPPORTED, "polyhip_sw_batch: no kernel for RA=%d CP=%d", p.ra, p.cp);
     }
-    if (p.path == 7) {
-        uint32_t *list = nullptr, *count = nullptr;
-        const uint32_t *infoM = nullptr, *infoQ = nullptr;
-        const int rc = k3p::packed_run(sc, p.pk, d_A, d_offA, npairs, d_B, (uint32_t)lenB, nullptr, nullptr,
-                                       static_cast<uint8_t *>(d_work) + p.fast_bytes, d_score, d_endA, d_endB, d_err, &list,
-                                       &count, st, &infoM, &infoQ);
-        if (rc != POLYHIP_OK)
-            return rc;
-        // (one call for score + strings, 257..1024 rows: the traceback kernel finds the end cell of a maximum that sits in
-        // one block during its own sweep; the locate step then only takes the ties)
-        const int do_defer = defer && k3w::wave8_ok(sc, max_lenA) ? 1 : 0;
-        if (deferred)
-            *deferred = do_defer;
-        return k3w::wave_run(sc, d_A, d_offA, npairs, max_lenA, d_B, nullptr, (uint32_t)lenB, nullptr, nullptr, nullptr,
-                             npairs, d_score, d_endA, d_endB, d_err, st, infoM, infoQ, do_defer);
-    }
-    if (p.path == 6)
-        return k3w::wave_run(sc, d_A, d_offA, npairs, max_lenA, d_B, d_offB, (uint32_t)lenB, nullptr, nullptr, nullptr,
-                             npairs, d_score, d_endA, d_endB, d_err, st);
-    if (p.path == 5) {
-        const int na = sc->ncodes + 1, nb = sc->ncodesB + 1;
-        const size_t smem = (size_t)na * nb * 4 + 512;
-        const uint64_t nblk = (npairs + k3::THREADS - 1) / k3::THREADS;
-#define PH_SW_PAIR(RA_)                                                                                               \
-    do {                                                                                                              \
-        auto kern = k3::sw_pair_kernel<RA_>;                                                                          \
-        PH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                   (int)smem));                                                                       \
-        hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(k3::THREADS), smem, st, d_A, d_offA, npairs, d_B, d_offB,  \
-                           (uint32_t)lenB, sc->d_codeA, sc->d_codeB, sc->d_lutcc, na, nb, (int)sc->gap, d_score,      \
-                           d_endA, d_endB, d_err);                                                                    \
-    } while (0)
-        if (p.ra == 64)
-            PH_SW_PAIR(64);
-        else if (p.ra == 152)
-            PH_SW_PAIR(152);
-        else
-            PH_SW_PAIR(256);
-#undef PH_SW_PAIR
-        PH_HIP(hipGetLastError());
+    switch (c.path) {
+    case k3::PATH_FAST: {
+        auto kern = c.cp == 8 ? (c.ra == 64 ? k3::sw_shared_kernel<64, 8> : c.ra == 152 ? k3::sw_shared_kernel<152, 8> : k3::sw_shared_kernel<256, 8>)
+                              : (c.ra == 64 ? k3::sw_shared_kernel<64, 32> : c.ra == 152 ? k3::sw_shared_kernel<152, 32> : k3::sw_shared_kernel<256, 32>);
+        PH_HIP(launch(kern, (unsigned)((npairs + k3::THREADS - 1) / k3::THREADS), c.smem_bytes, st, d_A, d_offA, npairs, d_B,
+                      (uint32_t)lenB, c.lenB_pad, prof, c.jc_max, sc->d_codeA, binfo, sc->ncodes, (int)sc->gap, d_score, d_endA, d_endB,
+                      d_err, nullptr, nullptr));
         return POLYHIP_OK;
     }
-    const uint64_t blocks = (npairs + 255) / 256;
-    hipLaunchKernelGGL(k3::sw_generic_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_A, d_offA, npairs, d_B, d_offB,
-                       lenB, sc->d_lut, sc->d_validA, sc->d_validB, (int)sc->gap, static_cast<int32_t *>(d_work),
-                       d_score, d_endA, d_endB, d_err);
+    case k3::PATH_SMALL:
+    case k3::PATH_WAVE:
+        return k3w::wave_run(sc, d_A, d_offA, npairs, max_lenA, d_B, d_offB, (uint32_t)lenB, binfo, nullptr, nullptr, npairs, d_score,
+                             d_endA, d_endB, d_err, st);
+    case k3::PATH_PACKED:
+    case k3::PATH_LONG: {
+        // the packed pass first (two pairs per lane), then the exact one-wave-per-pair kernel on what it leaves (a lane-per-pair
+        // kernel would take a full DP's time for the few pairs).  Path 3 defers end cells whenever asked (its own locate
+        // step), path 7 only with the byte-profile locate kernel: the traceback kernel that finds them sweeps the same columns.
+        const int do_defer = defer && (c.path == k3::PATH_PACKED || c.wave8) ? 1 : 0;
+        if (deferred)
+            *deferred = do_defer;
+        // path 3 in sub-batches (c.split): both slices' tables once, in front of the fork (a tiny kernel queued beside a
+        // full-chip one waits for it)
+        const k3p::PackedPlan &pk = c.split ? c.sub : c.pk;
+        const uint64_t piece = c.split ? k3::SUB : npairs;
+        const size_t slice = (c.sub.work_bytes + 255) & ~(size_t)255;
+        AuxStream *aux = c.split ? &aux_stream(st) : nullptr;
+        if (c.split) {
+            for (int q = 0; q < 2; ++q)
+                if (int rc = k3p::packed_profiles(sc, pk, d_B, (uint32_t)lenB, work + c.pk_off + q * slice, st))
+                    return rc;
+            PH_HIP(aux->fork(st)); // the byte profile and the tables are ready
+        }
+        uint64_t k = 0;
+        for (uint64_t i0 = 0; i0 < npairs; i0 += piece, ++k) {
+            const int rc = packed_then_wave(sc, c, pk, d_A, d_offA, i0, std::min(piece, npairs - i0), max_lenA, d_B, (uint32_t)lenB,
+                                            prof, binfo, work + c.pk_off + (k & 1) * slice, d_score, d_endA, d_endB, d_err,
+                                            (k & 1) ? aux->s : st, do_defer);
+            if (rc != POLYHIP_OK) {
+                if (aux)
+                    (void)aux->join(st);
+                return rc;
+            }
+        }
+        if (aux)
+            PH_HIP(aux->join(st));
+        return POLYHIP_OK;
+    }
+    case k3::PATH_PAIR: {
+        auto kern = c.ra == 64 ? k3::sw_pair_kernel<64> : c.ra == 152 ? k3::sw_pair_kernel<152> : k3::sw_pair_kernel<256>;
+        PH_HIP(launch(kern, (unsigned)((npairs + k3::THREADS - 1) / k3::THREADS), table_smem(sc), st, d_A, d_offA, npairs, d_B,
+                      d_offB, (uint32_t)lenB, sc->d_codeA, sc->d_codeB, sc->d_lutcc, sc->ncodes + 1, sc->ncodesB + 1, (int)sc->gap,
+                      d_score, d_endA, d_endB, d_err));
+        return POLYHIP_OK;
+    }
+    case k3::PATH_GENERIC:
+        break;
+    }
+    hipLaunchKernelGGL(k3::sw_generic_kernel, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, st, d_A, d_offA, npairs, d_B,
+                       d_offB, lenB, sc->d_lut, sc->d_validA, sc->d_validB, (int)sc->gap, static_cast<int32_t *>(d_work), d_score,
+                       d_endA, d_endB, d_err);
     PH_HIP(hipGetLastError());
     return POLYHIP_OK;
 }
@@ -939,21 +912,9 @@ int polyhip_sw_batch(const polyhip_scoring *sc, const uint8_t *A, const uint64_t
         return sw_batch_one(sc, A, offA, npairs, B, offB, lenB, score, endA, endB, err);
     // pairs are independent -- the reads split by bytes, the shared reference goes to every device
     PH_REQUIRE(offA && score && endA && endB && err, "polyhip_sw_batch: null pointer");
-    const std::vector<uint64_t> cut = split_pairs(*P, offA, offB, npairs, 24);
-    size_t first = 0;
-    while (first + 1 < md::size(*P) && cut[first + 1] == cut[first])
-        ++first;
-    KernelChoice kc;
-    const int rc = md::run(*P, [&](size_t q) {
-        const uint64_t i0 = cut[q], m = cut[q + 1] - i0;
-        md::BaseScope pos(i0, 0);
-        const int r = sw_batch_one(sc, A, offA + i0, m, B, offB ? offB + i0 : nullptr, lenB, score + i0, endA + i0, endB + i0, err + i0);
-        if (q == first)
-            kc = kernel_choice_get();
-        return r;
+    return run_shards(*P, split_pairs(*P, offA, offB, npairs, 24), [&](size_t, uint64_t i0, uint64_t m) {
+        return sw_batch_one(sc, A, offA + i0, m, B, offB ? offB + i0 : nullptr, lenB, score + i0, endA + i0, endB + i0, err + i0);
     });
-    kernel_choice_set(kc);
-    return rc;
 }
 
 } // extern "C"

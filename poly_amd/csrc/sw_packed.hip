@@ -39,9 +39,6 @@
 #ifndef PH_SW_NEAR_SPAN
 #define PH_SW_NEAR_SPAN 15 // ties whose blocks lie within this many blocks of the first are resolved by sw_locate16_kernel itself
 #endif
-#ifndef PH_SW_TILE64_DEFAULT
-#define PH_SW_TILE64_DEFAULT 1 // 1: reads above 152 rows take 64 rows per lane (four waves per SIMD) unless POLYHIP_SW_TILE64=0
-#endif
 
 namespace polyhip {
 namespace k3p {
@@ -1473,10 +1470,11 @@ __global__ __launch_bounds__(THREADS, 2) void sw_locate16_kernel(
 #undef PH_L16_CELL
 
 // ---- host side ---------------------------------------------------------------------------------------
-bool packed_plan(const polyhip_scoring *sc, uint64_t npairs, uint32_t max_lenA, uint64_t lenB, PackedPlan *out)
+bool packed_plan(const polyhip_scoring *sc, uint64_t npairs, uint32_t max_lenA, uint64_t lenB, const PackedAids &aids,
+                 PackedPlan *out)
 {
     PackedPlan p{};
-    if (env_is("POLYHIP_SW_PACKED", '0')) // testing aid
+    if (!aids.packed) // POLYHIP_SW_PACKED=0, testing aid
         return false;
     const uint64_t minlen = std::min<uint64_t>(max_lenA, lenB);
     if (!(sc->int8_ok && sc->gap <= -1 && -sc->gap < 16384 && sc->smax > 0 && sc->cp <= 8 &&
@@ -1489,7 +1487,7 @@ bool packed_plan(const polyhip_scoring *sc, uint64_t npairs, uint32_t max_lenA, 
     // (round 6) 64 rows per lane on twice the lanes: the H column and the row codes fit 128 registers, four waves per SIMD
     // instead of two (what sw_pk1x2_kernel does for 152 rows).  POLYHIP_SW_TILE64=0: the 128-row tiles.
     static const int tiles64[][2] = {{64, 1}, {152, 1}, {64, 4}, {152, 2}, {64, 8}, {152, 4}, {64, 16}, {152, 8}, {128, 16}};
-    for (const auto &t : PH_SW_TILE64_DEFAULT != env_is("POLYHIP_SW_TILE64", PH_SW_TILE64_DEFAULT ? '0' : '1') ? tiles64 : tiles)
+    for (const auto &t : aids.tile64 ? tiles64 : tiles)
         if ((uint32_t)(t[0] * t[1]) >= max_lenA) {
             p.rb = t[0];
             p.k = t[1];
@@ -1499,7 +1497,7 @@ bool packed_plan(const polyhip_scoring *sc, uint64_t npairs, uint32_t max_lenA, 
     p.skip_rows = p.k == 1 && max_lenA + 16 <= (uint32_t)p.ra; // at least four row groups to save
     // every H below 2048: the three-instruction half-float cell (POLYHIP_SW_F16=0: the int16 one, testing aid)
     // (column 0 of the profile carries score + |gap|: that sum has to be a half-float integer too)
-    p.f16 = (uint64_t)sc->smax * minlen <= 2047ull && (int64_t)sc->smax - sc->gap <= 2048 && !env_is("POLYHIP_SW_F16", '0');
+    p.f16 = (uint64_t)sc->smax * minlen <= 2047ull && (int64_t)sc->smax - sc->gap <= 2048 && aids.f16;
     p.ncp = sc->ncodes + 1;
     p.tab_bytes = (uint32_t)(p.ncp * p.ncp * 16);
     p.lenB_pad = (uint32_t)align_up(lenB, 4);
@@ -1507,10 +1505,10 @@ bool packed_plan(const polyhip_scoring *sc, uint64_t npairs, uint32_t max_lenA, 
     p.jcb = std::max<uint32_t>(1, std::min<uint32_t>(64, 36864u / p.tab_bytes));
     p.pk_smem = (size_t)(p.jcb + p.k - 1) * p.tab_bytes + 256;
     // one wave per workgroup, the block's table at a fixed LDS address (POLYHIP_SW_PK1=0: the chunk-staged kernel)
-    p.pk1 = p.f16 && p.k == 1 && p.ncp * p.ncp <= 64 && !env_is("POLYHIP_SW_PK1", '0');
+    p.pk1 = p.f16 && p.k == 1 && p.ncp * p.ncp <= 64 && aids.pk1;
     // the two-lane form of that kernel (round 6: 128 registers, four waves per SIMD; POLYHIP_SW_PK1X2=0: one lane per two pairs)
     p.x2_rb = 0;
-    if (p.pk1 && p.ra == 152 && !env_is("POLYHIP_SW_PK1X2", '0')) // (up to 64 rows the one-lane kernel holds four waves itself)
+    if (p.pk1 && p.ra == 152 && aids.pk1x2) // (up to 64 rows the one-lane kernel holds four waves itself)
         p.x2_rb = 76;
     p.locate_smem = (size_t)p.lenB_pad * 8 + 256;
     if (p.ra <= 256 && p.locate_smem > 160 * 1024)
@@ -1519,7 +1517,7 @@ bool packed_plan(const polyhip_scoring *sc, uint64_t npairs, uint32_t max_lenA, 
     p.info_bytes = align_up((size_t)npairs * 4, 256);
     const size_t tab16 = ((size_t)p.lenB_pad / 4 + 1) * (size_t)p.ncp * 8;
     p.locate16_smem = tab16 + 256;
-    p.locate16 = p.f16 && p.k == 1 && p.locate16_smem <= 79 * 1024 && !env_is("POLYHIP_SW_LOCATE16", '0');
+    p.locate16 = p.f16 && p.k == 1 && p.locate16_smem <= 79 * 1024 && aids.locate16;
     p.prof16_bytes = p.locate16 ? align_up(tab16, 256) : 0;
     p.work_bytes = p.prof2_bytes + 3 * p.info_bytes + 256 + p.prof16_bytes;
     *out = p;
@@ -1541,41 +1539,28 @@ static int launch_packed(const polyhip_scoring *sc, const PackedPlan &p, const u
     }
     if (K == 1 && p.pk1 && p.x2_rb != 0 && 2 * p.x2_rb <= RA) {
         // two lanes per lane's worth of rows, four waves per SIMD (POLYHIP_SW_PK1X2=0: one lane, two waves)
-        if constexpr (K == 1) {
-            const uint64_t blocks = (npairs + 63) / 64;
-            auto kern = p.skip_rows ? sw_pk1x2_kernel<76, true> : sw_pk1x2_kernel<76, false>;
-            hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64), 2048 + 256 + 1024, st, d_A, d_offA, npairs, prof2, p.nq,
-                               p.tab_bytes, p.ncp, sc->d_codeA, sc->ncodes, (int)(-sc->gap), infoM, infoQ);
-            PH_HIP(hipGetLastError());
-        }
+        if constexpr (K == 1)
+            PH_HIP(launch<64>(p.skip_rows ? sw_pk1x2_kernel<76, true> : sw_pk1x2_kernel<76, false>, (unsigned)((npairs + 63) / 64),
+                              2048 + 256 + 1024, st, d_A, d_offA, npairs, prof2, p.nq, p.tab_bytes, p.ncp, sc->d_codeA, sc->ncodes,
+                              (int)(-sc->gap), infoM, infoQ));
     } else if (K == 1 && p.pk1) {
-        if constexpr (K == 1) {
-            auto kern = p.skip_rows ? sw_pk1_kernel<RA, true> : sw_pk1_kernel<RA, false>;
-            const uint64_t blocks = (npairs + 127) / 128;
-            hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64), 1024 + 256 + 1024, st, d_A, d_offA, npairs, prof2, p.nq,
-                               p.tab_bytes, p.ncp, sc->d_codeA, sc->ncodes, (int)(-sc->gap), infoM, infoQ);
-            PH_HIP(hipGetLastError());
-        }
+        if constexpr (K == 1)
+            PH_HIP(launch<64>(p.skip_rows ? sw_pk1_kernel<RA, true> : sw_pk1_kernel<RA, false>, (unsigned)((npairs + 127) / 128),
+                              1024 + 256 + 1024, st, d_A, d_offA, npairs, prof2, p.nq, p.tab_bytes, p.ncp, sc->d_codeA, sc->ncodes,
+                              (int)(-sc->gap), infoM, infoQ));
     } else if constexpr (K == 1) {
         auto kern = p.f16 ? (p.skip_rows ? sw_pk_kernel<RA, true, true> : sw_pk_kernel<RA, false, true>)
                           : (p.skip_rows ? sw_pk_kernel<RA, true, false> : sw_pk_kernel<RA, false, false>);
-        PH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)p.pk_smem));
-        const uint64_t blocks = (npairs + 2 * THREADS - 1) / (2 * THREADS);
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(THREADS), p.pk_smem, st, d_A, d_offA, npairs, prof2, p.nq,
-                           p.jcb, p.tab_bytes, p.ncp, sc->d_codeA, sc->ncodes, (int)(-sc->gap), infoM, infoQ);
-        PH_HIP(hipGetLastError());
+        PH_HIP(launch(kern, (unsigned)((npairs + 2 * THREADS - 1) / (2 * THREADS)), p.pk_smem, st, d_A, d_offA, npairs, prof2, p.nq,
+                      p.jcb, p.tab_bytes, p.ncp, sc->d_codeA, sc->ncodes, (int)(-sc->gap), infoM, infoQ));
     } else {
         static_assert(RA % K == 0, "RA, K");
-        auto kern = p.f16 ? sw_pkb_kernel<RA / K, K, true> : sw_pkb_kernel<RA / K, K, false>;
-        PH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)p.pk_smem));
         constexpr uint64_t per_block = 2 * THREADS / K;
-        const uint64_t blocks = (npairs + per_block - 1) / per_block;
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(THREADS), p.pk_smem, st, d_A, d_offA, npairs, prof2, p.nq,
-                           p.jcb, p.tab_bytes, p.ncp, sc->d_codeA, sc->ncodes, (int)(-sc->gap), infoM, infoQ);
-        PH_HIP(hipGetLastError());
+        PH_HIP(launch(p.f16 ? sw_pkb_kernel<RA / K, K, true> : sw_pkb_kernel<RA / K, K, false>,
+                      (unsigned)((npairs + per_block - 1) / per_block), p.pk_smem, st, d_A, d_offA, npairs, prof2, p.nq, p.jcb,
+                      p.tab_bytes, p.ncp, sc->d_codeA, sc->ncodes, (int)(-sc->gap), infoM, infoQ));
     }
+    const unsigned blocks = (unsigned)((npairs + THREADS - 1) / THREADS);
     if constexpr (RA == 64 || RA == 152) {
         if (p.locate16 && !defer) { // (a deferred end cell needs no sweep: the 32-bit kernel's bookkeeping does)
             uint2 *prof16 = reinterpret_cast<uint2 *>(reinterpret_cast<uint8_t *>(list) + p.info_bytes);
@@ -1583,27 +1568,16 @@ static int launch_packed(const polyhip_scoring *sc, const PackedPlan &p, const u
             if (!p.reuse_profiles)
                 hipLaunchKernelGGL(profile16_kernel, dim3((n16 + 255) / 256), dim3(256), 0, st, d_B, lenB, p.lenB_pad,
                                    sc->d_lutc, sc->ncodes, p.ncp, prof16);
-            auto kern16 = sw_locate16_kernel<RA / 2>;
-            PH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern16), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)p.locate16_smem));
-            const uint64_t blocks = (npairs + THREADS - 1) / THREADS;
-            hipLaunchKernelGGL(kern16, dim3((unsigned)blocks), dim3(THREADS), p.locate16_smem, st, d_A, d_offA, npairs, d_B,
-                               lenB, p.lenB_pad, prof16, sc->d_codeA, binfo, sc->ncodes, (int)sc->gap, (int)sc->smax, infoM,
-                               infoQ, list, count, d_score, d_endA, d_endB, d_err, defer);
-            PH_HIP(hipGetLastError());
+            PH_HIP(launch(sw_locate16_kernel<RA / 2>, blocks, p.locate16_smem, st, d_A, d_offA, npairs, d_B, lenB, p.lenB_pad, prof16,
+                          sc->d_codeA, binfo, sc->ncodes, (int)sc->gap, (int)sc->smax, infoM, infoQ, list, count, d_score, d_endA,
+                          d_endB, d_err, defer));
             return POLYHIP_OK;
         }
     }
-    if constexpr (RA <= 256) {
-        auto kern = sw_locate_kernel<RA, 8>;
-        PH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)p.locate_smem));
-        const uint64_t blocks = (npairs + THREADS - 1) / THREADS;
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(THREADS), p.locate_smem, st, d_A, d_offA, npairs, d_B, lenB,
-                           p.lenB_pad, prof, sc->d_codeA, binfo, sc->ncodes, (int)sc->gap, (int)sc->smax, infoM, infoQ,
-                           list, count, d_score, d_endA, d_endB, d_err, defer);
-        PH_HIP(hipGetLastError());
-    }
+    if constexpr (RA <= 256)
+        PH_HIP(launch(sw_locate_kernel<RA, 8>, blocks, p.locate_smem, st, d_A, d_offA, npairs, d_B, lenB, p.lenB_pad, prof,
+                      sc->d_codeA, binfo, sc->ncodes, (int)sc->gap, (int)sc->smax, infoM, infoQ, list, count, d_score, d_endA,
+                      d_endB, d_err, defer));
     return POLYHIP_OK;
 }
 
@@ -1647,28 +1621,21 @@ int packed_run(const polyhip_scoring *sc, const PackedPlan &p, const uint8_t *d_
         *infoM_out = infoM;
     if (infoQ_out)
         *infoQ_out = infoQ;
-#define PH_PKB_CASE(RB_, K_)                                                                                              \
-    if (p.rb == RB_ && p.k == K_)                                                                                         \
-        return launch_packed<RB_ * K_, K_>(sc, p, d_A, d_offA, npairs, d_B, lenB, prof, binfo, prof2, infoM, infoQ, list, \
-                                           count, d_score, d_endA, d_endB, d_err, st, defer);
-    PH_PKB_CASE(64, 4)
-    PH_PKB_CASE(64, 8)
-    PH_PKB_CASE(64, 16)
-    PH_PKB_CASE(152, 2)
-    PH_PKB_CASE(128, 4)
-    PH_PKB_CASE(152, 4)
-    PH_PKB_CASE(128, 8)
-    PH_PKB_CASE(152, 8)
-    PH_PKB_CASE(128, 16)
-#undef PH_PKB_CASE
-    if (p.ra == 64)
-        return launch_packed<64, 1>(sc, p, d_A, d_offA, npairs, d_B, lenB, prof, binfo, prof2, infoM, infoQ, list, count,
-                                 d_score, d_endA, d_endB, d_err, st, defer);
-    if (p.ra == 152)
-        return launch_packed<152, 1>(sc, p, d_A, d_offA, npairs, d_B, lenB, prof, binfo, prof2, infoM, infoQ, list, count,
-                                  d_score, d_endA, d_endB, d_err, st, defer);
-    return launch_packed<256, 2>(sc, p, d_A, d_offA, npairs, d_B, lenB, prof, binfo, prof2, infoM, infoQ, list, count,
-                              d_score, d_endA, d_endB, d_err, st, defer);
+    // the tile of packed_plan -> the kernels' template arguments <rows per pair, lanes per pair>; {128, 2}: <256, 2>
+    using Launch = decltype(&launch_packed<64, 1>);
+    static const struct {
+        int rb, k;
+        Launch fn;
+    } tiles[] = {{64, 4, launch_packed<256, 4>},   {64, 8, launch_packed<512, 8>},   {64, 16, launch_packed<1024, 16>},
+                 {152, 2, launch_packed<304, 2>},  {128, 4, launch_packed<512, 4>},  {152, 4, launch_packed<608, 4>},
+                 {128, 8, launch_packed<1024, 8>}, {152, 8, launch_packed<1216, 8>}, {128, 16, launch_packed<2048, 16>},
+                 {64, 1, launch_packed<64, 1>},    {152, 1, launch_packed<152, 1>}};
+    Launch fn = launch_packed<256, 2>;
+    for (const auto &t : tiles)
+        if (t.rb == p.rb && t.k == p.k)
+            fn = t.fn;
+    return fn(sc, p, d_A, d_offA, npairs, d_B, lenB, prof, binfo, prof2, infoM, infoQ, list, count, d_score, d_endA, d_endB, d_err,
+              st, defer);
 }
 
 } // namespace k3p

@@ -62,22 +62,36 @@ struct polyhip_scoring {
 namespace polyhip {
 // the handle (or its copy) whose tables live on the calling thread's current device; null + polyhip_last_error() on failure
 const polyhip_scoring *scoring_here(const polyhip_scoring *sc);
-// polyhip_sw_last_path & friends are per-thread; a fan-out runs the kernels on worker threads, so the wrapper carries
-// the first non-empty shard's answers back to the caller's thread (sw_batch.hip / sw_traceback.hip own the variables)
+
+// What the calling thread's last calls ran (polyhip_sw_last_path & friends): the score pass, the traceback and NW write
+// their own fields (sw_batch.hip, sw_traceback.hip), the exports read them
 struct KernelChoice {
-    int sw_path = 0, sw_half = 0, tb_path = 0, tb_half = 0, nw_path = 0;
+    int sw_path = 0, sw_half = 0, sw_lanes = 0, tb_path = 0, tb_half = 0, nw_path = 0;
 };
-KernelChoice kernel_choice_get();            // this thread's
-void kernel_choice_set(const KernelChoice &); // ... becomes this
-namespace k3 {
-void score_choice(int *path, int *half, bool set); // sw_batch.hip's two variables
-}
+KernelChoice &kernel_choice(); // this thread's
+
+// The compact score table [ncodes + 1][ncodesB + 1] int32 + codeA + codeB in LDS (sw_pair_kernel, sw_wave_kernel,
+// sw_wave8_kernel's front part): its bytes, and whether it fits the 60 KB those kernels allow it
+inline size_t table_smem(const polyhip_scoring *sc) { return (size_t)(sc->ncodes + 1) * (sc->ncodesB + 1) * 4 + 512; }
+inline bool table_fits(const polyhip_scoring *sc) { return table_smem(sc) <= 60 * 1024; }
 } // namespace polyhip
 
 // ---- packed score pass (sw_packed.hip), driven from polyhip_sw_batch_dev (sw_batch.hip) ----------------
 #include <hip/hip_runtime.h>
 
 namespace polyhip {
+
+// sets the kernel's dynamic-LDS limit, launches it on workgroups of BLOCK threads and returns the launch's error
+template <unsigned BLOCK = 256, typename... Params, typename... Args>
+inline hipError_t launch(void (*kern)(Params...), unsigned blocks, size_t smem, hipStream_t st, Args... args)
+{
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(BLOCK), smem, st, args...);
+    return hipGetLastError();
+}
+
 namespace k3p {
 
 struct PackedPlan {
@@ -97,8 +111,20 @@ struct PackedPlan {
     size_t work_bytes;              // 256 (tie counter) + prof2 + infoM + infoQ + tie list
 };
 
-// false: the batch does not qualify (see sw_packed.hip) or POLYHIP_SW_PACKED=0
-bool packed_plan(const polyhip_scoring *sc, uint64_t npairs, uint32_t max_lenA, uint64_t lenB, PackedPlan *out);
+// The packed pass's testing aids, read by the score pass's choice (sw_batch.hip choose()); each is true unless its
+// variable is 0
+struct PackedAids {
+    bool packed = true;   // POLYHIP_SW_PACKED=0: no packed pass (paths 3 and 7)
+    bool tile64 = true;   // POLYHIP_SW_TILE64=0: above 152 rows the 128-row tiles instead of the 64-row ones
+    bool f16 = true;      // POLYHIP_SW_F16=0: the int16 cell
+    bool pk1 = true;      // POLYHIP_SW_PK1=0: the chunk-staged sw_pk_kernel
+    bool pk1x2 = true;    // POLYHIP_SW_PK1X2=0: one lane per two pairs of 65..152 rows
+    bool locate16 = true; // POLYHIP_SW_LOCATE16=0: the 32-bit locate kernel
+};
+
+// false: the batch does not qualify (see sw_packed.hip) or !aids.packed
+bool packed_plan(const polyhip_scoring *sc, uint64_t npairs, uint32_t max_lenA, uint64_t lenB, const PackedAids &aids,
+                 PackedPlan *out);
 
 // profile2 + packed pass + locate.  Pairs the exact kernel has to redo (ties) are left on *list_out
 // (count at *count_out, both inside d_work); every other pair has its four outputs written.
@@ -142,10 +168,11 @@ int wave_run(const polyhip_scoring *sc, const uint8_t *d_A, const uint64_t *d_of
              const uint32_t *count,
              uint64_t max_items, int64_t *d_score, uint32_t *d_endA, uint32_t *d_endB, uint32_t *d_err, hipStream_t st,
              const uint32_t *infoM = nullptr, const uint32_t *infoQ = nullptr, // locate mode: see sw_wave.hip
-             int defer = 0); // ... and leave the end cell of a pair with one block to the traceback kernel (wave8_ok only)
+             bool wave8 = false, // ... on the byte profile of the pair first (wave8_ok; infoM / infoQ, no list, shared B)
+             int defer = 0);     // ... and leave the end cell of a pair with one block to the traceback kernel (wave8 only)
 // locate mode on a byte profile of the pair (sw_wave8_kernel): reads of 257..1024 rows, score - gap in a byte, the planes of a
-// workgroup's four pairs within 64 KB of LDS (POLYHIP_SW_WAVE8=0: never)
-bool wave8_ok(const polyhip_scoring *sc, uint32_t max_lenA);
+// workgroup's four pairs within 64 KB of LDS (allowed = false, POLYHIP_SW_WAVE8=0: never)
+bool wave8_ok(const polyhip_scoring *sc, uint32_t max_lenA, bool allowed);
 
 } // namespace k3w
 } // namespace polyhip
@@ -167,6 +194,26 @@ inline std::vector<uint64_t> split_pairs(const md::Pool &P, const uint64_t *offA
     return md::split(npairs, md::size(P), [&](uint64_t i) {
         return offA[i] - offA[0] + (offB ? offB[i] - offB[0] : 0) + i * out_per_pair;
     });
+}
+
+// fn(q, i0, m) for shard q = pairs [i0, i0 + m) of `cut` on worker q of the device list (md::run; error messages name
+// positions in the whole batch).  polyhip_sw_last_path & friends are per-thread and the kernels ran on the workers: the
+// first non-empty shard's choice becomes the calling thread's.
+inline int run_shards(md::Pool &P, const std::vector<uint64_t> &cut, const std::function<int(size_t, uint64_t, uint64_t)> &fn)
+{
+    size_t first = 0;
+    while (first + 1 < md::size(P) && cut[first + 1] == cut[first])
+        ++first;
+    KernelChoice kc;
+    const int rc = md::run(P, [&](size_t q) {
+        md::BaseScope pos(cut[q], 0);
+        const int r = fn(q, cut[q], cut[q + 1] - cut[q]);
+        if (q == first)
+            kc = kernel_choice();
+        return r;
+    });
+    kernel_choice() = kc;
+    return rc;
 }
 
 // Validates a packed batch of pairs (offsets ascending, buffers present), copies it to the device with offsets

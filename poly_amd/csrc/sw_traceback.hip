@@ -49,9 +49,6 @@ constexpr int THREADS = 256;
 constexpr int TB_WIDE = 1;     // the conservative per-pair window for every pair (POLYHIP_TB_WIDE=1, testing aid)
 constexpr int TB_DEFERRED = 2; // the caller is the fused entry point, whose score pass may have deferred end cells
 
-static thread_local int g_tb_last_path = 0;
-static thread_local int g_tb_last_half = 0;
-static thread_local int g_nw_last_path = 0;
 
 struct Window {
     uint32_t wcols;   // columns of the re-run DP (<= lenB)
@@ -2646,17 +2643,6 @@ static TbChoice choose(const Plan &p, bool shared_B, bool score_given, bool have
     return c;
 }
 
-// sets the kernel's dynamic-LDS limit, launches it on workgroups of THREADS and returns the launch's error
-template <typename... Params, typename... Args>
-static hipError_t launch(void (*kern)(Params...), unsigned blocks, size_t smem, hipStream_t st, Args... args)
-{
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(THREADS), smem, st, args...);
-    return hipGetLastError();
-}
-
 // NW workspace per pair: the larger of the generic layout (2-bit codes + the H column) and the
 // register-tiled one (G and L words per 32 rows of RA)
 static inline int nw_ra(uint32_t max_lenA) { return max_lenA <= 64 ? 64 : 0; } // beyond: one wave per pair
@@ -2813,28 +2799,8 @@ __global__ __launch_bounds__(256) void pack_copy_kernel(const uint32_t *__restri
 using namespace polyhip;
 
 extern "C" {
-
-} // extern "C"
-polyhip::KernelChoice polyhip::kernel_choice_get()
-{
-    KernelChoice c;
-    k3::score_choice(&c.sw_path, &c.sw_half, false);
-    c.tb_path = k3t::g_tb_last_path;
-    c.tb_half = k3t::g_tb_last_half;
-    c.nw_path = k3t::g_nw_last_path;
-    return c;
-}
-void polyhip::kernel_choice_set(const KernelChoice &c)
-{
-    int p = c.sw_path, h = c.sw_half;
-    k3::score_choice(&p, &h, true);
-    k3t::g_tb_last_path = c.tb_path;
-    k3t::g_tb_last_half = c.tb_half;
-    k3t::g_nw_last_path = c.nw_path;
-}
-extern "C" {
-int polyhip_sw_traceback_last_path(void) { return k3t::g_tb_last_path; }
-int polyhip_sw_traceback_last_half(void) { return k3t::g_tb_last_half; }
+int polyhip_sw_traceback_last_path(void) { return kernel_choice().tb_path; }
+int polyhip_sw_traceback_last_half(void) { return kernel_choice().tb_half; }
 
 uint32_t polyhip_sw_traceback_stride(const polyhip_scoring *sc, uint32_t max_lenA, uint64_t lenB)
 {
@@ -2874,7 +2840,7 @@ static int traceback_impl(const polyhip_scoring *sc, const k3t::Plan &p, const k
                "polyhip_sw_traceback: null pointer");
     PH_REQUIRE(aln_stride >= p.win.stride, "polyhip_sw_traceback: aln_stride %u < %u (polyhip_sw_traceback_stride)",
                aln_stride, p.win.stride);
-    g_tb_last_path = c.path;
+    kernel_choice().tb_path = c.path;
     // the fused entry point deferred end cells only after the same choice said that its kernel finds them
     PH_REQUIRE(!deferred || c.finds_deferred(), "polyhip_sw_align_batch: end cells were deferred but the byte-profile traceback is not taken");
     const int wide = (c.wide ? TB_WIDE : 0) | (deferred ? TB_DEFERRED : 0);
@@ -2905,7 +2871,7 @@ static int traceback_impl(const polyhip_scoring *sc, const k3t::Plan &p, const k
     const int na = sc->ncodes + 1, nb = sc->ncodesB + 1;
     int8_t *prof = static_cast<int8_t *>(d_work);
     void *d_dir = static_cast<uint8_t *>(d_work) + p.prof_bytes;
-    g_tb_last_half = c.half ? 1 : 0;
+    kernel_choice().tb_half = c.half ? 1 : 0;
     if (c.path == PATH_HALF2 || (c.path == PATH_PROF && c.half)) {
         const uint32_t n16 = (p.lenB_pad / 4 + 1) * (uint32_t)(sc->ncodes + 1);
         hipLaunchKernelGGL(tb_profile16_kernel, dim3((n16 + 255) / 256), dim3(256), 0, st, d_B, (uint32_t)lenB, p.lenB_pad,
@@ -3183,23 +3149,10 @@ int polyhip_sw_align_batch(const polyhip_scoring *sc, const uint8_t *A, const ui
         return sw_align_batch_one(sc, A, offA, npairs, B, offB, lenB, score, endA, endB, err, alnA, alnB, alnLen, aln_stride);
     // pairs are independent; a shard's strings land in its own run of the caller's fixed-stride slots
     PH_REQUIRE(offA && score && endA && endB && err && alnA && alnB && alnLen, "polyhip_sw_align_batch: null pointer");
-    const std::vector<uint64_t> cut = split_pairs(*P, offA, offB, npairs, 24 + 2ull * aln_stride);
-    size_t first = 0;
-    while (first + 1 < md::size(*P) && cut[first + 1] == cut[first])
-        ++first;
-    KernelChoice kc;
-    const int rc = md::run(*P, [&](size_t q) {
-        const uint64_t i0 = cut[q], m = cut[q + 1] - i0;
-        md::BaseScope pos(i0, 0);
-        const int r = sw_align_batch_one(sc, A, offA + i0, m, B, offB ? offB + i0 : nullptr, lenB, score + i0, endA + i0, endB + i0,
-                                         err + i0, alnA + i0 * (size_t)aln_stride, alnB + i0 * (size_t)aln_stride, alnLen + i0,
-                                         aln_stride);
-        if (q == first)
-            kc = kernel_choice_get();
-        return r;
+    return run_shards(*P, split_pairs(*P, offA, offB, npairs, 24 + 2ull * aln_stride), [&](size_t, uint64_t i0, uint64_t m) {
+        return sw_align_batch_one(sc, A, offA + i0, m, B, offB ? offB + i0 : nullptr, lenB, score + i0, endA + i0, endB + i0, err + i0,
+                                  alnA + i0 * (size_t)aln_stride, alnB + i0 * (size_t)aln_stride, alnLen + i0, aln_stride);
     });
-    kernel_choice_set(kc); // polyhip_sw_last_path & co. on the caller's thread: what the first shard's kernels were
-    return rc;
 }
 
 // The same with PACKED strings: a pair's strings are a few hundred bytes of its aln_stride-byte slots (151 of 525 at
@@ -3421,22 +3374,12 @@ int polyhip_sw_align_batch_packed(const polyhip_scoring *sc, const uint8_t *A, c
     const size_t nsh = md::size(*P);
     const std::vector<uint64_t> cut = split_pairs(*P, offA, offB, npairs, 24 + 8 + 2 * 160);
     std::vector<PackedShard> sh(nsh);
-    size_t first = 0;
-    while (first + 1 < nsh && cut[first + 1] == cut[first])
-        ++first;
-    KernelChoice kc;
-    int rc = md::run(*P, [&](size_t q) {
-        sh[q].i0 = cut[q];
-        sh[q].m = cut[q + 1] - cut[q];
-        const uint64_t i0 = sh[q].i0;
-        md::BaseScope pos(i0, 0);
-        const int r = packed_shard_align(sc, A, offA + i0, B, offB ? offB + i0 : nullptr, lenB, score + i0, endA + i0, endB + i0,
-                                         err + i0, sh[q]);
-        if (q == first)
-            kc = kernel_choice_get();
-        return r;
+    int rc = run_shards(*P, cut, [&](size_t q, uint64_t i0, uint64_t m) {
+        sh[q].i0 = i0;
+        sh[q].m = m;
+        return packed_shard_align(sc, A, offA + i0, B, offB ? offB + i0 : nullptr, lenB, score + i0, endA + i0, endB + i0, err + i0,
+                                  sh[q]);
     });
-    kernel_choice_set(kc);
     if (rc != POLYHIP_OK)
         return rc; // the shards' device buffers go with `sh`
     std::vector<uint64_t> base(nsh + 1, 0);
@@ -3465,7 +3408,7 @@ int polyhip_sw_align_batch_packed(const polyhip_scoring *sc, const uint8_t *A, c
 
 extern "C" {
 
-int polyhip_nw_last_path(void) { return k3t::g_nw_last_path; }
+int polyhip_nw_last_path(void) { return kernel_choice().nw_path; }
 
 size_t polyhip_nw_workspace_bytes(uint64_t npairs, uint32_t max_lenA, uint64_t max_lenB)
 {
@@ -3508,7 +3451,7 @@ int polyhip_nw_align_batch_dev(const polyhip_scoring *sc, const uint8_t *d_A, co
                         lenB < (1ull << 31) - 64 && !nw_generic)
                            ? k3t::nw_wave_r(max_lenA)
                            : 0;
-    k3t::g_nw_last_path = reg_ra ? 1 : wave_r ? 3 : 2;
+    kernel_choice().nw_path = reg_ra ? 1 : wave_r ? 3 : 2;
     for (uint64_t p0 = 0; p0 < npairs; p0 += chunk) {
         const uint64_t p1 = std::min(npairs, p0 + chunk);
         const unsigned blocks = (unsigned)((p1 - p0 + k3t::THREADS - 1) / k3t::THREADS);
@@ -3624,22 +3567,10 @@ int polyhip_nw_align_batch(const polyhip_scoring *sc, const uint8_t *A, const ui
     if (!P)
         return nw_align_batch_one(sc, A, offA, npairs, B, offB, lenB, score, err, alnA, alnB, alnLen, aln_stride);
     PH_REQUIRE(offA && score && err && alnA && alnB && alnLen, "polyhip_nw_align_batch: null pointer");
-    const std::vector<uint64_t> cut = split_pairs(*P, offA, offB, npairs, 16 + 2ull * aln_stride);
-    size_t first = 0;
-    while (first + 1 < md::size(*P) && cut[first + 1] == cut[first])
-        ++first;
-    KernelChoice kc;
-    const int rc = md::run(*P, [&](size_t q) {
-        const uint64_t i0 = cut[q], m = cut[q + 1] - i0;
-        md::BaseScope pos(i0, 0);
-        const int r = nw_align_batch_one(sc, A, offA + i0, m, B, offB ? offB + i0 : nullptr, lenB, score + i0, err + i0,
-                                         alnA + i0 * (size_t)aln_stride, alnB + i0 * (size_t)aln_stride, alnLen + i0, aln_stride);
-        if (q == first)
-            kc = kernel_choice_get();
-        return r;
+    return run_shards(*P, split_pairs(*P, offA, offB, npairs, 16 + 2ull * aln_stride), [&](size_t, uint64_t i0, uint64_t m) {
+        return nw_align_batch_one(sc, A, offA + i0, m, B, offB ? offB + i0 : nullptr, lenB, score + i0, err + i0,
+                                  alnA + i0 * (size_t)aln_stride, alnB + i0 * (size_t)aln_stride, alnLen + i0, aln_stride);
     });
-    kernel_choice_set(kc);
-    return rc;
 }
 
 } // extern "C"

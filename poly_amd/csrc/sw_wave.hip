@@ -453,77 +453,44 @@ __global__ __launch_bounds__(THREADS) void sw_wave8_kernel(
     }
 }
 
-bool wave8_ok(const polyhip_scoring *sc, uint32_t max_lenA)
+// sw_wave8_kernel's LDS: the score table, then the planes of the workgroup's four pairs
+static size_t wave8_smem(const polyhip_scoring *sc, uint32_t max_lenA)
 {
-    const int na = sc->ncodes + 1, nb = sc->ncodesB + 1;
-    const size_t smem = (size_t)na * nb * 4 + 512;
     const int r8 = max_lenA <= 512 ? 8 : 16;
-    const size_t smem8 = ((smem + 15) & ~(size_t)15) + (size_t)(THREADS / 64) * nb * r8 * 64;
+    return ((table_smem(sc) + 15) & ~(size_t)15) + (size_t)(THREADS / 64) * (sc->ncodesB + 1) * r8 * 64;
+}
+
+bool wave8_ok(const polyhip_scoring *sc, uint32_t max_lenA, bool allowed)
+{
     return max_lenA > 256 && max_lenA <= 1024 && sc->gap <= -1 && -sc->gap <= 127 && (int64_t)sc->smax - sc->gap <= 127 &&
-           (int64_t)sc->smin - sc->gap >= -128 && smem8 <= 64 * 1024 && !env_is("POLYHIP_SW_WAVE8", '0');
+           (int64_t)sc->smin - sc->gap >= -128 && wave8_smem(sc, max_lenA) <= 64 * 1024 && allowed;
 }
 
 int wave_run(const polyhip_scoring *sc, const uint8_t *d_A, const uint64_t *d_offA, uint64_t npairs, uint32_t max_lenA,
              const uint8_t *d_B, const uint64_t *d_offB, uint32_t lenB, const uint32_t *binfo, const uint32_t *list,
              const uint32_t *count,
              uint64_t max_items, int64_t *d_score, uint32_t *d_endA, uint32_t *d_endB, uint32_t *d_err, hipStream_t st,
-             const uint32_t *infoM, const uint32_t *infoQ, int defer)
+             const uint32_t *infoM, const uint32_t *infoQ, bool wave8, int defer)
 {
     const int na = sc->ncodes + 1, nb = sc->ncodesB + 1;
-    const size_t smem = (size_t)na * nb * 4 + 512;
-    const uint64_t blocks = std::min<uint64_t>((max_items + THREADS / 64 - 1) / (THREADS / 64), 4096);
+    const size_t smem = table_smem(sc);
+    const unsigned blocks = (unsigned)std::min<uint64_t>((max_items + THREADS / 64 - 1) / (THREADS / 64), 4096);
     if (blocks == 0)
         return POLYHIP_OK;
     // locate mode, 257..1024 rows, one reference: the byte-profile kernel takes every pair whose maximum the packed pass
     // knows; the general kernel below then only the others (POLYHIP_SW_WAVE8=0: the general kernel for all; testing aid)
-    int m0_only = 0;
-    PH_REQUIRE(!defer || (infoM && infoQ && !list && !d_offB && wave8_ok(sc, max_lenA)), "polyhip_sw_batch: end cells deferred without the byte-profile locate kernel");
-    if (infoM && infoQ && !list && !d_offB && wave8_ok(sc, max_lenA)) {
-        const int r8 = max_lenA <= 512 ? 8 : 16;
-        const size_t smem8 = ((smem + 15) & ~(size_t)15) + (size_t)(THREADS / 64) * nb * r8 * 64;
-        {
-            if (r8 == 8) {
-                auto kern = sw_wave8_kernel<8>;
-                PH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem8));
-                hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(THREADS), smem8, st, d_A, d_offA, npairs, d_B, lenB, sc->d_codeA,
-                                   sc->d_codeB, sc->d_lutcc, na, nb, (int)sc->gap, infoM, infoQ, (int)sc->smax, d_score, d_endA, d_endB, d_err, defer);
-            } else {
-                auto kern = sw_wave8_kernel<16>;
-                PH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem8));
-                hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(THREADS), smem8, st, d_A, d_offA, npairs, d_B, lenB, sc->d_codeA,
-                                   sc->d_codeB, sc->d_lutcc, na, nb, (int)sc->gap, infoM, infoQ, (int)sc->smax, d_score, d_endA, d_endB, d_err, defer);
-            }
-            PH_HIP(hipGetLastError());
-            m0_only = 1;
-        }
-    }
-#define PH_WAVE_LAUNCH(R_)                                                                                            \
-    do {                                                                                                              \
-        auto kern = sw_wave_kernel<R_>;                                                                               \
-        PH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                   (int)smem));                                                                       \
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(THREADS), smem, st, d_A, d_offA, npairs, d_B, d_offB, lenB, \
-                           sc->d_codeA, sc->d_codeB, sc->d_lutcc, na, nb, (int)sc->gap, binfo, list, count, infoM,   \
-                           infoQ, (int)sc->smax, d_score, d_endA, d_endB, d_err, m0_only);                            \
-    } while (0)
-    if (max_lenA <= 64)
-        PH_WAVE_LAUNCH(1);
-    else if (max_lenA <= 128)
-        PH_WAVE_LAUNCH(2);
-    else if (max_lenA <= 192)
-        PH_WAVE_LAUNCH(3);
-    else if (max_lenA <= 256)
-        PH_WAVE_LAUNCH(4);
-    else if (max_lenA <= 512)
-        PH_WAVE_LAUNCH(8);
-    else if (max_lenA <= 1024)
-        PH_WAVE_LAUNCH(16);
-    else if (max_lenA <= 2048)
-        PH_WAVE_LAUNCH(32);
-    else
-        PH_WAVE_LAUNCH(64); // up to WAVE_MAX_LENA rows
-#undef PH_WAVE_LAUNCH
-    PH_HIP(hipGetLastError());
+    PH_REQUIRE(!wave8 || (infoM && infoQ && !list && !d_offB), "polyhip_sw_batch: byte-profile locate kernel without a packed pass");
+    PH_REQUIRE(!defer || wave8, "polyhip_sw_batch: end cells deferred without the byte-profile locate kernel");
+    if (wave8)
+        PH_HIP(launch(max_lenA <= 512 ? sw_wave8_kernel<8> : sw_wave8_kernel<16>, blocks, wave8_smem(sc, max_lenA), st, d_A, d_offA,
+                      npairs, d_B, lenB, sc->d_codeA, sc->d_codeB, sc->d_lutcc, na, nb, (int)sc->gap, infoM, infoQ, (int)sc->smax,
+                      d_score, d_endA, d_endB, d_err, defer));
+    const int r = max_lenA <= 64 ? 1 : max_lenA <= 128 ? 2 : max_lenA <= 192 ? 3 : max_lenA <= 256 ? 4 : max_lenA <= 512 ? 8
+                : max_lenA <= 1024 ? 16 : max_lenA <= 2048 ? 32 : 64; // up to WAVE_MAX_LENA rows
+    auto kern = r == 1 ? sw_wave_kernel<1> : r == 2 ? sw_wave_kernel<2> : r == 3 ? sw_wave_kernel<3> : r == 4 ? sw_wave_kernel<4>
+              : r == 8 ? sw_wave_kernel<8> : r == 16 ? sw_wave_kernel<16> : r == 32 ? sw_wave_kernel<32> : sw_wave_kernel<64>;
+    PH_HIP(launch(kern, blocks, smem, st, d_A, d_offA, npairs, d_B, d_offB, lenB, sc->d_codeA, sc->d_codeB, sc->d_lutcc, na, nb,
+                  (int)sc->gap, binfo, list, count, infoM, infoQ, (int)sc->smax, d_score, d_endA, d_endB, d_err, wave8 ? 1 : 0));
     return POLYHIP_OK;
 }
 

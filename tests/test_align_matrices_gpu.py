@@ -8,7 +8,7 @@ others off (POLYHIP_SW_WAVE / _SW_PAIR, POLYHIP_TB_PROF / _TB_F16 / _TB_WAVE / _
 Which kernel runs (n = codes of the first alphabet, m = of the second; "fits" = (n+1)(m+1)*4 + 512 <= 60 KB, i.e. n, m <= 122
 for a square table; cp = (n + 4) & ~3; batches here are below 49,152 pairs except test_full_size_protein_batch):
 
-  score pass (sw_batch.hip plan())                              case here
+  score pass (sw_batch.hip choose())                            case here
   1  lane per pair, shared B, <= 256 rows, int8, gap <= -1, cp <= 32   _SW_WAVE=0 on BLOSUM*/PAM*/...; 65,536 x 150 aa
   2  generic                                                    _SW_WAVE=0 (+ _SW_PAIR=0) off the fast path; n >= 123
   4  one wave per pair, shared B, small batch (the fast path's default)   protein tables, <= 256 rows

@@ -385,7 +385,8 @@ def test_sw_score_and_strings_shared_reference(ids):
 
 
 def test_sw_packed_strings_in_chunks_on_a_device_list(monkeypatch):
-    """more pairs than one chunk of a shard (262,144): the running total stays on the device between chunks"""
+    """more pairs than one chunk of a shard (262,144): the running total stays on the device between chunks.  The score
+    pass's packed lanes come back through the fan-out like its path: the call before it on this thread ran no packed pass."""
     from poly_amd import align, devices
     sc, omat, gap = _nuc4()
     rng = np.random.default_rng(22)
@@ -394,8 +395,18 @@ def test_sw_packed_strings_in_chunks_on_a_device_list(monkeypatch):
     A, offA = _pack(reads)
     B, _ = _pack([ref])
     one = align.sw_align_strings_packed(sc, A, offA, B)
+    one_s = align.sw_batch_packed(sc, A, offA, B)
+    path, lanes = align.last_path(), align.last_packed_lanes()
+    assert path == 3 and lanes == 1
+    small, offs = _pack(reads[:64])
+    align.sw_batch_packed(sc, small, offs, B)
+    assert align.last_path() == 4 and align.last_packed_lanes() == 0
     with devices.devices([0, 0]):
+        got_s = align.sw_batch_packed(sc, A, offA, B)
+        assert (align.last_path(), align.last_packed_lanes()) == (path, lanes)
         got = align.sw_align_strings_packed(sc, A, offA, B)
+    for g, o in zip(got_s, one_s):
+        assert (g == o).all()
     for q in range(4):
         assert (got[q] == one[q]).all()
     assert got[4] == one[4] and got[5] == one[5]
