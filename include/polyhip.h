@@ -80,7 +80,7 @@ int polyhip_device_arch(char *buf, size_t buflen);
  * buffers.  Results, error codes and messages are those of the one-device call (the status reported is the lowest
  * failing shard's, i.e. the first failure in batch order; positions in messages are positions of the whole batch).
  * An id may appear more than once ("0,0,0"): the shards then share that GPU (testing on a one-GPU box).  The _dev
- * entry points, the feeders and polyhip_scoring_create are not affected (a scoring handle is copied to the other
+ * entry points, the feeders, the polyhip_bwt_* calls (they run on their handle's device) and polyhip_scoring_create are not affected (a scoring handle is copied to the other
  * devices of the list on first use).  polyhip_sw_last_path and friends then describe the first non-empty shard's kernels.
  *   polyhip_set_devices(ids, n)  n = 0 clears the list.  Calls in flight finish on the list they started with.
  *   polyhip_get_devices          -> the list's length (ids filled up to `capacity`).
@@ -646,6 +646,78 @@ int polyhip_fasta_pack_dev(const uint8_t *d_file, uint64_t nbytes,
 int polyhip_fasta_pack(const uint8_t *file, uint64_t nbytes, uint8_t *seqs,
                        uint64_t *offsets, uint64_t *rec_start,
                        uint64_t max_records, uint64_t *result);
+
+/* ---- search/bwt: FM-index  (search/bwt/bwt.go:186-680) ---- */
+/*
+ * T = sequence + '$'; its suffixes sort with '$' lowest and every other byte by its unsigned value (bwt.go:563-581),
+ * so 0x00..0x23 and '!' sort after '$'.  The sequence may hold any byte but '$' (0x00 and bytes >= 0x80 included).
+ * A handle owns T, the suffix array (uint32), the last column L and an occurrence structure on the HIP device that is
+ * current at creation; every polyhip_bwt_* call runs on that device and returns the calling thread to its own.  The
+ * device list (polyhip_set_devices) does not apply to these calls, as it does not to the feeders.
+ * Rows: the n + 1 rotations of T in sorted order.  A search result is the interval [start, end) of rows that begin
+ * with the pattern, by LF backward search over the whole of L ('$' included): a pattern that holds '$' or is longer
+ * than T matches cyclically ("a$", "$b" on "banana": 1 row each), a symbol that does not occur gives (0, 0), and every
+ * empty result is reported as (0, 0).
+ *
+ * create (bwt.go:455-517): "Provided sequence must not by empty. BWT cannot be constructed" for n == 0 and
+ *   "Provided sequence contains the nullChar $. BWT cannot be constructed", both POLYHIP_ERR_INVALID; n >= 2^32 - 1 is
+ *   refused with POLYHIP_ERR_INVALID.  The suffix array is built on the device by prefix doubling (radix-sorted 64-bit
+ *   keys); the layout of the occurrence structure depends on the alphabet (polyhip_bwt_layout: 0 = nucleotide, at
+ *   most 4 distinct bytes, 2-bit L in 128-byte lines with their checkpoint counts; 1 = general; POLYHIP_BWT_GENERAL=1
+ *   in the environment forces 1).  _dev: d_seq is device memory ordered on `stream`, d_work holds
+ *   polyhip_bwt_workspace_bytes(n) bytes; the call synchronises `stream` (it reads back the alphabet and one group
+ *   count per doubling round) and returns with the handle built.
+ * len (bwt.go:301-304): n.  transform (bwt.go:306-323): L, n + 1 bytes with the '$'.  suffix_array: the n + 1 rows'
+ *   text positions.  rounds: the doubling rounds the build took.
+ * count (bwt.go:235-247, 353-404): one pattern of the packed batch per entry: start[p], end[p] as above, count =
+ *   end - start; err[p] = 1 for an empty pattern ("Pattern can not be empty"), its interval (0, 0).
+ * locate (bwt.go:249-273): first[0..npat] = exclusive scan of the interval widths; out[first[p] .. first[p+1]) =
+ *   SA[start .. end) in row order, the reference's order (not sorted).  Host flavour: the batch's patterns in, always
+ *   fills first[]; if first[npat] > capacity it writes nothing to out and fails with POLYHIP_ERR_INVALID naming the
+ *   size needed.  _dev: intervals from polyhip_bwt_count_dev in; entries at or past `capacity` are not written (compare
+ *   d_first[npat] with it); d_work: polyhip_bwt_locate_workspace_bytes(npat) bytes.
+ * extract (bwt.go:275-299): request i = T[start[i], end[i]) written to out[out_off[i] ..); err[i] = 0, or the
+ *   reference's first failing check: 1 "Start must be strictly less than end", 2 "end [E] exceeds the max range of the
+ *   BWT [n]" (end > n), 3 "start [S] exceeds the min range of the BWT [0]", 4 the slot out_off[i+1] - out_off[i] is
+ *   shorter than end - start.  The host flavour wants out_off[0] == 0.
+ */
+typedef struct polyhip_bwt polyhip_bwt;
+size_t polyhip_bwt_workspace_bytes(uint64_t n);
+int polyhip_bwt_create(const uint8_t *seq, uint64_t n, polyhip_bwt **out);
+int polyhip_bwt_create_dev(const uint8_t *d_seq, uint64_t n, void *d_work,
+                           size_t work_bytes, polyhip_stream_t stream,
+                           polyhip_bwt **out);
+int polyhip_bwt_destroy(polyhip_bwt *h);
+int64_t polyhip_bwt_len(const polyhip_bwt *h);
+int polyhip_bwt_layout(const polyhip_bwt *h);
+int polyhip_bwt_rounds(const polyhip_bwt *h);
+int polyhip_bwt_transform(const polyhip_bwt *h, uint8_t *out);
+int polyhip_bwt_transform_dev(const polyhip_bwt *h, uint8_t *d_out,
+                              polyhip_stream_t stream);
+int polyhip_bwt_suffix_array(const polyhip_bwt *h, uint32_t *out);
+int polyhip_bwt_count_dev(const polyhip_bwt *h, const uint8_t *d_pat,
+                          const uint64_t *d_off, uint64_t npat,
+                          uint32_t *d_start, uint32_t *d_end, uint32_t *d_err,
+                          polyhip_stream_t stream);
+int polyhip_bwt_count(const polyhip_bwt *h, const uint8_t *pat,
+                      const uint64_t *off, uint64_t npat, uint32_t *start,
+                      uint32_t *end, uint32_t *err);
+size_t polyhip_bwt_locate_workspace_bytes(uint64_t npat);
+int polyhip_bwt_locate_dev(const polyhip_bwt *h, const uint32_t *d_start,
+                           const uint32_t *d_end, uint64_t npat,
+                           uint64_t *d_first, uint32_t *d_out,
+                           uint64_t capacity, void *d_work, size_t work_bytes,
+                           polyhip_stream_t stream);
+int polyhip_bwt_locate(const polyhip_bwt *h, const uint8_t *pat,
+                       const uint64_t *off, uint64_t npat, uint64_t *first,
+                       uint32_t *out, uint64_t capacity, uint32_t *err);
+int polyhip_bwt_extract_dev(const polyhip_bwt *h, const int64_t *d_start,
+                            const int64_t *d_end, uint64_t nreq,
+                            const uint64_t *d_out_off, uint8_t *d_out,
+                            uint32_t *d_err, polyhip_stream_t stream);
+int polyhip_bwt_extract(const polyhip_bwt *h, const int64_t *start,
+                        const int64_t *end, uint64_t nreq,
+                        const uint64_t *out_off, uint8_t *out, uint32_t *err);
 
 /* ---- R1: the path's one collective -- all-gather of per-rank sketches (RCCL over xGMI) ---- */
 /*

@@ -7,6 +7,7 @@ Host-side mirror of the reference's Go packages over the C ABI of
     poly_amd.align     <- search/align     (Scoring, NewScoring, SmithWaterman)
     poly_amd.primers   <- primers          (SantaLucia, MarmurDoty, MeltingTemp)
     poly_amd.seqhash   <- seqhash          (RotateSequence, Hash)
+    poly_amd.bwt       <- search/bwt       (New, Count, Locate, Extract, Len, GetTransform)
 
 All compute happens in hand-written HIP kernels; PyTorch is used only to own
 device memory and streams for the device-resident (``*_dev``) entry points.

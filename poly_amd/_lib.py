@@ -102,6 +102,23 @@ SIGNATURES = {
     "polyhip_fasta_workspace_bytes": (C.c_size_t, [_u64]),
     "polyhip_fasta_pack_dev": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, C.c_size_t, _vp]),
     "polyhip_fasta_pack": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _u64, _vp]),
+    "polyhip_bwt_workspace_bytes": (C.c_size_t, [_u64]),
+    "polyhip_bwt_create": (C.c_int, [_vp, _u64, C.POINTER(C.c_void_p)]),
+    "polyhip_bwt_create_dev": (C.c_int, [_vp, _u64, _vp, C.c_size_t, _vp, C.POINTER(C.c_void_p)]),
+    "polyhip_bwt_destroy": (C.c_int, [_vp]),
+    "polyhip_bwt_len": (C.c_int64, [_vp]),
+    "polyhip_bwt_layout": (C.c_int, [_vp]),
+    "polyhip_bwt_rounds": (C.c_int, [_vp]),
+    "polyhip_bwt_transform": (C.c_int, [_vp, _vp]),
+    "polyhip_bwt_transform_dev": (C.c_int, [_vp, _vp, _vp]),
+    "polyhip_bwt_suffix_array": (C.c_int, [_vp, _vp]),
+    "polyhip_bwt_count_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "polyhip_bwt_count": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "polyhip_bwt_locate_workspace_bytes": (C.c_size_t, [_u64]),
+    "polyhip_bwt_locate_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, C.c_size_t, _vp]),
+    "polyhip_bwt_locate": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp]),
+    "polyhip_bwt_extract_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "polyhip_bwt_extract": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "polyhip_comm_unique_id": (C.c_int, [_vp]),
     "polyhip_comm_init_rank": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "polyhip_comm_destroy": (C.c_int, [_vp]),
