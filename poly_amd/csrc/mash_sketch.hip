@@ -34,10 +34,12 @@
 #include <algorithm>
 
 #include "common.h"
+#include "k1_tauq.h"
 #include "host_pipeline.h"
 #include "multi_device.h"
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 // PH_ABL != 0 only in scripts/ubench/k1_ablate.hip: knocks out one phase to measure its cost
@@ -575,10 +577,14 @@ __device__ void bottom_s_fast(const Smem &sm, uint32_t s, uint32_t tau, uint32_t
     auto one = [](uint32_t b) { return 1u << ((b & 1u) << 4); }; // +1 on bin b's half of its dword
     // a thread owns nbf / THREADS = 8 or 4 consecutive bins (2048 or 1024 bins) = one 16- or 8-byte word
     const bool wide = nbf_log2 == 11u;
+    // a zero made here: a plain constant is hoisted out of the slab kernel's read loop as four VGPRs held across the
+    // hot loop (and spilled to scratch once the loop needs them)
+    uint32_t z;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(z));
     if (wide)
-        reinterpret_cast<uint4 *>(bins)[tid] = make_uint4(0, 0, 0, 0);
+        reinterpret_cast<uint4 *>(bins)[tid] = make_uint4(z, z, z, z);
     else
-        reinterpret_cast<uint2 *>(bins)[tid] = make_uint2(0, 0);
+        reinterpret_cast<uint2 *>(bins)[tid] = make_uint2(z, z);
     if (tid == 0)
         sm.misc[8] = 0; // bins with more than BIG_BIN values
     if (PH_BS_WIN) { // the window pass below reads PH_BS_WIN entries on either side of binned[0, C): nothing there may count
@@ -683,6 +689,9 @@ __device__ void bottom_s_fast(const Smem &sm, uint32_t s, uint32_t tau, uint32_t
         if (pos < s)
             outp[pos] = hv;
     };
+    // Only slots before e*, the end of the bin that holds slot s - 1, can rank below s: every element at or behind it is
+    // in a bin that starts at e* > s - 1 or later (C >= s here, so slot s - 1 holds a value)
+    const uint32_t e_star = bins16[sm.binned[s - 1] >> shift];
 #if PH_BS_WIN
     // binned[] is sorted up to the order INSIDE the bins, and with ~0.6 values per bin a bin rarely holds more than
     // three.  So an element's place is its slot, minus the left neighbours that are larger, plus the right neighbours that
@@ -692,7 +701,7 @@ __device__ void bottom_s_fast(const Smem &sm, uint32_t s, uint32_t tau, uint32_t
     // (a bin of five or more: 0.2 % of them) are ranked against their whole bin as before.
     if (PH_ABL != 22) { // (PH_ABL 22: no rank pass -- timing only)
         const uint32_t lim = 1u << shift; // (a ^ b) < lim: same bin
-        for (uint32_t j = tid; j < C; j += THREADS) {
+        for (uint32_t j = tid; j < e_star; j += THREADS) {
             const uint32_t *__restrict__ w = sm.binned + j;
             const uint32_t hv = w[0];
             uint32_t pos = j;
@@ -718,7 +727,7 @@ __device__ void bottom_s_fast(const Smem &sm, uint32_t s, uint32_t tau, uint32_t
         }
     }
 #else
-    for (uint32_t j = tid; j < C; j += THREADS)
+    for (uint32_t j = tid; j < e_star; j += THREADS)
         rank_in_bin(j, sm.binned[j]);
 #endif
     if (by_waves && nbig) // rare: keep it out of line (and out of the common path's register budget)
@@ -859,6 +868,20 @@ template <int KS> struct Slabs {
     // `u_inside` lie, with one dword beyond them, inside the read: no per-lane guard.
     uint32_t u_inside;
     uint32_t gb32; // gbytes mod 2^32
+    // slab u < u_inside (the main loop's loads): no guard and no branch.  SH: the read does not start on a dword, and
+    // the successor dword is loaded for the funnel shift (dword-aligned reads -- every read of a batch of lengths that
+    // are multiples of 4 -- run the loop without it)
+    template <bool SH> __device__ __forceinline__ void gload_inside(uint32_t u, uint32_t &lo, uint32_t &hi) const
+    {
+        const uint32_t *__restrict__ slab = gdw + (uint64_t)u * 64;
+        // an opaque lane offset: else the loop-invariant gdw + 4 * lane is hoisted into a 64-bit VGPR pair and every
+        // load pays a 64-bit add, where the saddr form (scalar slab base + 32-bit lane offset) needs none
+        uint32_t off = (uint32_t)lane * 4u;
+        asm volatile("" : "+v"(off));
+        const uint8_t *__restrict__ p = reinterpret_cast<const uint8_t *>(slab) + off;
+        lo = *reinterpret_cast<const uint32_t *>(p);
+        hi = SH ? *reinterpret_cast<const uint32_t *>(p + 4) : 0u;
+    }
     __device__ __forceinline__ void gload(uint32_t u, uint32_t &lo, uint32_t &hi) const
     {
         const uint32_t *__restrict__ slab = gdw + (uint64_t)u * 64;
@@ -877,9 +900,11 @@ template <int KS> struct Slabs {
         }
     }
 
-    template <int PAR> __device__ __forceinline__ void stage(uint32_t lo, uint32_t hi) const
+    // SH = 0: the read is dword-aligned (gsh == 0) and lo is the slab's dword; SH = 1: funnel by gsh, which for a
+    // gsh of 0 is lo as well, so the generic path (SH = 1) needs no select
+    template <int PAR, bool SH = true> __device__ __forceinline__ void stage(uint32_t lo, uint32_t hi) const
     {
-        const uint32_t v = gsh ? funnel_bytes(hi, lo, gsh) : lo;
+        const uint32_t v = SH ? funnel_bytes(hi, lo, gsh) : lo;
         seqb[1 + 64 * PAR + lane] = v;
         if (PAR == 0) {
             if (lane < DUPD)
@@ -963,6 +988,33 @@ template <int KS> struct Slabs {
     }
 };
 
+__device__ __forceinline__ uint32_t lds_addr(const uint32_t *p)
+{
+    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint32_t *)p;
+}
+
+// ds_write_b32 of value c by the lanes in mask[c] alone, c = 0..3, with no branch: hipcc guards each `if (a) store`
+// with a saveexec and a skip branch (four per slab, and out of line).  Only for code that runs with all 64 lanes
+// active, where exec = mask is exec & mask; a store under an empty mask writes nothing.
+__device__ __forceinline__ void lds_store4_masked(const uint32_t (&addr)[4], const uint32_t (&v)[4], const uint64_t (&mask)[4])
+{
+    uint64_t saved;
+    asm volatile("s_mov_b64 %0, exec\n\t"
+                 "s_mov_b64 exec, %9\n\t"
+                 "ds_write_b32 %1, %5\n\t"
+                 "s_mov_b64 exec, %10\n\t"
+                 "ds_write_b32 %2, %6\n\t"
+                 "s_mov_b64 exec, %11\n\t"
+                 "ds_write_b32 %3, %7\n\t"
+                 "s_mov_b64 exec, %12\n\t"
+                 "ds_write_b32 %4, %8\n\t"
+                 "s_mov_b64 exec, %0"
+                 : "=&s"(saved)
+                 : "v"(addr[0]), "v"(addr[1]), "v"(addr[2]), "v"(addr[3]), "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]),
+                   "s"(mask[0]), "s"(mask[1]), "s"(mask[2]), "s"(mask[3])
+                 : "memory");
+}
+
 // survivors of the lane's 4 hashes -> the wave's own segment; `cnt` is wave-uniform (kept in a scalar register)
 template <bool PARTIAL>
 __device__ __forceinline__ void append_own(uint32_t *__restrict__ seg, uint32_t capw, uint32_t &cnt, const uint32_t (&h)[4],
@@ -978,7 +1030,9 @@ __device__ __forceinline__ void append_own(uint32_t *__restrict__ seg, uint32_t 
         n[c] = (uint32_t)__popcll(m[c]);
         total += n[c];
     }
-    uint32_t base = __builtin_amdgcn_readfirstlane(cnt);
+    // no readfirstlane: the count is a sum of popcounts of ballots, which the compiler keeps in an SGPR by itself; a
+    // readfirstlane of it made it a VGPR read back every slab
+    uint32_t base = cnt;
     cnt = base + total;
 #if PH_SEL_ATOMIC
     {
@@ -997,13 +1051,15 @@ __device__ __forceinline__ void append_own(uint32_t *__restrict__ seg, uint32_t 
     }
 #endif
     if (cnt <= capw) { // wave-uniform; an overflowing wave stops storing and the read is redone
+        uint32_t at[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            uint32_t *__restrict__ at = seg + base; // scalar: the lane only adds its rank among the survivors
-            if (a[c])
-                at[__builtin_amdgcn_mbcnt_hi((uint32_t)(m[c] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m[c], 0u))] = h[c];
+            // scalar: the lane only adds its rank among the survivors
+            at[c] = lds_addr(seg + base) +
+                    4u * __builtin_amdgcn_mbcnt_hi((uint32_t)(m[c] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m[c], 0u));
             base += n[c];
         }
+        lds_store4_masked(at, h, m);
     }
 }
 
@@ -1049,37 +1105,63 @@ __device__ __forceinline__ uint32_t run_slabs(const Smem &sm, const ReadView &rv
         S.gload(a + 1, l1, h1);
         S.template premix_unit<0>();
     }
-    for (uint32_t i = a; i < b; ++i) {
+    // one step: slab i (parity P = i & 1) is hashed.  Stage slab i+1 from the registers, then put slab i+2's loads in
+    // flight in the same registers: they land while this slab is premixed and hashed.  MAIN: slab i is full and slab
+    // i+2 lies below u_inside, so neither the loads nor the select need a guard; SH as in gload_inside.
+    auto step = [&](auto par, auto main, auto sh, uint32_t i) {
+        constexpr int P = decltype(par)::value;
+        constexpr bool MAIN = decltype(main)::value, SH = decltype(sh)::value;
         uint32_t h[4];
-        // stage slab i+1 from the registers, then put slab i+2's loads in flight in the same registers: they land
-        // while this slab is premixed and hashed
-        if (i & 1) {
-            S.template stage<0>(l1, h1);
-            wave_sync();
+        S.template stage<1 - P, SH>(l1, h1);
+        wave_sync();
+        if (MAIN)
+            S.template gload_inside<SH>(i + 2, l1, h1);
+        else
             S.gload(i + 2, l1, h1);
-            if (PH_ABL != 15)
-                S.template premix_unit<0>();
-            wave_sync();
-            S.template hash<1>(h);
-        } else {
-            S.template stage<1>(l1, h1);
-            wave_sync();
-            S.gload(i + 2, l1, h1);
-            if (PH_ABL != 15)
-                S.template premix_unit<1>();
-            wave_sync();
-            S.template hash<0>(h);
-        }
+        if (PH_ABL != 15)
+            S.template premix_unit<1 - P>();
+        wave_sync();
+        S.template hash<P>(h);
         if (PH_ABL == 11) { // keeps the hashes alive, stores (almost) never
             if ((h[0] ^ h[1] ^ h[2] ^ h[3]) == 0x12345u)
                 seg[0] = h[0];
-        } else if (__builtin_expect(i < nfull, 1)) { // (scalar compare: 32-bit, so that no 64-bit count lives in VGPRs)
+        } else if (MAIN || __builtin_expect(i < nfull, 1)) { // (scalar compare: 32-bit, so that no 64-bit count lives in VGPRs)
             append_own<false>(seg, capw, cnt, h, 4u, tauq);
         } else {
             const int mine = (int)rem - 4 * S.lane;
             append_own<true>(seg, capw, cnt, h, mine <= 0 ? 0u : (mine < 4 ? (uint32_t)mine : 4u), tauq);
         }
         wave_sync(); // the rings are rewritten by the next step
+    };
+    using P0 = std::integral_constant<int, 0>;
+    using P1 = std::integral_constant<int, 1>;
+    using T = std::true_type;
+    using F = std::false_type;
+    // main loop: slabs [a, m) -- full, and with the loads of slab i+2 inside the read -- two per trip, so that the
+    // parity stays a compile-time constant; then the epilogue, the last one or two slabs of the read, with the guards
+    const uint32_t lim = nfull < b ? nfull : b;
+    const uint32_t ins = S.u_inside >= 2u ? S.u_inside - 2u : 0u;
+    const uint32_t m = ins < lim ? ins : lim;
+    uint32_t i = a;
+    auto main_loop = [&](auto sh) {
+        if ((i & 1) && i < m)
+            step(P1{}, T{}, sh, i++);
+        for (; i + 1 < m; i += 2) {
+            step(P0{}, T{}, sh, i);
+            step(P1{}, T{}, sh, i + 1);
+        }
+        if (i < m)
+            step(P0{}, T{}, sh, i++);
+    };
+    if (S.gsh)
+        main_loop(T{});
+    else
+        main_loop(F{});
+    for (; i < b; ++i) {
+        if (i & 1)
+            step(P1{}, F{}, T{}, i);
+        else
+            step(P0{}, F{}, T{}, i);
     }
     return cnt;
 }
@@ -1117,12 +1199,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(PH_SLAB
         if (rv.nwin < (int64_t)s)
             continue; // mash.go:81-84: positional, unsorted, tail untouched -- the general kernel picks these up
         // threshold a uniform hash would need for s + 6 sqrt(s) + 16 survivors, rounded up to 16 bits
-        uint32_t tauq = 0xFFFFFFFFu;
-        {
-            const uint64_t target = (uint64_t)s + (uint64_t)PH_SLAB_SIG * (uint64_t)__builtin_sqrtf((float)s) + 16ull;
-            if ((int64_t)target < rv.nwin)
-                tauq = (uint32_t)((target << 32) / (uint64_t)rv.nwin) | 0xFFFFu;
-        }
+        const uint32_t tauq = slab_tauq(s + PH_SLAB_SIG * (uint32_t)__builtin_sqrtf((float)s) + 16u, rv.nwin);
         __syncthreads(); // the previous read is done with LDS
         const uint32_t cw = PH_ABL == 14 ? tauq >> 31 : run_slabs<KS>(sm, rv, n_seq_dw, n_P_w, seg, capw, tauq);
         if ((tid & 63) == 0)
@@ -1445,7 +1522,7 @@ static int launch(const uint8_t *d_seqs, const uint64_t *d_offs, uint64_t n, uin
     bool slabs = false;
     if constexpr (KS > 0) {
         // POLYHIP_K1_SLABS=0 keeps the tile pass (testing aid: the two passes are cross-checked in tests/)
-        slabs = !env_is("POLYHIP_K1_SLABS", '0') && L.smem_slab <= 64 * 1024;
+        slabs = !env_is("POLYHIP_K1_SLABS", '0') && L.smem_slab <= 64 * 1024 && s < 32768u; // (slab_tauq: target < 2^16)
         if (slabs) {
             auto slab = sketch_slab_kernel<KS>;
             PH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(slab), hipFuncAttributeMaxDynamicSharedMemorySize,
