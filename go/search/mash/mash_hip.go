@@ -191,3 +191,50 @@ func SketchSharedCounts(seqs []string, kmerSize, sketchSize int) ([]*Mash, *Shar
 	}
 	return ms, res
 }
+
+// NeighborList is an all-vs-all result kept as neighbour lists (CSR): sketch i's neighbours are Cols / Shared /
+// Dist[First[i]:First[i+1]] -- the sketches that share at least minShared hashes with it, sketch i itself left out.
+// Shared is the sameHashes of mash.go:108-132, Dist the Distance of mash.go:138-140 for that pair, bit for bit.
+type NeighborList struct {
+	First  []uint64
+	Cols   []uint32
+	Shared []uint16
+	Dist   []float64
+}
+
+// Neighbors returns, for every sketch of a set of one SketchSize, the sketches that share at least minShared (>= 1) hashes
+// with it: all of them in ascending order (k == 0), or the k with the most shared hashes, ties towards the smaller index
+// (k > 0).  The dense matrix DistanceMatrix returns is nearly all "nothing shared" for a set of any size; this is the
+// part of it that is not, and it has no n*n anywhere.
+func Neighbors(ms []*Mash, minShared, k int) *NeighborList {
+	n := len(ms)
+	if n == 0 {
+		return &NeighborList{First: []uint64{0}}
+	}
+	s := ms[0].SketchSize
+	flat := make([]uint32, 0, n*s)
+	for i, m := range ms {
+		if m.SketchSize != s || len(m.Sketches) != s {
+			panic(fmt.Sprintf("mash.Neighbors: sketch %d has SketchSize %d, the set's is %d", i, m.SketchSize, s))
+		}
+		flat = append(flat, m.Sketches...)
+	}
+	res := &NeighborList{First: make([]uint64, n+1)}
+	capacity := n * 64
+	if k > 0 {
+		capacity = n * k
+	}
+	for attempt := 0; attempt < 2; attempt++ {
+		res.Cols, res.Shared, res.Dist = make([]uint32, capacity+1), make([]uint16, capacity+1), make([]float64, capacity+1)
+		if err := polyhip.MashNeighbors(flat, n, s, flat, n, s, minShared, k, true, 0, res.First, res.Cols, res.Shared, res.Dist, capacity); err != nil {
+			panic(err)
+		}
+		if res.First[n] <= uint64(capacity) {
+			break
+		}
+		capacity = int(res.First[n]) // first[] carries the true counts: once more with the size it asks for
+	}
+	total := res.First[n]
+	res.Cols, res.Shared, res.Dist = res.Cols[:total], res.Shared[:total], res.Dist[:total]
+	return res
+}

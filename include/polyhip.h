@@ -283,6 +283,55 @@ typedef struct polyhip_matrix_info {
 } polyhip_matrix_info;
 int polyhip_mash_sketch_distance_matrix_last_info(polyhip_matrix_info *info);
 
+/* ---- K2 neighbour lists: the all-vs-all answered as CSR instead of a dense matrix ----
+ * shared(i, j) is the cell (i, j) of polyhip_mash_shared_counts_dev (mash.go:107-132, the early-out of :117 and irregular
+ * sketches included).  Row i of the list keeps the entries (j, shared) with
+ *     shared(i, j) >= min_shared            (min_shared >= 1: pairs without a shared hash are never listed; 0 is
+ *                                            POLYHIP_ERR_INVALID)
+ *     j != i + self_offset                  if exclude_self (self_offset = the column of X's row 0 when X is a row block of Y)
+ *     the k largest shared, ties towards the smaller column, if k > 0 (a row with fewer candidates returns all of them)
+ * as CSR: first uint64[nx + 1] (first[0] = 0), cols uint32, shared uint16, dist float64 = 1 - shared / min(sx, sy) (the
+ * value polyhip_mash_distance_from_counts_dev writes for that cell; may be NULL).  Rows in order; inside a row ascending
+ * column (k == 0) or shared descending, then column ascending (k > 0).  The same input gives the same bytes.
+ * capacity = entries cols / shared / dist hold: first[] ALWAYS carries the true counts and nothing is written beyond the
+ * capacity, so a caller whose buffers were too small (first[nx] > capacity) resizes and repeats the call; cols = shared =
+ * NULL asks for the counts alone.
+ * Y may hold up to 2^31 sketches: it is joined in column blocks of one dense stripe (about 105k sketches at SketchSize <=
+ * 1023), each with its own index, one after the other in the workspace.  SketchSize 0 / > 65535 as
+ * polyhip_mash_shared_counts_dev; nx == 0 or ny == 0: the empty list.  The call synchronises `stream` (once per row range).
+ * d_work: polyhip_mash_neighbors_workspace_bytes(...) bytes.  It holds the block index and a temporary list of
+ * max(1024 * nx, ny) entries; rows that need more are joined again in pieces (polyhip_neighbors_info.row_chunks > 1). */
+/* Largest k of the top-k form: the selection is k rounds over a row's candidates on one wave, so a larger k is
+ * POLYHIP_ERR_INVALID rather than a kernel that runs for minutes (threshold the list and select on the host instead). */
+#define POLYHIP_MASH_NEIGHBORS_MAX_K 1024u
+size_t polyhip_mash_neighbors_workspace_bytes(uint64_t nx, uint32_t sx,
+                                              uint64_t ny, uint32_t sy);
+int polyhip_mash_neighbors_dev(const uint32_t *d_X, uint64_t nx, uint32_t sx,
+                               const uint32_t *d_Y, uint64_t ny, uint32_t sy,
+                               uint32_t min_shared, uint32_t k,
+                               int exclude_self, uint64_t self_offset,
+                               uint64_t *d_first, uint32_t *d_cols,
+                               uint16_t *d_shared, double *d_dist,
+                               uint64_t capacity, void *d_work,
+                               size_t work_bytes, polyhip_stream_t stream);
+/* host flavour; on a device list (polyhip_set_devices) the rows of X shard over the devices, every device sees all of Y,
+ * and the lists concatenate in row order. */
+int polyhip_mash_neighbors(const uint32_t *X, uint64_t nx, uint32_t sx,
+                           const uint32_t *Y, uint64_t ny, uint32_t sy,
+                           uint32_t min_shared, uint32_t k, int exclude_self,
+                           uint64_t self_offset, uint64_t *first,
+                           uint32_t *cols, uint16_t *shared, double *dist,
+                           uint64_t capacity);
+/* What the calling thread's last polyhip_mash_neighbors / _dev did: column blocks of Y, index builds, row ranges joined
+ * (1 unless the temporary list overflowed), the CSR assembly that ran (1 = one pass with reserved segments and a reorder
+ * kernel), entries that passed the threshold and entries listed (after top-k), devices. */
+typedef struct polyhip_neighbors_info {
+    uint32_t column_blocks, index_builds, row_chunks, assembly;
+    uint64_t entries_thresholded, entries;
+    uint32_t devices, reserved;
+} polyhip_neighbors_info;
+int polyhip_mash_neighbors_last_info(polyhip_neighbors_info *info);
+
 /* ---- K3: search/align SmithWaterman  (search/align/align.go:171-232) ---- */
 /*
  * align.Scoring{SubstitutionMatrix, GapPenalty} (align.go:73-95) flattened

@@ -3055,3 +3055,5 @@ int polyhip::k2_exchange_index(md::Pool &P, std::vector<K2XShard> &sh, uint64_t 
     *built = true;
     return POLYHIP_OK;
 }
+
+#include "mash_neighbors.h" // K2 neighbour lists (threshold and top-k): this file's index, geometry and merge, as CSR

@@ -271,3 +271,81 @@ def distance_from_counts_dev(counts_t, sx: int, sy: int, dist_t, stream=None) ->
     _lib.check(_lib.lib().polyhip_mash_distance_from_counts_dev(
         counts_t.data_ptr(), nx, ny, counts_t.stride(0), sx, sy, dist_t.data_ptr(), dist_t.stride(0),
         _lib.stream_ptr(stream)))
+
+
+# ---- K2 neighbour lists: the all-vs-all as CSR (threshold and top-k) ---------------------------
+
+def neighbors_packed(X: np.ndarray, Y: np.ndarray, min_shared: int = 1, k: int = 0, exclude_self: bool = False,
+                     self_offset: int = 0, want_dist: bool = True):
+    """Host-pointer entry point (polyhip_mash_neighbors): X (nx, sx) and Y (ny, sy) uint32 sketches ->
+    (first uint64 (nx + 1), cols uint32, shared uint16, dist float64 | None): row i's entries are
+    cols/shared/dist[first[i]:first[i + 1]] -- every j with shared(i, j) >= min_shared (not j == i + self_offset if
+    exclude_self), the k best of them if k > 0 (k <= 1024, POLYHIP_MASH_NEIGHBORS_MAX_K).  The buffers are sized by a
+    guess and, if first[nx] says the guess was too small, by the true count in a second call."""
+    X = np.ascontiguousarray(X, dtype=np.uint32)
+    Y = np.ascontiguousarray(Y, dtype=np.uint32)
+    nx, sx = X.shape
+    ny, sy = Y.shape
+    first = np.zeros(nx + 1, dtype=np.uint64)
+    cap = min(nx * ny, nx * k if k > 0 else max(nx * 1024, 1 << 20))
+    while True:
+        cols = np.zeros(cap, dtype=np.uint32)
+        shared = np.zeros(cap, dtype=np.uint16)
+        dist = np.zeros(cap, dtype=np.float64) if want_dist else None
+        _lib.check(_lib.lib().polyhip_mash_neighbors(
+            X.ctypes.data, nx, sx, Y.ctypes.data, ny, sy, min_shared, k, int(bool(exclude_self)), self_offset,
+            first.ctypes.data, cols.ctypes.data, shared.ctypes.data, dist.ctypes.data if want_dist else None, cap))
+        n = int(first[nx])
+        if n <= cap:
+            return first, cols[:n], shared[:n], dist[:n] if want_dist else None
+        cap = n
+
+
+def Neighbors(sketches: list[Mash], min_shared: int = 1, k: int = 0, exclude_self: bool = True):
+    """Additive batch API: the neighbour lists of a set against itself, one SketchSize; row i = sketches[i]'s
+    (first, cols, shared, dist) as neighbors_packed returns them."""
+    S = np.stack([m.Sketches for m in sketches]).astype(np.uint32)
+    return neighbors_packed(S, S, min_shared, k, exclude_self, 0, True)
+
+
+def neighbors_workspace_bytes(nx: int, sx: int, ny: int, sy: int) -> int:
+    return int(_lib.lib().polyhip_mash_neighbors_workspace_bytes(nx, sx, ny, sy))
+
+
+def neighbors_dev(X_t, Y_t, first_t, cols_t, shared_t, dist_t, work_t, min_shared: int = 1, k: int = 0,
+                  exclude_self: bool = False, self_offset: int = 0, stream=None) -> None:
+    """Device-resident neighbour lists on torch CUDA tensors: X (nx, sx) / Y (ny, sy) int32|uint32, first int64|uint64
+    (nx + 1), cols int32|uint32 / shared int16|uint16 / dist float64 of one capacity (cols_t.numel(); dist_t may be None;
+    cols_t = shared_t = None: the counts alone), work uint8[neighbors_workspace_bytes].  first always carries the true
+    counts; nothing is written beyond the capacity."""
+    nx, sx = X_t.shape
+    ny, sy = Y_t.shape
+    assert X_t.is_cuda and Y_t.is_cuda and first_t.is_cuda and work_t.is_cuda
+    assert X_t.is_contiguous() and Y_t.is_contiguous() and X_t.element_size() == 4 and Y_t.element_size() == 4
+    assert first_t.element_size() == 8 and first_t.numel() == nx + 1 and first_t.is_contiguous()
+    cap = 0
+    if cols_t is not None:
+        cap = cols_t.numel()
+        assert cols_t.is_cuda and shared_t.is_cuda and cols_t.element_size() == 4 and shared_t.element_size() == 2
+        assert shared_t.numel() >= cap and cols_t.is_contiguous() and shared_t.is_contiguous()
+        if dist_t is not None:
+            assert dist_t.is_cuda and dist_t.element_size() == 8 and dist_t.numel() >= cap and dist_t.is_contiguous()
+    _lib.check(_lib.lib().polyhip_mash_neighbors_dev(
+        X_t.data_ptr(), nx, sx, Y_t.data_ptr(), ny, sy, min_shared, k, int(bool(exclude_self)), self_offset,
+        first_t.data_ptr(), cols_t.data_ptr() if cols_t is not None else None,
+        shared_t.data_ptr() if cols_t is not None else None, dist_t.data_ptr() if dist_t is not None else None, cap,
+        work_t.data_ptr(), work_t.numel() * work_t.element_size(), _lib.stream_ptr(stream)))
+
+
+def neighbors_last_info() -> dict:
+    """polyhip_neighbors_info of the calling thread's last neighbour-list call: column blocks of Y, index builds, row
+    ranges joined, the CSR assembly that ran, entries past the threshold, entries listed, devices."""
+    import ctypes as C
+
+    class Info(C.Structure):
+        _fields_ = [("column_blocks", C.c_uint32), ("index_builds", C.c_uint32), ("row_chunks", C.c_uint32),
+                    ("assembly", C.c_uint32), ("entries_thresholded", C.c_uint64), ("entries", C.c_uint64),
+                    ("devices", C.c_uint32), ("reserved", C.c_uint32)]
+    info = Info()
+    _lib.check(_lib.lib().polyhip_mash_neighbors_last_info(C.addressof(info)))
+    return {name: int(getattr(info, name)) for name, _ in Info._fields_ if name != "reserved"}
