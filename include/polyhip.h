@@ -768,6 +768,71 @@ int polyhip_bwt_extract(const polyhip_bwt *h, const int64_t *start,
                         const int64_t *end, uint64_t nreq,
                         const uint64_t *out_off, uint8_t *out, uint32_t *err);
 
+/* ---- read mapping: FM-index seeds, diagonal clusters, SmithWaterman extension (no counterpart in the reference) ---- */
+/*
+ * Places every read of a packed batch on the text T (n bytes) of a polyhip_bwt handle.  For a read r of m bytes:
+ *  1. strands: s = 0 with q = r; if both_strands also s = 1 with q = ReverseComplement(r) (transform.go:15-23, 78-109:
+ *     unmapped bytes become 0x00).
+ *  2. seeds at offsets o = 0, S, 2S, ... while o + L <= m.  A seed's occurrences are all p with T[p, p + L) = q[o, o + L)
+ *     (none when it holds '$' or a byte T lacks).  A seed with more than max_occ occurrences contributes nothing and is
+ *     counted in the info; every other occurrence is a hit on the diagonal d = p - o (signed).
+ *  3. clusters, per strand: with the hits sorted by d, a cluster opens at the smallest unassigned diagonal d0 and takes
+ *     every hit with d <= d0 + W; votes = its hits, dmax = its largest diagonal.
+ *  4. candidates: all clusters of both strands ordered by (votes descending, s ascending, d0 ascending); the first
+ *     max_cand are kept, the position in this order is the rank.
+ *  5. extension of every kept candidate: lo = max(0, d0 - W), hi = min(n, dmax + m + W), SmithWaterman(q, T[lo, hi)) as
+ *     polyhip_sw_align_batch computes it.
+ *  6. if a kept candidate gives the alphabet error the read is unmapped and err is the error of the lowest such rank
+ *     (polyhip_sw_batch's encoding).  Otherwise the best candidate has the highest score, ties to the lowest rank, and the
+ *     read is mapped iff there is one and its score >= min_score.  A mapped read gets: score; second = the highest score
+ *     among its other kept candidates (0 if none); flags bit 0 = mapped, bit 1 = reverse strand; votes of the chosen
+ *     candidate; ref_end = lo + endB, ref_start = ref_end - (non-'-' symbols of alignB); read_end = endA, read_start =
+ *     endA - (non-'-' symbols of alignA), both in q's coordinates; the two aligned strings.  An unmapped read gets zeros
+ *     and empty strings.  A read shorter than seed_len has no seeds (unmapped, err 0); one longer than max_len is unmapped
+ *     with err 0xFFFFFFFF.  nreads == 0 is an empty, successful call.
+ * Strings are packed as in polyhip_sw_align_batch_packed: read i's two strings are [alnOff[i], alnOff[i + 1]) of alnA and
+ * alnB (nreads + 1 offsets); when aln_capacity is too small the call returns POLYHIP_ERR_INVALID after filling everything
+ * else, alnOff[nreads] = the bytes needed.  alnA == NULL: no strings are wanted (alnB, alnOff are not touched).
+ * Errors, in this order: a parameter out of range (seed_len, seed_stride, max_occ >= 1; 1 <= max_cand <= 64; min_score
+ * >= 1) is POLYHIP_ERR_INVALID naming the field, before any device call; max_len > 4096 or band > 1024 is
+ * POLYHIP_ERR_UNSUPPORTED (the per-pair alignment kernels' limits); a NULL handle, or a scoring handle created on another
+ * device than the index's, is POLYHIP_ERR_INVALID.  The call runs on the index's device, as every polyhip_bwt_* call
+ * does; the device list does not apply.
+ * _dev: every pointer is device memory ordered on `stream`; d_off[i] are offsets into d_reads.  The call synchronises
+ * `stream` (it reads back two counts per chunk).  d_work: polyhip_map_workspace_bytes(...) holds the worst case (max_occ
+ * hits per seed) of every read at once, capped at 8 GiB; with less the call loops over chunks of reads (a multiple of 256
+ * each; info.chunks) with the same outputs; less than one chunk of min(nreads, 256) reads needs is POLYHIP_ERR_INVALID.
+ * polyhip_map_last_info: the calling thread's last call.
+ */
+typedef struct polyhip_map_params {
+    uint32_t seed_len, seed_stride, max_occ, band, max_cand, both_strands;
+    int64_t min_score;
+} polyhip_map_params;
+typedef struct polyhip_map_info {
+    uint64_t seeds, seeds_over_max_occ, hits, clusters, pairs_aligned, reads_mapped;
+    uint32_t chunks;
+} polyhip_map_info;
+size_t polyhip_map_workspace_bytes(const polyhip_bwt *h, const polyhip_scoring *sc,
+                                   const polyhip_map_params *params, uint64_t nreads,
+                                   uint32_t max_len);
+int polyhip_map_reads_dev(const polyhip_bwt *h, const polyhip_scoring *sc,
+                          const polyhip_map_params *params, const uint8_t *d_reads,
+                          const uint64_t *d_off, uint64_t nreads, uint32_t max_len,
+                          int64_t *d_score, int64_t *d_second, uint32_t *d_flags,
+                          uint32_t *d_votes, uint32_t *d_ref_start, uint32_t *d_ref_end,
+                          uint32_t *d_read_start, uint32_t *d_read_end, uint32_t *d_err,
+                          uint8_t *d_alnA, uint8_t *d_alnB, uint64_t *d_alnOff,
+                          uint64_t aln_capacity, void *d_work, size_t work_bytes,
+                          polyhip_stream_t stream);
+int polyhip_map_reads(const polyhip_bwt *h, const polyhip_scoring *sc,
+                      const polyhip_map_params *params, const uint8_t *reads,
+                      const uint64_t *off, uint64_t nreads, uint32_t max_len,
+                      int64_t *score, int64_t *second, uint32_t *flags, uint32_t *votes,
+                      uint32_t *ref_start, uint32_t *ref_end, uint32_t *read_start,
+                      uint32_t *read_end, uint32_t *err, uint8_t *alnA, uint8_t *alnB,
+                      uint64_t *alnOff, uint64_t aln_capacity);
+int polyhip_map_last_info(polyhip_map_info *info);
+
 /* ---- R1: the path's one collective -- all-gather of per-rank sketches (RCCL over xGMI) ---- */
 /*
  * For hosts without torch.distributed (the Go/cgo drop-in); one process per GPU.  RCCL is

@@ -1,0 +1,744 @@
+// map_reads.hip -- place reads on an indexed text: FM-index seeds, diagonal clusters, SmithWaterman extension.
+//
+// The definition (include/polyhip.h, polyhip_map_reads) per read r of m bytes, strand s (q = r, or its reverse complement):
+//   seeds at offsets 0, S, 2S .. while o + L <= m; a seed's occurrences p (its SA interval; none when it holds '$' or a byte
+//   the text lacks; dropped and counted when more than max_occ) give hits on the diagonals d = p - o; per strand the hits
+//   sorted by d are cut greedily into clusters [d0, d0 + W]; all clusters ordered by (votes desc, s, d0), the first C kept;
+//   each kept one is extended by SmithWaterman(q, T[max(0, d0 - W), min(n, dmax + m + W))); the best score wins, ties to
+//   the lowest rank.
+// Pipeline per chunk of reads (the chunk is what the workspace holds in the worst case, max_occ hits per seed):
+//   map_seed_kernel     one lane per (read, strand, seed): backward search straight on the read's bytes (strand 1 through
+//                       the complement table, last byte first), interval start + width
+//   scan_excl           hit offsets; the total comes back to the host (grid of the sort)
+//   map_expand_kernel   64-bit keys (read * 2 + strand) << dbits | (d + max_len), one lane per seed
+//   radix_sort          bwt's LSD radix sort over the key's significant bits
+//   map_cluster_kernel  one wave per read: greedy clusters by ballots over 64 sorted hits at a time, the kept candidates
+//                       held rank per lane (insertion by one ballot), windows out
+//   scan_excl           candidate -> pair offsets; the pair count comes back to the host
+//   map_pairs_kernel / map_gather_kernel   the packed A batch (strand-oriented read copies) and B batch (windows of T)
+//   polyhip_sw_align_batch_dev             the existing per-pair-B SmithWaterman, strings in fixed-stride slots
+//   map_reduce_kernel   one wave per read: first error, best and second score, coordinates from the strings' gap counts
+//   map_strings_kernel  the chosen pair's strings packed behind the previous chunk's
+#include "bwt_index.h"
+#include "sw_scoring.h"
+
+namespace polyhip {
+namespace {
+
+constexpr uint32_t MAP_MAX_LEN = 4096, MAP_MAX_BAND = 1024, MAP_MAX_CAND = 64; // the per-pair-B kernels' limits; a wave's lanes
+constexpr uint64_t MAP_CHUNK = 256;                                              // chunks are multiples of this many reads
+constexpr uint64_t MAP_TB_PAIRS = 131072; // pairs whose traceback workspace is held at once (the aligner loops beyond)
+constexpr size_t MAP_WORK_CAP = 8ull << 30;
+
+struct MapShape {
+    uint32_t L, S, max_occ, W, C, strands;
+    uint32_t ns;      // seed slots per (read, strand): seeds of a read of max_len bytes
+    uint32_t max_len; // also the diagonal bias: d + max_len >= 0
+    uint32_t dbits;   // bits of a biased diagonal
+    uint64_t n;       // text length
+};
+
+enum { CNT_SEEDS = 0, CNT_OVER = 1, CNT_CLUSTERS = 2, CNT_MAPPED = 3, CNT_N = 4 };
+
+// transform.complementTable (transform.go:78-109): IUPAC letters in both cases, every other byte -> 0x00
+__device__ __forceinline__ uint32_t dna_complement(uint32_t b)
+{
+    const bool lower = b >= 'a' && b <= 'z';
+    const uint32_t c = dna_complement_upper(lower ? b - 32 : b);
+    return c && lower ? c + 32 : c;
+}
+
+__device__ __forceinline__ void count_add(unsigned long long *cnt, uint32_t v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1)
+        v += __shfl_xor(v, d, 64);
+    if ((threadIdx.x & 63) == 0 && v)
+        atomicAdd(cnt, (unsigned long long)v);
+}
+
+// One lane per seed slot.  start / width = the seed's rows of the index; width 0 for a slot past the read's last seed, a
+// seed without occurrences and a seed with more than max_occ.
+template <int LAYOUT>
+__global__ __launch_bounds__(BT) void map_seed_kernel(Index x, const uint8_t *__restrict__ reads, const uint64_t *__restrict__ off,
+                                                      uint64_t nslots, MapShape g, uint32_t *__restrict__ start,
+                                                      uint32_t *__restrict__ width, unsigned long long *__restrict__ cnt)
+{
+    __shared__ uint8_t code[256];
+    __shared__ uint8_t cmp[256];
+    __shared__ uint32_t Cs[256];
+    code[threadIdx.x] = x.dense[threadIdx.x];
+    cmp[threadIdx.x] = (uint8_t)dna_complement(threadIdx.x);
+    Cs[threadIdx.x] = x.C[threadIdx.x];
+    __syncthreads();
+    uint32_t nseeds = 0, nover = 0;
+    const uint64_t span = (uint64_t)gridDim.x * BT;
+    for (uint64_t base = blockIdx.x * (uint64_t)BT; base < nslots; base += span) {
+        const uint64_t slot = base + threadIdx.x;
+        if (slot < nslots) {
+            const uint32_t k = (uint32_t)(slot % g.ns);
+            const uint64_t rs = slot / g.ns;
+            const uint32_t strand = (uint32_t)(rs % g.strands);
+            const uint64_t r = rs / g.strands;
+            const uint64_t a = off[r], m = off[r + 1] - a;
+            const uint64_t o = (uint64_t)k * g.S;
+            uint32_t s = 0, e = 0;
+            if (m <= g.max_len && o + g.L <= m) {
+                ++nseeds;
+                e = x.N;
+                // q[o + j] for j = L - 1 .. 0: strand 1 reads the read forwards through the complement table
+                const uint8_t *p = strand ? reads + a + (m - o - g.L) : reads + a + o + (g.L - 1);
+                for (uint32_t j = 0; j < g.L && s < e; ++j) {
+                    const uint8_t raw = strand ? p[j] : *(p - j);
+                    const uint8_t ch = strand ? cmp[raw] : raw;
+                    const uint32_t c = code[ch];
+                    if (ch == NULL_CHAR || c == 0xFFu) {
+                        s = e = 0;
+                        break;
+                    }
+                    if (LAYOUT == 0) {
+                        s = Cs[c] + occ_nuc(x, c, s);
+                        e = Cs[c] + occ_nuc(x, c, e);
+                    } else {
+                        s = Cs[c] + occ_gen(x, c, ch, s);
+                        e = Cs[c] + occ_gen(x, c, ch, e);
+                    }
+                }
+            }
+            uint32_t w = e > s ? e - s : 0;
+            if (w > g.max_occ) {
+                ++nover;
+                w = 0;
+            }
+            start[slot] = s;
+            width[slot] = w;
+        }
+    }
+    count_add(cnt + CNT_SEEDS, nseeds);
+    count_add(cnt + CNT_OVER, nover);
+}
+
+// One lane per seed slot: its hits as keys (read * 2 + strand) << dbits | (p - o + max_len), value p
+__global__ __launch_bounds__(BT) void map_expand_kernel(const uint32_t *__restrict__ sa, const uint32_t *__restrict__ start,
+                                                        const uint32_t *__restrict__ first, uint64_t nslots, MapShape g,
+                                                        uint64_t *__restrict__ keys, uint32_t *__restrict__ vals)
+{
+    for (uint64_t slot = blockIdx.x * (uint64_t)BT + threadIdx.x; slot < nslots; slot += (uint64_t)gridDim.x * BT) {
+        const uint32_t f = first[slot], w = first[slot + 1] - f;
+        if (w == 0)
+            continue;
+        const uint32_t k = (uint32_t)(slot % g.ns);
+        const uint64_t rs = slot / g.ns;
+        const uint64_t r = rs / g.strands, strand = rs % g.strands;
+        const uint64_t hi = (r * 2 + strand) << g.dbits;
+        const uint64_t bias = (uint64_t)g.max_len - (uint64_t)k * g.S; // >= 0: a seed starts inside the read
+        const uint32_t s = start[slot];
+        for (uint32_t t = 0; t < w; ++t) {
+            const uint32_t p = sa[s + t];
+            keys[f + t] = hi | ((uint64_t)p + bias);
+            vals[f + t] = p;
+        }
+    }
+}
+
+// One wave per read over its sorted hits.  Lane i holds the candidate of rank i: a new cluster goes behind every kept one
+// with at least its votes (clusters arrive in (strand, d0) order, which is the order among equal votes).
+__global__ __launch_bounds__(BT) void map_cluster_kernel(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ first,
+                                                         const uint64_t *__restrict__ off, uint64_t nreads, MapShape g,
+                                                         uint32_t *__restrict__ ncand, uint32_t *__restrict__ cvotes,
+                                                         uint32_t *__restrict__ cstrand, uint32_t *__restrict__ clo,
+                                                         uint32_t *__restrict__ chi, unsigned long long *__restrict__ cnt)
+{
+    const int lane = threadIdx.x & 63;
+    const uint64_t dmask = (1ull << g.dbits) - 1;
+    for (uint64_t r = (blockIdx.x * (uint64_t)BT + threadIdx.x) / 64; r < nreads; r += (uint64_t)gridDim.x * (BT / 64)) {
+        const int64_t m = (int64_t)(off[r + 1] - off[r]);
+        uint32_t votes = 0, cs = 0, ncl = 0;
+        uint64_t d0k = 0, dmaxk = 0; // biased diagonals
+        for (uint32_t strand = 0; strand < g.strands; ++strand) {
+            const uint64_t s0 = (r * g.strands + strand) * g.ns;
+            uint32_t pos = first[s0];
+            const uint32_t end = first[s0 + g.ns];
+            while (pos < end) {
+                const uint64_t k0 = keys[pos], lim = k0 + g.W;
+                uint32_t n = 0;
+                for (;;) { // the hits are sorted: those within the band are a prefix of each 64
+                    const uint64_t i = (uint64_t)pos + n + lane;
+                    const bool in = i < end && keys[i] <= lim;
+                    const uint32_t c = (uint32_t)__popcll(__ballot(in));
+                    n += c;
+                    if (c < 64)
+                        break;
+                }
+                const uint64_t k1 = keys[pos + n - 1];
+                const int at = __popcll(__ballot(votes >= n)); // free lanes hold 0 votes, n >= 1
+                const uint32_t uv = __shfl_up(votes, 1, 64), us = __shfl_up(cs, 1, 64);
+                const uint64_t ud0 = __shfl_up(d0k, 1, 64), ud1 = __shfl_up(dmaxk, 1, 64);
+                if (lane > at) {
+                    votes = uv, cs = us, d0k = ud0, dmaxk = ud1;
+                } else if (lane == at) {
+                    votes = n, cs = strand, d0k = k0 & dmask, dmaxk = k1 & dmask;
+                }
+                ++ncl;
+                pos += n;
+            }
+        }
+        const uint32_t nc = min(ncl, g.C);
+        if ((uint32_t)lane < nc) {
+            const int64_t d0 = (int64_t)d0k - g.max_len, d1 = (int64_t)dmaxk - g.max_len;
+            const int64_t lo_ = d0 - (int64_t)g.W, hi_ = d1 + m + (int64_t)g.W;
+            const int64_t lo = lo_ > 0 ? lo_ : 0, hi = hi_ < (int64_t)g.n ? hi_ : (int64_t)g.n;
+            const uint64_t o = r * g.C + lane;
+            cvotes[o] = votes;
+            cstrand[o] = cs;
+            clo[o] = (uint32_t)lo;
+            chi[o] = (uint32_t)hi;
+        }
+        if (lane == 0) {
+            ncand[r] = nc;
+            if (ncl)
+                atomicAdd(cnt + CNT_CLUSTERS, (unsigned long long)ncl);
+        }
+    }
+}
+
+// One lane per (read, rank): the pair's read and the lengths of its A and B (scanned into offsets afterwards)
+__global__ __launch_bounds__(BT) void map_pairs_kernel(const uint32_t *__restrict__ pfirst, const uint64_t *__restrict__ off,
+                                                       const uint32_t *__restrict__ clo, const uint32_t *__restrict__ chi,
+                                                       uint64_t nreads, uint32_t C, uint32_t *__restrict__ pread,
+                                                       uint64_t *__restrict__ lenA, uint64_t *__restrict__ lenB)
+{
+    const uint64_t total = nreads * C;
+    for (uint64_t i = blockIdx.x * (uint64_t)BT + threadIdx.x; i < total; i += (uint64_t)gridDim.x * BT) {
+        const uint64_t r = i / C;
+        const uint32_t rank = (uint32_t)(i - r * C), p0 = pfirst[r];
+        if (rank >= pfirst[r + 1] - p0)
+            continue;
+        pread[p0 + rank] = (uint32_t)r;
+        lenA[p0 + rank] = off[r + 1] - off[r];
+        lenB[p0 + rank] = chi[i] - clo[i];
+    }
+}
+
+// One wave per pair: A = the read on the candidate's strand, B = its window of the text
+__global__ __launch_bounds__(BT) void map_gather_kernel(const uint8_t *__restrict__ reads, const uint64_t *__restrict__ off,
+                                                        const uint8_t *__restrict__ text, const uint32_t *__restrict__ pread,
+                                                        const uint32_t *__restrict__ pfirst, const uint32_t *__restrict__ cstrand,
+                                                        const uint32_t *__restrict__ clo, uint32_t C, uint64_t npairs,
+                                                        const uint64_t *__restrict__ offA, const uint64_t *__restrict__ offB,
+                                                        uint8_t *__restrict__ A, uint8_t *__restrict__ B)
+{
+    __shared__ uint8_t cmp[256];
+    cmp[threadIdx.x] = (uint8_t)dna_complement(threadIdx.x);
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    for (uint64_t p = (blockIdx.x * (uint64_t)BT + threadIdx.x) / 64; p < npairs; p += (uint64_t)gridDim.x * (BT / 64)) {
+        const uint32_t r = pread[p];
+        const uint64_t c = (uint64_t)r * C + (p - pfirst[r]);
+        const uint8_t *src = reads + off[r];
+        const uint64_t m = offA[p + 1] - offA[p], lb = offB[p + 1] - offB[p];
+        uint8_t *da = A + offA[p], *db = B + offB[p];
+        if (cstrand[c]) {
+            for (uint64_t i = lane; i < m; i += 64)
+                da[i] = cmp[src[m - 1 - i]];
+        } else {
+            for (uint64_t i = lane; i < m; i += 64)
+                da[i] = src[i];
+        }
+        const uint8_t *t = text + clo[c];
+        for (uint64_t i = lane; i < lb; i += 64)
+            db[i] = t[i];
+    }
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1)
+        v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+// One wave per read, lane i = its candidate of rank i.  slen / best: the chosen pair's string length (0 unmapped) and index.
+__global__ __launch_bounds__(BT) void map_reduce_kernel(const uint32_t *__restrict__ pfirst, const uint64_t *__restrict__ off, uint64_t nreads,
+                                                        MapShape g, int64_t min_score, const int64_t *__restrict__ pscore,
+                                                        const uint32_t *__restrict__ pendA, const uint32_t *__restrict__ pendB,
+                                                        const uint32_t *__restrict__ perr, const uint32_t *__restrict__ plen,
+                                                        const uint8_t *__restrict__ slotA, const uint8_t *__restrict__ slotB, uint32_t stride,
+                                                        const uint32_t *__restrict__ cvotes, const uint32_t *__restrict__ cstrand,
+                                                        const uint32_t *__restrict__ clo, int64_t *__restrict__ o_score,
+                                                        int64_t *__restrict__ o_second, uint32_t *__restrict__ o_flags,
+                                                        uint32_t *__restrict__ o_votes, uint32_t *__restrict__ o_rs, uint32_t *__restrict__ o_re,
+                                                        uint32_t *__restrict__ o_qs, uint32_t *__restrict__ o_qe, uint32_t *__restrict__ o_err,
+                                                        uint64_t *__restrict__ slen, uint32_t *__restrict__ best, unsigned long long *__restrict__ cnt)
+{
+    const int lane = threadIdx.x & 63;
+    uint32_t nmapped = 0;
+    for (uint64_t r = (blockIdx.x * (uint64_t)BT + threadIdx.x) / 64; r < nreads; r += (uint64_t)gridDim.x * (BT / 64)) {
+        const uint32_t p0 = pfirst[r], nc = pfirst[r + 1] - p0;
+        const bool have = (uint32_t)lane < nc;
+        const int64_t sc = have ? pscore[p0 + lane] : INT64_MIN;
+        const uint32_t er = have ? perr[p0 + lane] : 0u;
+        const uint64_t bad = __ballot(er != 0);
+        uint32_t err = off[r + 1] - off[r] > g.max_len ? 0xFFFFFFFFu : 0u;
+        if (bad)
+            err = __shfl(er, __ffsll((unsigned long long)bad) - 1, 64);
+        // the highest score, ties to the lowest rank
+        int64_t bs = sc;
+        int bi = lane;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            const int64_t os = __shfl_xor(bs, d, 64);
+            const int oi = __shfl_xor(bi, d, 64);
+            if (os > bs || (os == bs && oi < bi))
+                bs = os, bi = oi;
+        }
+        int64_t second = have && lane != bi ? sc : 0; // 0 without another candidate
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            const int64_t other = __shfl_xor(second, d, 64);
+            second = other > second ? other : second;
+        }
+        const bool mapped = nc > 0 && err == 0 && bs >= min_score;
+        uint32_t len = 0, ga = 0, gb = 0;
+        const uint32_t bp = p0 + (uint32_t)bi;
+        if (mapped) {
+            len = plen[bp];
+            const uint8_t *sa_ = slotA + (uint64_t)bp * stride + (stride - len), *sb_ = slotB + (uint64_t)bp * stride + (stride - len);
+            for (uint32_t i = lane; i < len; i += 64) {
+                ga += sa_[i] != '-';
+                gb += sb_[i] != '-';
+            }
+            ga = wave_sum(ga);
+            gb = wave_sum(gb);
+        }
+        if (lane == 0) {
+            const uint64_t c = r * g.C + (uint32_t)bi;
+            const uint32_t eA = mapped ? pendA[bp] : 0u, eB = mapped ? clo[c] + pendB[bp] : 0u;
+            o_score[r] = mapped ? bs : 0;
+            o_second[r] = mapped ? second : 0;
+            o_flags[r] = mapped ? 1u | (cstrand[c] << 1) : 0u;
+            o_votes[r] = mapped ? cvotes[c] : 0u;
+            o_re[r] = eB;
+            o_rs[r] = eB - gb;
+            o_qe[r] = eA;
+            o_qs[r] = eA - ga;
+            o_err[r] = err;
+            slen[r] = len;
+            best[r] = bp;
+            nmapped += mapped;
+        }
+    }
+    count_add(cnt + CNT_MAPPED, nmapped);
+}
+
+// One wave per read: alnOff[r] = *base + soff[r]; the chosen pair's strings go there when they fit the buffers whole
+__global__ __launch_bounds__(BT) void map_strings_kernel(const uint64_t *__restrict__ soff, const uint32_t *__restrict__ best, uint64_t nreads,
+                                                         const uint8_t *__restrict__ slotA, const uint8_t *__restrict__ slotB, uint32_t stride,
+                                                         const uint64_t *__restrict__ base, uint64_t *__restrict__ alnOff,
+                                                         uint8_t *__restrict__ outA, uint8_t *__restrict__ outB, uint64_t capacity)
+{
+    const int lane = threadIdx.x & 63;
+    for (uint64_t r = (blockIdx.x * (uint64_t)BT + threadIdx.x) / 64; r < nreads; r += (uint64_t)gridDim.x * (BT / 64)) {
+        const uint64_t o = *base + soff[r], len = soff[r + 1] - soff[r];
+        if (lane == 0)
+            alnOff[r] = o;
+        if (len == 0 || o + len > capacity)
+            continue;
+        const uint64_t src = (uint64_t)best[r] * stride + (stride - len);
+        for (uint64_t i = lane; i < len; i += 64) {
+            outA[o + i] = slotA[src + i];
+            outB[o + i] = slotB[src + i];
+        }
+    }
+}
+
+// after a chunk's strings: the running total, which is also alnOff's last entry
+__global__ void map_advance_kernel(uint64_t *__restrict__ base, const uint64_t *__restrict__ chunk_total, uint64_t *__restrict__ alnOff_end)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const uint64_t t = *base + *chunk_total;
+        *base = t;
+        *alnOff_end = t;
+    }
+}
+
+// ---- the workspace of a chunk of nr reads ---------------------------------------------------------------------------------
+struct MapWork {
+    unsigned long long *cnt; // CNT_N counters, then the strings' running total
+    uint32_t *start, *first;
+    uint64_t *ka, *kb;
+    uint32_t *va, *vb, *hist;
+    uint8_t *scratch;
+    uint32_t *pfirst, *cvotes, *cstrand, *clo, *chi, *pread;
+    uint64_t *offA, *offB;
+    uint8_t *A, *B;
+    int64_t *score;
+    uint32_t *endA, *endB, *err, *alnLen;
+    uint8_t *slotA, *slotB;
+    void *sw_work, *tb_work;
+    size_t sw_bytes, tb_bytes;
+    uint64_t *soff;
+    uint32_t *best;
+    uint64_t hcap, pcap;
+    uint32_t lenB, stride;
+};
+
+// carves the chunk's arrays out of `base` (nullptr: sizes only) and returns the bytes; 0 = the chunk cannot be held at all
+// (2^31 hits or more)
+size_t map_carve(const polyhip_scoring *sc, const MapShape &g, uint64_t nr, uint8_t *base, MapWork *out)
+{
+    MapWork w{};
+    const uint64_t slots = nr * g.strands * g.ns;
+    w.hcap = slots * g.max_occ;
+    w.pcap = nr * g.C;
+    if (w.hcap >= (1ull << 31) || w.pcap >= (1ull << 31))
+        return 0;
+    w.lenB = g.max_len + 3 * g.W;
+    w.stride = polyhip_sw_traceback_stride(sc, g.max_len, w.lenB);
+    const uint64_t nb = radix_blocks(std::max<uint64_t>(w.hcap, 1));
+    Carve c{base};
+    w.cnt = c.take<unsigned long long>(CNT_N + 1);
+    w.start = c.take<uint32_t>(slots);
+    w.first = c.take<uint32_t>(slots + 1);
+    w.ka = c.take<uint64_t>(w.hcap);
+    w.kb = c.take<uint64_t>(w.hcap);
+    w.va = c.take<uint32_t>(w.hcap);
+    w.vb = c.take<uint32_t>(w.hcap);
+    w.hist = c.take<uint32_t>(256 * nb + 1);
+    const size_t sb = std::max(std::max(scan_scratch_bytes<uint32_t>(256 * nb), scan_scratch_bytes<uint32_t>(slots)),
+                               std::max(scan_scratch_bytes<uint64_t>(w.pcap), scan_scratch_bytes<uint64_t>(nr)));
+    w.scratch = c.take<uint8_t>(sb);
+    w.pfirst = c.take<uint32_t>(nr + 1);
+    w.cvotes = c.take<uint32_t>(w.pcap);
+    w.cstrand = c.take<uint32_t>(w.pcap);
+    w.clo = c.take<uint32_t>(w.pcap);
+    w.chi = c.take<uint32_t>(w.pcap);
+    w.pread = c.take<uint32_t>(w.pcap);
+    w.offA = c.take<uint64_t>(w.pcap + 1);
+    w.offB = c.take<uint64_t>(w.pcap + 1);
+    w.A = c.take<uint8_t>(w.pcap * g.max_len + 64); // (the aligner's vector loads run a few bytes past a sequence)
+    w.B = c.take<uint8_t>(w.pcap * w.lenB + 64);
+    w.score = c.take<int64_t>(w.pcap);
+    w.endA = c.take<uint32_t>(w.pcap);
+    w.endB = c.take<uint32_t>(w.pcap);
+    w.err = c.take<uint32_t>(w.pcap);
+    w.alnLen = c.take<uint32_t>(w.pcap);
+    w.slotA = c.take<uint8_t>(w.pcap * w.stride);
+    w.slotB = c.take<uint8_t>(w.pcap * w.stride);
+    w.sw_bytes = std::max<size_t>(polyhip_sw_workspace_bytes(sc, w.pcap, g.max_len, w.lenB, 0), 256);
+    w.sw_work = c.take<uint8_t>(w.sw_bytes);
+    w.tb_bytes = polyhip_sw_traceback_workspace_bytes(sc, std::min(w.pcap, MAP_TB_PAIRS), g.max_len, w.lenB);
+    w.tb_work = c.take<uint8_t>(w.tb_bytes);
+    w.soff = c.take<uint64_t>(nr + 1);
+    w.best = c.take<uint32_t>(nr);
+    if (out)
+        *out = w;
+    return c.used;
+}
+
+// reads per chunk that `bytes` hold: every read when they all fit, else a multiple of MAP_CHUNK (0: not even one)
+uint64_t map_chunk_reads(const polyhip_scoring *sc, const MapShape &g, uint64_t nreads, size_t bytes)
+{
+    auto fits = [&](uint64_t nr) {
+        const size_t need = map_carve(sc, g, nr, nullptr, nullptr);
+        return need != 0 && need <= bytes;
+    };
+    if (fits(nreads))
+        return nreads;
+    uint64_t lo = 0, hi = (nreads + MAP_CHUNK - 1) / MAP_CHUNK; // chunks of lo * MAP_CHUNK fit, of hi * MAP_CHUNK do not
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        (fits(mid * MAP_CHUNK) ? lo : hi) = mid;
+    }
+    return lo * MAP_CHUNK;
+}
+
+const char *check_params(const polyhip_map_params *p)
+{
+    if (!p)
+        return "null parameters";
+    if (p->seed_len < 1)
+        return "seed_len must be at least 1";
+    if (p->seed_stride < 1)
+        return "seed_stride must be at least 1";
+    if (p->max_occ < 1)
+        return "max_occ must be at least 1";
+    if (p->max_cand < 1 || p->max_cand > MAP_MAX_CAND)
+        return "max_cand must be 1..64";
+    if (p->min_score < 1)
+        return "min_score must be at least 1";
+    return nullptr;
+}
+
+MapShape make_shape(const polyhip_map_params *p, uint64_t n, uint32_t max_len)
+{
+    MapShape g{};
+    g.L = p->seed_len;
+    g.S = p->seed_stride;
+    g.max_occ = p->max_occ;
+    g.W = p->band;
+    g.C = p->max_cand;
+    g.strands = p->both_strands ? 2 : 1;
+    g.ns = max_len >= g.L ? (max_len - g.L) / g.S + 1 : 0;
+    g.max_len = max_len;
+    g.dbits = (uint32_t)bits_for(n + max_len);
+    g.n = n;
+    return g;
+}
+
+thread_local polyhip_map_info t_info{};
+
+int validate(const char *who, const polyhip_bwt *hp, const polyhip_scoring *sc, const polyhip_map_params *p, uint32_t max_len)
+{
+    if (const char *bad = check_params(p))
+        return set_error(POLYHIP_ERR_INVALID, "%s: %s", who, bad);
+    if (max_len > MAP_MAX_LEN)
+        return set_error(POLYHIP_ERR_UNSUPPORTED, "%s: max_len %u exceeds %u (the per-pair alignment kernels' limit)", who, max_len,
+                         MAP_MAX_LEN);
+    if (p->band > MAP_MAX_BAND)
+        return set_error(POLYHIP_ERR_UNSUPPORTED, "%s: band %u exceeds %u", who, p->band, MAP_MAX_BAND);
+    PH_REQUIRE(hp, "%s: null index handle", who);
+    PH_REQUIRE(sc, "%s: null scoring handle", who);
+    PH_REQUIRE(sc->device == as_h(hp)->dev, "%s: the scoring handle lives on device %d, the index on device %d", who, sc->device,
+               as_h(hp)->dev);
+    return POLYHIP_OK;
+}
+
+struct MapOut {
+    int64_t *score, *second;
+    uint32_t *flags, *votes, *ref_start, *ref_end, *read_start, *read_end, *err;
+    uint8_t *alnA, *alnB;
+    uint64_t *alnOff;
+    uint64_t capacity;
+};
+
+// The call on device pointers, on the index's device (the caller has entered it).  *needed = the strings' bytes.
+int map_run(const BwtHandle *h, const polyhip_scoring *sc, const polyhip_map_params *p, const uint8_t *d_reads, const uint64_t *d_off,
+            uint64_t nreads, uint32_t max_len, const MapOut &o, void *d_work, size_t work_bytes, hipStream_t st, uint64_t *needed)
+{
+    const char *who = "polyhip_map_reads";
+    polyhip_map_info info{};
+    *needed = 0;
+    const bool strings = o.alnA != nullptr;
+    if (nreads == 0) {
+        if (o.alnOff)
+            PH_HIP(hipMemsetAsync(o.alnOff, 0, sizeof(uint64_t), st));
+        t_info = info;
+        return POLYHIP_OK;
+    }
+    PH_REQUIRE(d_off && o.score && o.second && o.flags && o.votes && o.ref_start && o.ref_end && o.read_start && o.read_end && o.err,
+               "%s: null argument", who);
+    PH_REQUIRE(!strings || (o.alnB && o.alnOff), "%s: alnA without alnB / alnOff", who);
+    const MapShape g = make_shape(p, h->n, max_len);
+    const uint64_t per = map_chunk_reads(sc, g, nreads, d_work ? work_bytes : 0);
+    PH_REQUIRE(per > 0, "%s: a workspace of %zu bytes does not hold a chunk of %llu reads (%zu bytes)", who, work_bytes,
+               (unsigned long long)std::min<uint64_t>(nreads, MAP_CHUNK),
+               map_carve(sc, g, std::min<uint64_t>(nreads, MAP_CHUNK), nullptr, nullptr));
+    MapWork w;
+    (void)map_carve(sc, g, per, static_cast<uint8_t *>(d_work), &w);
+    uint64_t *sbase = reinterpret_cast<uint64_t *>(w.cnt + CNT_N);
+    PH_HIP(hipMemsetAsync(w.cnt, 0, (CNT_N + 1) * sizeof(unsigned long long), st));
+    SyncOnExit sync(st); // counts are read back into locals
+    for (uint64_t r0 = 0; r0 < nreads; r0 += per, ++info.chunks) {
+        const uint64_t nr = std::min(per, nreads - r0), slots = nr * g.strands * g.ns;
+        const uint64_t *off = d_off + r0;
+        // seeds -> hits
+        uint32_t nhits = 0;
+        if (slots) {
+            if (h->x.layout == 0)
+                hipLaunchKernelGGL(map_seed_kernel<0>, dim3(grid_for(slots)), dim3(BT), 0, st, h->x, d_reads, off, slots, g, w.start, w.first,
+                                   w.cnt);
+            else
+                hipLaunchKernelGGL(map_seed_kernel<1>, dim3(grid_for(slots)), dim3(BT), 0, st, h->x, d_reads, off, slots, g, w.start, w.first,
+                                   w.cnt);
+            PH_HIP(hipGetLastError());
+            PH_HIP(scan_excl<uint32_t>(w.first, w.first, slots, w.scratch, st));
+            PH_HIP(hipMemcpyAsync(&nhits, w.first + slots, sizeof nhits, hipMemcpyDeviceToHost, st));
+            PH_HIP(hipStreamSynchronize(st));
+        }
+        info.hits += nhits;
+        uint32_t npairs = 0;
+        uint64_t *ka = w.ka, *kb = w.kb;
+        uint32_t *va = w.va, *vb = w.vb;
+        if (nhits) {
+            hipLaunchKernelGGL(map_expand_kernel, dim3(grid_for(slots)), dim3(BT), 0, st, h->d_sa, w.start, w.first, slots, g, ka, va);
+            PH_HIP(hipGetLastError());
+            if (int rc = radix_sort(ka, va, kb, vb, nhits, (int)g.dbits + bits_for(2 * nr - 1), w.hist, w.scratch, st))
+                return rc;
+            hipLaunchKernelGGL(map_cluster_kernel, dim3(grid_for(nr * 64)), dim3(BT), 0, st, ka, w.first, off, nr, g, w.pfirst, w.cvotes,
+                               w.cstrand, w.clo, w.chi, w.cnt);
+            PH_HIP(hipGetLastError());
+            PH_HIP(scan_excl<uint32_t>(w.pfirst, w.pfirst, nr, w.scratch, st));
+            PH_HIP(hipMemcpyAsync(&npairs, w.pfirst + nr, sizeof npairs, hipMemcpyDeviceToHost, st));
+            PH_HIP(hipStreamSynchronize(st));
+        } else {
+            PH_HIP(hipMemsetAsync(w.pfirst, 0, (nr + 1) * sizeof(uint32_t), st)); // no read has a candidate
+        }
+        info.pairs_aligned += npairs;
+        if (npairs) {
+            hipLaunchKernelGGL(map_pairs_kernel, dim3(grid_for(nr * g.C)), dim3(BT), 0, st, w.pfirst, off, w.clo, w.chi, nr, g.C, w.pread,
+                               w.offA, w.offB);
+            PH_HIP(hipGetLastError());
+            PH_HIP(scan_excl<uint64_t>(w.offA, w.offA, npairs, w.scratch, st));
+            PH_HIP(scan_excl<uint64_t>(w.offB, w.offB, npairs, w.scratch, st));
+            hipLaunchKernelGGL(map_gather_kernel, dim3(grid_for((uint64_t)npairs * 64)), dim3(BT), 0, st, d_reads, off, h->d_text, w.pread,
+                               w.pfirst, w.cstrand, w.clo, g.C, (uint64_t)npairs, w.offA, w.offB, w.A, w.B);
+            PH_HIP(hipGetLastError());
+            if (int rc = polyhip_sw_align_batch_dev(sc, w.A, w.offA, npairs, g.max_len, w.B, w.offB, w.lenB, w.score, w.endA, w.endB, w.err,
+                                                    w.slotA, w.slotB, w.alnLen, w.stride, w.sw_work, w.sw_bytes, w.tb_work, w.tb_bytes, st))
+                return rc;
+        }
+        hipLaunchKernelGGL(map_reduce_kernel, dim3(grid_for(nr * 64)), dim3(BT), 0, st, w.pfirst, off, nr, g, p->min_score, w.score, w.endA,
+                           w.endB, w.err, w.alnLen, w.slotA, w.slotB, w.stride, w.cvotes, w.cstrand, w.clo, o.score + r0, o.second + r0,
+                           o.flags + r0, o.votes + r0, o.ref_start + r0, o.ref_end + r0, o.read_start + r0, o.read_end + r0, o.err + r0,
+                           w.soff, w.best, w.cnt);
+        PH_HIP(hipGetLastError());
+        if (strings) {
+            PH_HIP(scan_excl<uint64_t>(w.soff, w.soff, nr, w.scratch, st));
+            hipLaunchKernelGGL(map_strings_kernel, dim3(grid_for(nr * 64)), dim3(BT), 0, st, w.soff, w.best, nr, w.slotA, w.slotB, w.stride,
+                               sbase, o.alnOff + r0, o.alnA, o.alnB, o.capacity);
+            PH_HIP(hipGetLastError());
+            hipLaunchKernelGGL(map_advance_kernel, dim3(1), dim3(64), 0, st, sbase, w.soff + nr, o.alnOff + nreads);
+            PH_HIP(hipGetLastError());
+        }
+    }
+    unsigned long long cnt[CNT_N + 1];
+    PH_HIP(hipMemcpyAsync(cnt, w.cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
+    PH_HIP(hipStreamSynchronize(st));
+    info.seeds = cnt[CNT_SEEDS];
+    info.seeds_over_max_occ = cnt[CNT_OVER];
+    info.clusters = cnt[CNT_CLUSTERS];
+    info.reads_mapped = cnt[CNT_MAPPED];
+    t_info = info;
+    *needed = cnt[CNT_N];
+    if (strings && *needed > o.capacity)
+        return set_error(POLYHIP_ERR_INVALID, "%s: the aligned strings need %llu bytes, the buffers hold %llu", who,
+                         (unsigned long long)*needed, (unsigned long long)o.capacity);
+    return POLYHIP_OK;
+}
+
+// the whole-batch workspace, capped: what map_run cuts its chunks from
+size_t map_workspace(const polyhip_scoring *sc, const MapShape &g, uint64_t nreads)
+{
+    if (nreads == 0)
+        return 0;
+    const uint64_t padded = nreads <= MAP_CHUNK ? nreads : (nreads + MAP_CHUNK - 1) / MAP_CHUNK * MAP_CHUNK;
+    const size_t all = map_carve(sc, g, padded, nullptr, nullptr);
+    if (all != 0 && all <= MAP_WORK_CAP)
+        return all;
+    const uint64_t per = std::max<uint64_t>(map_chunk_reads(sc, g, padded, MAP_WORK_CAP), MAP_CHUNK);
+    return map_carve(sc, g, per, nullptr, nullptr);
+}
+
+} // namespace
+} // namespace polyhip
+
+using namespace polyhip;
+
+extern "C" {
+
+size_t polyhip_map_workspace_bytes(const polyhip_bwt *hp, const polyhip_scoring *sc, const polyhip_map_params *p, uint64_t nreads,
+                                   uint32_t max_len)
+{
+    if (!hp || !sc || check_params(p) || max_len > MAP_MAX_LEN || p->band > MAP_MAX_BAND)
+        return 0;
+    return map_workspace(sc, make_shape(p, as_h(hp)->n, max_len), nreads);
+}
+
+int polyhip_map_reads_dev(const polyhip_bwt *hp, const polyhip_scoring *sc, const polyhip_map_params *p, const uint8_t *d_reads,
+                          const uint64_t *d_off, uint64_t nreads, uint32_t max_len, int64_t *d_score, int64_t *d_second, uint32_t *d_flags,
+                          uint32_t *d_votes, uint32_t *d_ref_start, uint32_t *d_ref_end, uint32_t *d_read_start, uint32_t *d_read_end,
+                          uint32_t *d_err, uint8_t *d_alnA, uint8_t *d_alnB, uint64_t *d_alnOff, uint64_t aln_capacity, void *d_work,
+                          size_t work_bytes, polyhip_stream_t stream)
+{
+    if (int rc = validate("polyhip_map_reads_dev", hp, sc, p, max_len))
+        return rc;
+    const BwtHandle *h = as_h(hp);
+    DeviceScope ds;
+    PH_HIP(ds.enter(h->dev));
+    const MapOut o{d_score, d_second, d_flags, d_votes, d_ref_start, d_ref_end, d_read_start, d_read_end, d_err, d_alnA, d_alnB, d_alnOff,
+                   aln_capacity};
+    uint64_t needed = 0;
+    return map_run(h, sc, p, d_reads, d_off, nreads, max_len, o, d_work, work_bytes, as_stream(stream), &needed);
+}
+
+int polyhip_map_reads(const polyhip_bwt *hp, const polyhip_scoring *sc, const polyhip_map_params *p, const uint8_t *reads,
+                      const uint64_t *off, uint64_t nreads, uint32_t max_len, int64_t *score, int64_t *second, uint32_t *flags,
+                      uint32_t *votes, uint32_t *ref_start, uint32_t *ref_end, uint32_t *read_start, uint32_t *read_end, uint32_t *err,
+                      uint8_t *alnA, uint8_t *alnB, uint64_t *alnOff, uint64_t aln_capacity)
+{
+    const char *who = "polyhip_map_reads";
+    if (int rc = validate(who, hp, sc, p, max_len))
+        return rc;
+    const bool strings = alnA != nullptr;
+    if (nreads == 0) {
+        if (alnOff)
+            alnOff[0] = 0;
+        t_info = polyhip_map_info{};
+        return POLYHIP_OK;
+    }
+    PH_REQUIRE(off && score && second && flags && votes && ref_start && ref_end && read_start && read_end && err, "%s: null argument", who);
+    PH_REQUIRE(!strings || (alnB && alnOff), "%s: alnA without alnB / alnOff", who);
+    for (uint64_t i = 0; i < nreads; ++i)
+        PH_REQUIRE(off[i] <= off[i + 1], "%s: offsets are not ascending at %llu", who, (unsigned long long)i);
+    const uint64_t nbytes = off[nreads] - off[0];
+    PH_REQUIRE(reads || nbytes == 0, "%s: null read buffer", who);
+    const BwtHandle *h = as_h(hp);
+    DeviceScope ds;
+    PH_HIP(ds.enter(h->dev));
+    hipStream_t st = h->stream;
+    const size_t wb = map_workspace(sc, make_shape(p, h->n, max_len), nreads);
+    // outputs in one block: two int64 and seven uint32 per read, then the string offsets
+    DevBuf dreads, doff, dout, dA, dB, dwork;
+    PH_HIP(dreads.alloc(nbytes + 64));
+    PH_HIP(doff.alloc((nreads + 1) * sizeof(uint64_t)));
+    PH_HIP(dout.alloc(nreads * (2 * 8 + 7 * 4) + (nreads + 1) * 8));
+    if (strings) {
+        PH_HIP(dA.alloc(aln_capacity));
+        PH_HIP(dB.alloc(aln_capacity));
+    }
+    PH_HIP(dwork.alloc(wb));
+    std::vector<uint64_t> rebased(nreads + 1);
+    for (uint64_t i = 0; i <= nreads; ++i)
+        rebased[i] = off[i] - off[0];
+    SyncOnExit sync(st);
+    if (nbytes)
+        PH_HIP(hipMemcpyAsync(dreads.p, reads + off[0], nbytes, hipMemcpyHostToDevice, st));
+    PH_HIP(hipMemcpyAsync(doff.p, rebased.data(), (nreads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    int64_t *d64 = dout.as<int64_t>();
+    uint64_t *dao = reinterpret_cast<uint64_t *>(d64 + 2 * nreads);
+    uint32_t *d32 = reinterpret_cast<uint32_t *>(dao + nreads + 1);
+    const MapOut o{d64, d64 + nreads, d32, d32 + nreads, d32 + 2 * nreads, d32 + 3 * nreads, d32 + 4 * nreads, d32 + 5 * nreads,
+                   d32 + 6 * nreads, strings ? dA.as<uint8_t>() : nullptr, strings ? dB.as<uint8_t>() : nullptr, strings ? dao : nullptr,
+                   aln_capacity};
+    uint64_t needed = 0;
+    const int rc = map_run(h, sc, p, dreads.as<uint8_t>(), doff.as<uint64_t>(), nreads, max_len, o, dwork.p, wb, st, &needed);
+    if (rc != POLYHIP_OK && !(strings && needed > aln_capacity))
+        return rc;
+    // (a call whose only failure is the strings' capacity still delivers everything else)
+    uint32_t *const h32[7] = {flags, votes, ref_start, ref_end, read_start, read_end, err};
+    PH_HIP(hipMemcpyAsync(score, o.score, nreads * 8, hipMemcpyDeviceToHost, st));
+    PH_HIP(hipMemcpyAsync(second, o.second, nreads * 8, hipMemcpyDeviceToHost, st));
+    for (int q = 0; q < 7; ++q)
+        PH_HIP(hipMemcpyAsync(h32[q], d32 + q * nreads, nreads * 4, hipMemcpyDeviceToHost, st));
+    if (strings) {
+        PH_HIP(hipMemcpyAsync(alnOff, dao, (nreads + 1) * 8, hipMemcpyDeviceToHost, st));
+        const uint64_t fit = std::min(needed, aln_capacity);
+        if (fit) {
+            PH_HIP(hipMemcpyAsync(alnA, dA.p, fit, hipMemcpyDeviceToHost, st));
+            PH_HIP(hipMemcpyAsync(alnB, dB.p, fit, hipMemcpyDeviceToHost, st));
+        }
+    }
+    PH_HIP(hipStreamSynchronize(st));
+    return rc;
+}
+
+int polyhip_map_last_info(polyhip_map_info *info)
+{
+    PH_REQUIRE(info, "polyhip_map_last_info: null argument");
+    *info = t_info;
+    return POLYHIP_OK;
+}
+
+} // extern "C"

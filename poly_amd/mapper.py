@@ -1,0 +1,174 @@
+"""Read mapping on MI355X: FM-index seeds (poly_amd.bwt), diagonal clusters, SmithWaterman extension (poly_amd.align).
+
+The reference has no mapper; the definition is the comment above ``polyhip_map_reads`` in include/polyhip.h and
+tests/map_oracle.py restates it on the CPU.  Everything is computed in HIP (polyhip_map_*); nothing is computed here.
+
+Reads are Go strings, i.e. bytes: a ``str`` is taken one byte per character (latin-1), and ``MapReads`` returns aligned
+strings as ``str`` when the reads were ``str`` (``bytes`` otherwise), as poly_amd.bwt does.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _lib
+from .mash import _pack
+
+FLAG_MAPPED, FLAG_REVERSE = 1, 2
+
+
+class _CParams(C.Structure):
+    _fields_ = [("seed_len", C.c_uint32), ("seed_stride", C.c_uint32), ("max_occ", C.c_uint32), ("band", C.c_uint32),
+                ("max_cand", C.c_uint32), ("both_strands", C.c_uint32), ("min_score", C.c_int64)]
+
+
+class _CInfo(C.Structure):
+    _fields_ = [("seeds", C.c_uint64), ("seeds_over_max_occ", C.c_uint64), ("hits", C.c_uint64), ("clusters", C.c_uint64),
+                ("pairs_aligned", C.c_uint64), ("reads_mapped", C.c_uint64), ("chunks", C.c_uint32)]
+
+
+@dataclass
+class MapParams:
+    """polyhip_map_params.  The defaults are unmeasured: they are what short-read mappers commonly start from, not the
+    result of a sweep on this hardware."""
+    seed_len: int = 20
+    seed_stride: int = 10
+    max_occ: int = 32
+    band: int = 24
+    max_cand: int = 4
+    both_strands: bool = True
+    min_score: int = 1
+
+    def _c(self) -> _CParams:
+        return _CParams(int(self.seed_len), int(self.seed_stride), int(self.max_occ), int(self.band), int(self.max_cand),
+                        1 if self.both_strands else 0, int(self.min_score))
+
+
+@dataclass
+class MapResult:
+    """one entry per read; ``alignA[i]`` / ``alignB[i]`` are bytes (None when no strings were asked for)"""
+    score: np.ndarray
+    second: np.ndarray
+    flags: np.ndarray
+    votes: np.ndarray
+    ref_start: np.ndarray
+    ref_end: np.ndarray
+    read_start: np.ndarray
+    read_end: np.ndarray
+    err: np.ndarray
+    alignA: list | None
+    alignB: list | None
+    aln_off: np.ndarray | None = None
+    status: int = 0
+
+
+@dataclass
+class MapRecord:
+    mapped: bool
+    reverse: bool
+    score: int
+    second: int
+    votes: int
+    ref_start: int
+    ref_end: int
+    read_start: int
+    read_end: int
+    alignA: object
+    alignB: object
+    err: int
+
+
+def _strings_short() -> bool:
+    """the last ERR_INVALID was the one about the strings' capacity (everything else was delivered)"""
+    return b"aligned strings need" in _lib.lib().polyhip_last_error()
+
+
+def last_info() -> dict:
+    """polyhip_map_last_info: what the calling thread's last call did"""
+    info = _CInfo()
+    _lib.check(_lib.lib().polyhip_map_last_info(C.byref(info)))
+    return {name: int(getattr(info, name)) for name, _ in _CInfo._fields_}
+
+
+def workspace_bytes(index, scoring, params: MapParams, nreads: int, max_len: int) -> int:
+    p = params._c()
+    return int(_lib.lib().polyhip_map_workspace_bytes(index.handle(), scoring.handle(), C.byref(p), int(nreads), int(max_len)))
+
+
+def map_reads_packed(index, scoring, buf: np.ndarray, offs: np.ndarray, params: MapParams | None = None, strings: bool = True,
+                     capacity: int | None = None, max_len: int | None = None) -> MapResult:
+    """Host-pointer entry point on a packed batch.  ``capacity`` bytes per string buffer (default: 1.25 x the reads' bytes
+    + 64 KB; a batch that needs more is run again with the exact size -- unless ``capacity`` was given, in which case the
+    result carries ``status`` = ERR_INVALID, ``aln_off[-1]`` = the bytes needed, and no strings)."""
+    params = params or MapParams()
+    n = len(offs) - 1
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    if max_len is None:
+        max_len = int(np.diff(offs.astype(np.int64)).max()) if n else 0
+    p = params._c()
+    score, second = np.zeros(n, np.int64), np.zeros(n, np.int64)
+    u32 = [np.zeros(n, np.uint32) for _ in range(7)]
+    off = np.zeros(n + 1, np.uint64)
+    cap = int(capacity) if capacity is not None else int(int(offs[n] - offs[0]) * 1.25) + (64 << 10)
+    alnA = alnB = None
+    rc = _lib.OK
+    for _ in range(2):
+        if strings:
+            alnA, alnB = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.uint8)
+        rc = _lib.lib().polyhip_map_reads(
+            index.handle(), scoring.handle(), C.byref(p), buf.ctypes.data, offs.ctypes.data, n, int(max_len),
+            score.ctypes.data, second.ctypes.data, *[a.ctypes.data for a in u32],
+            alnA.ctypes.data if strings else None, alnB.ctypes.data if strings else None, off.ctypes.data if strings else None, cap)
+        if strings and rc == _lib.ERR_INVALID and _strings_short():  # the strings did not fit: off[n] says what they need
+            if capacity is not None:
+                break
+            cap = int(off[n])
+            continue
+        _lib.check(rc)
+        break
+    sa = sb = None
+    if strings and rc == _lib.OK:
+        o = off.astype(np.int64)
+        sa = [alnA[o[i]:o[i + 1]].tobytes() for i in range(n)]
+        sb = [alnB[o[i]:o[i + 1]].tobytes() for i in range(n)]
+    return MapResult(score, second, *u32, sa, sb, off if strings else None, int(rc))
+
+
+def MapReads(index, scoring, reads, params: MapParams | None = None) -> list:
+    """Every read of a list placed on the index's text -> list of MapRecord"""
+    as_str = bool(reads) and all(isinstance(r, str) for r in reads)
+    buf, offs = _pack(reads)
+    r = map_reads_packed(index, scoring, buf, offs, params)
+    conv = (lambda b: b.decode("latin-1")) if as_str else (lambda b: b)
+    return [MapRecord(bool(r.flags[i] & FLAG_MAPPED), bool(r.flags[i] & FLAG_REVERSE), int(r.score[i]), int(r.second[i]),
+                      int(r.votes[i]), int(r.ref_start[i]), int(r.ref_end[i]), int(r.read_start[i]), int(r.read_end[i]),
+                      conv(r.alignA[i]), conv(r.alignB[i]), int(r.err[i])) for i in range(len(reads))]
+
+
+# ---- device-resident entry point (torch CUDA tensors) ---------------------------------------------------------------------
+def map_reads_dev(index, scoring, reads_t, off_t, max_len: int, params: MapParams, score_t, second_t, flags_t, votes_t,
+                  ref_start_t, ref_end_t, read_start_t, read_end_t, err_t, alnA_t=None, alnB_t=None, alnOff_t=None, work_t=None,
+                  stream=None) -> int:
+    """off_t: uint64-sized (torch.int64) [n + 1]; score / second: torch.int64 [n]; the others uint32-sized (torch.int32)
+    [n]; alnA_t / alnB_t: uint8 of one capacity, alnOff_t [n + 1]; work_t: any size polyhip_map_workspace_bytes allows
+    (allocated if omitted).  Returns the status: OK, or ERR_INVALID when only the strings' capacity was short
+    (alnOff_t[n] = the bytes needed); everything else raises."""
+    import torch
+    n = off_t.numel() - 1
+    if work_t is None:
+        work_t = torch.empty(max(workspace_bytes(index, scoring, params, n, max_len), 1), dtype=torch.uint8, device=off_t.device)
+    p = params._c()
+    strings = alnA_t is not None
+    rc = _lib.lib().polyhip_map_reads_dev(
+        index.handle(), scoring.handle(), C.byref(p), reads_t.data_ptr(), off_t.data_ptr(), n, int(max_len),
+        score_t.data_ptr(), second_t.data_ptr(), flags_t.data_ptr(), votes_t.data_ptr(), ref_start_t.data_ptr(),
+        ref_end_t.data_ptr(), read_start_t.data_ptr(), read_end_t.data_ptr(), err_t.data_ptr(),
+        alnA_t.data_ptr() if strings else None, alnB_t.data_ptr() if strings else None, alnOff_t.data_ptr() if strings else None,
+        alnA_t.numel() if strings else 0, work_t.data_ptr(), work_t.numel() * work_t.element_size(), _lib.stream_ptr(stream))
+    if rc == _lib.ERR_INVALID and strings and _strings_short():
+        return int(rc)
+    _lib.check(rc)
+    return int(rc)
