@@ -184,7 +184,8 @@ int polyhip_mash_shared_counts_reuse_dev(const uint32_t *d_X, uint64_t nx,
  * histogram).  Building parts 0 .. nparts-1 one after the other into ONE workspace, then polyhip_mash_index_finalize_dev,
  * gives the same index as polyhip_mash_index_build_dev (same bucket starts; the same items in every bucket, in whatever
  * order the atomics put them) -- how the parts are tested on one GPU.  polyhip_mash_index_part_spans reports where the
- * parts sit: item_spans / start_spans get nparts + 1 byte offsets into d_work each (part p = [spans[p], spans[p+1])).
+ * parts sit: item_spans / start_spans get nparts + 1 byte offsets into d_work each (part p = [spans[p], spans[p+1])); it
+ * synchronises `stream` as well (the spans are host values computed from the device's histogram and header).
  */
 struct polyhip_comm;
 int polyhip_mash_index_build_part_dev(const uint32_t *d_Y, uint64_t ny, uint32_t sy,
@@ -197,6 +198,11 @@ int polyhip_mash_index_part_spans(uint64_t ny, uint32_t sy, uint32_t nparts,
                                   polyhip_stream_t stream);
 int polyhip_mash_index_finalize_dev(uint64_t ny, uint32_t sy, void *d_work,
                                     size_t work_bytes, polyhip_stream_t stream);
+/* The three read-backs below (polyhip_mash_index_format_dev, polyhip_mash_index_build_info_dev,
+ * polyhip_mash_shared_counts_mode_dev) take no stream: each waits for ALL work outstanding on the current device
+ * (hipDeviceSynchronize) and then copies the workspace's header, so it reports the last build or join enqueued on that
+ * workspace whatever stream it was enqueued on -- a non-blocking one included.  They are diagnostics: keep them out of a
+ * pipeline that must stay asynchronous. */
 /* Bytes per item of the index in d_work (synchronous read-back; tests, profiling, sizing an exchange): 8 = (value, sketch
  * id | occurrence number); 4 = the compact form the build picks ON THE DEVICE when the join to come is the one-stripe dense
  * join (up to ~113k columns of 10-bit counters) and the value's bits below its bucket plus the largest multiplicity of a

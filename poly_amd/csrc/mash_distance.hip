@@ -2546,11 +2546,19 @@ int polyhip_mash_index_part_spans(uint64_t ny, uint32_t sy, uint32_t nparts, con
     return POLYHIP_OK;
 }
 
+// The read-backs below take no stream: they wait for everything the device has outstanding (a build or join enqueued on a
+// non-blocking stream is not ordered before a null-stream copy) and then copy the header words.
+static hipError_t read_header(uint32_t (&h)[k2::H_WORDS], const void *d_work)
+{
+    const hipError_t e = hipDeviceSynchronize();
+    return e != hipSuccess ? e : hipMemcpy(h, d_work, sizeof h, hipMemcpyDeviceToHost);
+}
+
 int polyhip_mash_index_format_dev(const void *d_work, uint32_t *item_bytes)
 {
     PH_REQUIRE(d_work && item_bytes, "polyhip_mash_index_format: null pointer");
     uint32_t h[k2::H_WORDS];
-    PH_HIP(hipMemcpy(h, d_work, sizeof h, hipMemcpyDeviceToHost));
+    PH_HIP(read_header(h, d_work));
     *item_bytes = h[k2::H_FMT] ? 4u : 8u;
     return POLYHIP_OK;
 }
@@ -2559,7 +2567,7 @@ int polyhip_mash_index_build_info_dev(const void *d_work, uint32_t info[6])
 {
     PH_REQUIRE(d_work && info, "polyhip_mash_index_build_info: null pointer");
     uint32_t h[k2::H_WORDS];
-    PH_HIP(hipMemcpy(h, d_work, sizeof h, hipMemcpyDeviceToHost));
+    PH_HIP(read_header(h, d_work));
     info[0] = h[k2::H_B4];
     info[1] = h[k2::H_B4_NC];
     info[2] = h[k2::H_B4_R];
@@ -2611,7 +2619,7 @@ int polyhip_mash_shared_counts_mode_dev(const void *d_work, uint32_t *mode, uint
 {
     PH_REQUIRE(d_work, "polyhip_mash_shared_counts_mode: null workspace");
     uint32_t h[k2::H_WORDS];
-    PH_HIP(hipMemcpy(h, d_work, sizeof h, hipMemcpyDeviceToHost));
+    PH_HIP(read_header(h, d_work));
     if (mode)
         *mode = h[k2::H_MODE];
     if (n_irregular_x)

@@ -110,3 +110,25 @@ def santalucia_scan_dev(seq_t, length: int, start0: int, nstarts: int, minLen: i
     _lib.check(_lib.lib().polyhip_santalucia_scan_dev(
         seq_t.data_ptr(), length, start0, nstarts, minLen, maxLen, primer_conc, salt_conc, mg_conc,
         tm_t.data_ptr(), dH_t.data_ptr(), dS_t.data_ptr(), ld, _lib.stream_ptr(stream)))
+
+
+def santalucia_batch_dev(seqs_t, offsets_t, primer_conc: float, salt_conc: float, mg_conc: float, tm_t, dH_t, dS_t,
+                         stream=None) -> None:
+    """Device-resident batch on torch CUDA tensors (uint8 bytes, int64/uint64 offsets, float64[n] outputs); an empty
+    sequence gets quiet NaNs."""
+    n = offsets_t.numel() - 1
+    assert seqs_t.is_cuda and offsets_t.is_cuda and tm_t.is_cuda and dH_t.is_cuda and dS_t.is_cuda
+    assert offsets_t.element_size() == 8 and seqs_t.element_size() == 1 and tm_t.element_size() == 8
+    assert tm_t.numel() >= n and dH_t.numel() >= n and dS_t.numel() >= n
+    _lib.check(_lib.lib().polyhip_santalucia_batch_dev(
+        seqs_t.data_ptr(), offsets_t.data_ptr(), n, primer_conc, salt_conc, mg_conc,
+        tm_t.data_ptr(), dH_t.data_ptr(), dS_t.data_ptr(), _lib.stream_ptr(stream)))
+
+
+def marmurdoty_batch_dev(seqs_t, offsets_t, tm_t, stream=None) -> None:
+    """Device-resident MarmurDoty on torch CUDA tensors (uint8 bytes, int64/uint64 offsets, float64[n] tm)."""
+    n = offsets_t.numel() - 1
+    assert seqs_t.is_cuda and offsets_t.is_cuda and tm_t.is_cuda
+    assert offsets_t.element_size() == 8 and seqs_t.element_size() == 1 and tm_t.element_size() == 8 and tm_t.numel() >= n
+    _lib.check(_lib.lib().polyhip_marmurdoty_batch_dev(seqs_t.data_ptr(), offsets_t.data_ptr(), n, tm_t.data_ptr(),
+                                                       _lib.stream_ptr(stream)))
