@@ -781,7 +781,8 @@ int polyhip_bwt_extract(const polyhip_bwt *h, const int64_t *start,
  *     unmapped bytes become 0x00).
  *  2. seeds at offsets o = 0, S, 2S, ... while o + L <= m.  A seed's occurrences are all p with T[p, p + L) = q[o, o + L)
  *     (none when it holds '$' or a byte T lacks).  A seed with more than max_occ occurrences contributes nothing and is
- *     counted in the info; every other occurrence is a hit on the diagonal d = p - o (signed).
+ *     counted in the info; every other occurrence is a hit on the diagonal d = p - o (signed).  A max_occ above n means
+ *     no limit (a seed has at most n occurrences; the workspace is sized for min(max_occ, n) hits per seed).
  *  3. clusters, per strand: with the hits sorted by d, a cluster opens at the smallest unassigned diagonal d0 and takes
  *     every hit with d <= d0 + W; votes = its hits, dmax = its largest diagonal.
  *  4. candidates: all clusters of both strands ordered by (votes descending, s ascending, d0 ascending); the first

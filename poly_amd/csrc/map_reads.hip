@@ -476,7 +476,7 @@ MapShape make_shape(const polyhip_map_params *p, uint64_t n, uint32_t max_len)
     MapShape g{};
     g.L = p->seed_len;
     g.S = p->seed_stride;
-    g.max_occ = p->max_occ;
+    g.max_occ = (uint32_t)std::min<uint64_t>(p->max_occ, n); // a seed has at most n occurrences: above n means no limit
     g.W = p->band;
     g.C = p->max_cand;
     g.strands = p->both_strands ? 2 : 1;
