@@ -1397,190 +1397,129 @@ constexpr int DENSE_THREADS = 1024; // one workgroup per CU (its LDS is the whol
 #ifndef PH_K2_DENSE_U
 #define PH_K2_DENSE_U 8
 #endif
-#ifndef PH_K2_PIPE2
-#define PH_K2_PIPE2 0 // 1: two groups of DENSE_U buckets in flight per wave (round 6; measured in profiles/r06_k2_join_pipe.log)
-#endif
 constexpr int DENSE_U = PH_K2_DENSE_U; // buckets a wave loads back to back, 128 items of each
 static_assert(64 % DENSE_U == 0, "a chunk of 64 bucket descriptors (one per lane) is walked DENSE_U at a time by v_readlane: "
                                  "DENSE_U must divide 64 (12 read lanes 64..71 = lanes 0..7 again and counted buckets twice)");
 
-// ---- dense join: a counter per COLUMN in LDS ------------------------------------------------------------
-// Same bucket walk as rowjoin_kernel, but the accumulator is a dense array of BITS-bit counters in LDS, one per
-// column of a stripe (PER = 32 / BITS per dword, bumped with one 32-bit LDS atomic: a count never exceeds the smaller
-// SketchSize < 2^BITS, so the fields cannot carry into each other).  No hash probing, no zero-fill of the
-// output (a stripe is flushed whole, zeros included: the 2 B per pair the matrix costs anyway), and the work
-// follows the shared hashes.  With 10-bit counters (SketchSize <= 1023) the ~138 KB of LDS next to a 1000-hash
-// row hold 105k columns: config 3's 100k sketches are ONE stripe, every bucket is read once per row.
-// Rows: all regular ones (`rows` == NULL), or the rows the sparse join handed over (hdr[H_NOVF] of them).
 // Barrier for LDS traffic only: the wave's LDS operations are complete, nothing is said about its global loads and
-// stores.  rowjoin_dense_kernel shares nothing through global memory inside a workgroup, and __syncthreads() would
+// stores.  The counter joins share nothing through global memory inside a workgroup, and __syncthreads() would
 // also wait for the flush's stores (and any load issued ahead) to complete -- a memory round trip per row.
 __device__ __forceinline__ void lds_barrier()
 {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-// REG (round 4; rows of at most DENSE_THREADS hashes): no LDS staging of the row at all.  Thread t keeps element t of the
+// ---- the bucket walk of the two counter joins (rowjoin_dense_kernel: a matrix, rowjoin_nbr_kernel: lists) -----------
+// A workgroup of DENSE_THREADS takes one row of X at a time and visits the bucket of every distinct value of the row;
+// what happens to an item that matches is the caller's (`consume`).
+// Two rows ahead of the walk: row k + 2's hashes and row k + 1's bucket bounds are loaded while row k's buckets
+// are walked (one hash per thread; sketches above 1024 hashes take the plain loads).  A row costs two dependent
+// memory round trips before its first bucket can be touched -- off the critical path this way.
+struct RowAhead {
+    int64_t i = -1;          // row of X, -1: past the end
+    uint32_t skip = 0;       // not the walk's (an irregular row: the merge's); none of its hashes is loaded
+    uint32_t v = 0;          // my hash of it
+    uint32_t bs = 0, be = 0; // its bucket
+    uint32_t pv = 0, nv = 0; // REG: the hashes in front of and behind mine
+};
+
+// REG (rows of at most DENSE_THREADS hashes): no LDS staging of the row at all.  Thread t keeps element t of the
 // row -- its value, the values on either side, its bucket's bounds, all loaded a row ahead -- and IS the descriptor of that
 // element: "first copy of its value in the row" is a compare with the element in front, the multiplicity is 1 unless the
 // next element is equal (then a short scan of the row in global memory), and a wave walks the buckets of ITS OWN 64
 // consecutive elements by v_readlane (an element that is not a first copy, or whose bucket is empty, is an empty bucket).
-// What goes: the row's copy in LDS, the LDS atomic per distinct value, four descriptor arrays and the three barriers
-// around them -- 5.5 of a row's 24 us at config 3 (profiles/r04_write_bw.md).  POLYHIP_K2_REGROW=0: the staged form.
-template <int BITS, bool COMPACT, bool REG = false>
-__global__ __launch_bounds__(DENSE_THREADS) void rowjoin_dense_kernel(const uint32_t *__restrict__ X, uint64_t nx, uint32_t sx,
-                                                               const uint8_t *__restrict__ flagsX,
-                                                               const uint32_t *__restrict__ start,
-                                                               const void *__restrict__ items_v, uint32_t nbk,
-                                                               const uint32_t *__restrict__ hdr,
-                                                               const uint32_t *__restrict__ rows, uint64_t ny,
-                                                               uint32_t stripe_dwords, uint32_t id_bits,
-                                                               uint16_t *__restrict__ counts, uint64_t ld, int zero_ahead)
-{
-    constexpr uint32_t NWAVES = DENSE_THREADS / 64;
-    if (hdr[H_MODE] != MODE_SPARSE)
-        return;
-    if ((hdr[H_FMT] != 0u) != COMPACT) // the index says which item format it holds; the other instantiation has nothing to do
-        return;
-    constexpr uint32_t PER = 32 / BITS, FMASK = (1u << BITS) - 1u;
+// What goes: the row's copy in LDS, the LDS atomic per distinct value, four descriptor arrays and the barriers
+// around them -- 5.5 of a row's 24 us at config 3 (profiles/r04_write_bw.md).
+// !REG, the staged form (longer rows; POLYHIP_K2_REGROW=0): the row is copied to LDS, its distinct values, their
+// multiplicities and buckets go to four arrays there (5 * sx dwords at `xv`), and wave w owns the distinct values w, w + 16, ...
+template <bool COMPACT, bool REG>
+struct BucketWalk {
     // 8-byte items (value, id | occurrence number) or compact 4-byte ones (H_FMT)
     typedef typename std::conditional<COMPACT, uint32_t, uint2>::type Item;
-    const Item *__restrict__ items = static_cast<const Item *>(items_v);
-    // the counters come FIRST: their LDS address is then the item's own byte offset plus a constant the instruction carries
-    extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
-    uint32_t *dense = dyn, *xv = dyn + stripe_dwords, *dval = xv + sx, *dmul = xv + 2 * (size_t)sx, *dbeg = xv + 3 * (size_t)sx,
-             *dend = xv + 4 * (size_t)sx;
-    __shared__ uint32_t ndist;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t shift = hdr[H_SHIFT], id_mask = (1u << id_bits) - 1u;
-    const uint32_t low_mask = (1u << shift) - 1u, occ_cap = (1u << (11u - (COMPACT ? shift : 0u))) - 1u; // compact: shift <= 10
-    const uint64_t nrows = rows ? hdr[H_NOVF] : nx;
-    const uint32_t stripe_cols = stripe_dwords * PER;
-    const bool one_stripe = ny <= stripe_cols;
-    // Workgroup b runs on XCD b % 8 (round-robin dispatch), each XCD with its own L2.  The rows in flight on one XCD
-    // are CONSECUTIVE ones (gridDim / 8 of them): neighbouring sketches share most of their hashes -- a family's
-    // copies -- so their buckets are fetched into that L2 once, not into all eight.
-    const uint32_t G = gridDim.x, per_xcd = G / 8u;
-    const bool by_xcd = per_xcd != 0 && G % 8u == 0;
-    const uint64_t off = by_xcd ? (uint64_t)(blockIdx.x % 8u) * per_xcd + blockIdx.x / 8u : blockIdx.x;
-    // Two rows ahead of the walk: row k + 2's hashes and row k + 1's bucket bounds are loaded while row k's buckets
-    // are walked (one hash per thread; sketches above 1024 hashes take the plain loads).  A row costs two dependent
-    // memory round trips before its first bucket can be touched -- off the critical path this way.
-    const bool ahead = sx <= (uint32_t)DENSE_THREADS;
-    struct Pre {
-        int64_t i;       // row of X, -1: past the end
-        uint32_t skip;   // irregular row (flagsX): the merge's
-        uint32_t v;      // my hash of it
-        uint32_t bs, be; // its bucket
-        uint32_t pv, nv; // REG: the hashes in front of and behind mine
+    static constexpr uint32_t NWAVES = DENSE_THREADS / 64;
+    struct Desc {
+        uint32_t key = 0, lim = 0, beg = 0, end = 0; // what an item is compared with, the bucket's items; all zero: an empty bucket
     };
-    auto load_row = [&](uint64_t k, Pre &q) {
-        const uint64_t r = k * G + off;
-        q.i = -1;
-        q.skip = 0;
-        q.v = 0;
-        q.pv = q.nv = 0;
-        if (r < nrows) {
-            q.i = (int64_t)(rows ? rows[r] : r);
-            q.skip = rows ? 0u : flagsX[q.i];
-            if (ahead && (uint32_t)tid < sx) {
-                const uint32_t *xp = X + (uint64_t)q.i * sx;
-                q.v = xp[tid];
-                if constexpr (REG) { // (the same cache lines)
-                    q.pv = tid ? xp[tid - 1] : 0u;
-                    q.nv = (uint32_t)tid + 1u < sx ? xp[tid + 1] : 0u;
-                }
+    const uint32_t *X;
+    uint32_t sx;
+    const uint32_t *start;
+    const Item *items;
+    uint32_t nbk, shift, id_bits;
+    uint32_t *xv, *ndist; // the staged form's LDS: the row and four descriptor arrays, the number of descriptors
+    int tid;
+
+    __device__ __forceinline__ bool ahead() const { return sx <= (uint32_t)DENSE_THREADS; }
+
+    // row i of X becomes a row ahead: my hash of it, unless the walk skips the row
+    __device__ __forceinline__ void load_row(RowAhead &q, uint64_t i, uint32_t skip) const
+    {
+        q = RowAhead{};
+        q.i = (int64_t)i;
+        q.skip = skip;
+        if (ahead() && !skip && (uint32_t)tid < sx) {
+            const uint32_t *xp = X + i * sx;
+            q.v = xp[tid];
+            if constexpr (REG) { // (the same cache lines)
+                q.pv = tid ? xp[tid - 1] : 0u;
+                q.nv = (uint32_t)tid + 1u < sx ? xp[tid + 1] : 0u;
             }
         }
-    };
-    auto load_bounds = [&](Pre &q) {
+    }
+    __device__ __forceinline__ void load_bounds(RowAhead &q) const
+    {
         q.bs = q.be = 0;
-        if (ahead && q.i >= 0 && (uint32_t)tid < sx) {
+        if (ahead() && q.i >= 0 && !q.skip && (uint32_t)tid < sx) {
             const uint32_t b = q.v >> shift;
             if (b < nbk) {
                 q.bs = start[b];
                 q.be = start[b + 1];
             }
         }
-    };
-    // the counters start at zero and every flush leaves them so (a thread clears the dwords it has just written out)
-    for (uint32_t t = tid * 4; t < stripe_dwords; t += DENSE_THREADS * 4) // stripe_dwords is a multiple of 8
-        *reinterpret_cast<uint4 *>(dense + t) = make_uint4(0, 0, 0, 0);
-    if constexpr (REG)
-        lds_barrier();
-    // ZERO-AHEAD (round 5; MEASURED, NOT FASTER, opt-in: POLYHIP_K2_ZAHEAD=1).  A row's flush writes all its columns, zeros
-    // included, AFTER its walk, with the memory pipes idle during the walk and the LDS idle during the flush.  In this variant
-    // the zeros of the NEXT row go out during THIS row's walk -- a wave slips two 1 KB stores behind each group of bucket loads
-    // -- and what is left behind the walk is a scan of the LDS counters that writes the row's few hundred non-zero counts over
-    // its zeros and clears them.  Per 12,500 x 100,000 row block (profiles/r05e_join_zero_ahead_ablation.log): whole-row flush
-    // 1.154 ms, zero-ahead 1.179, zero-ahead with NO zeros written at all 0.983 -- so the flush costs 0.17 ms, not the 5.9 of
-    // 24 us per row the round-4 ablation suggested, and vmcnt counts a wave's loads and stores in ONE order: the next group's
-    // wait covers the stores slipped in front of it, and the walk slows by what the flush had cost.  Giving all the stores to
-    // the wave with spare time (a 1000-hash row: wave 15 holds 40 of 64 elements) made that wave the critical path (1.57 ms:
-    // one wave streams ~8 GB/s of such stores).  One stripe, 16-byte aligned rows; anything else keeps the whole-row flush.
-    const bool zahead = zero_ahead != 0 && one_stripe && ld % 8u == 0 && (reinterpret_cast<uintptr_t>(counts) & 15u) == 0;
-    const uint32_t row_bytes = (uint32_t)ny * 2u;                      // (one stripe: ny <= stripe_cols < 2^17)
-    const uint32_t wave_share = (((row_bytes + NWAVES - 1) / NWAVES) + 1023u) & ~1023u; // whole 1 KB wave stores
-    constexpr int per_group = 2;
-    int64_t zeroed = -1;                                               // the row whose zeros have been issued
-    uint8_t *zbase = nullptr;                                          // row being zero-filled by this wave
-    uint32_t zpos = 0, zend = 0;                                       // ... its share [zpos, zend) of the row's bytes
-    typedef uint32_t zvec_t __attribute__((ext_vector_type(4)));
-    auto zero_step = [&](int nstores) __attribute__((always_inline)) {
-        for (int q = 0; q < nstores && zpos < zend; ++q, zpos += 1024u) { // (wave-uniform)
-            const uint32_t at = zpos + (uint32_t)lane * 16u;
-#ifdef PH_K2_ZA_NOSTORE // ablation probe (no zeros written: wrong matrix)
-            if (at == 0xFFFFFFFFu)
-                zbase[0] = 0;
-            continue;
-#endif
-            if (at + 16u <= row_bytes) {
-                __builtin_nontemporal_store(zvec_t{0u, 0u, 0u, 0u}, reinterpret_cast<zvec_t *>(zbase + at));
-            } else if (at < row_bytes) { // the row's last, short piece (ny no multiple of 8)
-                for (uint32_t b = at; b < row_bytes; b += 2)
-                    *reinterpret_cast<uint16_t *>(zbase + b) = 0;
-            }
+    }
+
+    // value v, `a` times in the row, bucket [bs, be), as a descriptor.  8-byte items: lim = multiplicity << id_bits, "occurrence
+    // number < multiplicity" is one compare of the item's whole second word ((0, 0xFFFFFFFF) = no item fails it).  Compact:
+    // key = the value's low bits in the item's top field, + 1 in the occurrence field (items store occurrence + 1), lim =
+    // multiplicity << CK_LOW, capped at what the field numbers: "same value and occurrence number < multiplicity" is ONE
+    // subtract and ONE compare (an item of another value wraps or overshoots; the all-zero word = no item fails too).
+    __device__ __forceinline__ Desc descriptor(uint32_t v, uint32_t a, uint32_t bs, uint32_t be) const
+    {
+        Desc d;
+        if (COMPACT) {
+            const uint32_t low_mask = (1u << shift) - 1u, occ_cap = (1u << (11u - shift)) - 1u; // compact: shift <= 10
+            d.key = (shift ? (v & low_mask) << (32u - shift) : 0u) + (1u << CK_LOW);
+            d.lim = min(a, occ_cap) << CK_LOW;
+        } else {
+            d.key = v;
+            d.lim = a > (0xFFFFFFFFu >> id_bits) ? 0xFFFFFFFFu : a << id_bits;
         }
-    };
-    auto zero_begin = [&](int64_t row, bool) __attribute__((always_inline)) { // this wave's share of `row` becomes its pending zero-fill
-        zbase = reinterpret_cast<uint8_t *>(counts + (uint64_t)row * ld);
-        zpos = min((uint32_t)wave * wave_share, row_bytes);
-        zend = min(zpos + wave_share, row_bytes);
-        zend = zpos + ((zend - zpos + 1023u) & ~1023u); // (the last piece's lanes beyond the row store nothing)
-    };
-    Pre cur, nxt;
-    load_row(0, cur);
-    load_bounds(cur);
-    load_row(1, nxt);
-    for (uint64_t k = 0; cur.i >= 0; ++k) {
+        d.beg = bs;
+        d.end = be;
+        return d;
+    }
+
+    // The row at hand (cur, not skipped) is made ready for walk().  REG: my element as a bucket descriptor (empty unless it
+    // is a first copy).  Staged: the LDS pass, two workgroup barriers; the caller's last barrier behind the walk before
+    // (or behind clearing its counters) stands in front of it.
+    __device__ __forceinline__ Desc describe(const RowAhead &cur) const
+    {
         const uint64_t i = (uint64_t)cur.i;
-        const bool work = !cur.skip; // wave-uniform (irregular rows belong to the merge)
-        uint32_t rval = 0, rlim = 0, rbeg = 0, rend = 0; // REG: my element as a bucket descriptor (empty unless it is a first copy)
         if constexpr (REG) {
-            const bool first = work && (uint32_t)tid < sx && (tid == 0 || cur.pv != cur.v);
-            if (first && cur.be > cur.bs) { // (bounds of a bucket beyond nbk were never loaded: 0, 0)
-                uint32_t a = 1;
-                if ((uint32_t)tid + 1u < sx && cur.nv == cur.v) { // a value the row repeats (rare)
-                    const uint32_t *xp = X + i * sx;
-                    while ((uint32_t)tid + a < sx && xp[tid + a] == cur.v)
-                        ++a;
-                }
-                if (COMPACT) {
-                    rval = (shift ? (cur.v & low_mask) << (32u - shift) : 0u) + (1u << CK_LOW);
-                    rlim = min(a, occ_cap) << CK_LOW;
-                } else {
-                    rval = cur.v;
-                    rlim = a > (0xFFFFFFFFu >> id_bits) ? 0xFFFFFFFFu : a << id_bits;
-                }
-                rbeg = cur.bs;
-                rend = cur.be;
+            const bool first = (uint32_t)tid < sx && (tid == 0 || cur.pv != cur.v);
+            if (!first || cur.be <= cur.bs) // (bounds of a bucket beyond nbk were never loaded: 0, 0)
+                return Desc{};
+            uint32_t a = 1;
+            if ((uint32_t)tid + 1u < sx && cur.nv == cur.v) { // a value the row repeats (rare)
+                const uint32_t *xp = X + i * sx;
+                while ((uint32_t)tid + a < sx && xp[tid + a] == cur.v)
+                    ++a;
             }
-        }
-        if (work && !REG) {
-            lds_barrier();
+            return descriptor(cur.v, a, cur.bs, cur.be);
+        } else {
+            uint32_t *dval = xv + sx, *dmul = xv + 2 * (size_t)sx, *dbeg = xv + 3 * (size_t)sx, *dend = xv + 4 * (size_t)sx;
             if (tid == 0)
-                ndist = 0;
-            if (ahead) {
+                *ndist = 0;
+            if (ahead()) {
                 if ((uint32_t)tid < sx)
                     xv[tid] = cur.v;
             } else {
@@ -1596,42 +1535,189 @@ __global__ __launch_bounds__(DENSE_THREADS) void rowjoin_dense_kernel(const uint
                 const uint32_t b = v >> shift;
                 if (b >= nbk)
                     continue;
-                const uint32_t bs = ahead ? cur.bs : start[b], be = ahead ? cur.be : start[b + 1];
+                const uint32_t bs = ahead() ? cur.bs : start[b], be = ahead() ? cur.be : start[b + 1];
                 if (be == bs)
                     continue;
                 uint32_t a = 1;
                 while (p + a < sx && xv[p + a] == v)
                     ++a;
-                const uint32_t slot = atomicAdd(&ndist, 1u);
+                const uint32_t slot = atomicAdd(ndist, 1u);
                 dval[slot] = v;
                 dmul[slot] = a;
                 dbeg[slot] = bs;
                 dend[slot] = be;
             }
             lds_barrier();
+            return Desc{};
         }
+    }
+
+    // Up to 64 buckets whose descriptors sit in the wave's lanes (lane l: the wave's l-th), `cnt` of them.  The walk takes
+    // them from there by v_readlane -- bucket bounds, key and limit are scalars, no LDS round trip stands between two
+    // buckets.  DENSE_U buckets at a time: the first 128 items of each are loaded back to back (a family's copies of one
+    // hash are one bucket), then consumed.
+    template <class Consume>
+    __device__ __forceinline__ void walk_chunk(const Desc m, const uint32_t cnt, const Consume &consume) const
+    {
+        const uint32_t lane = (uint32_t)tid & 63u;
+        if constexpr (COMPACT) {
+            // Buffer loads: a bucket is its own little buffer (base and size are scalars built on the scalar
+            // unit), every lane reads at the constant offset 4 * lane, and a lane beyond the bucket's end gets 0 =
+            // no item -- no address arithmetic, no bounds compare, no select on the vector unit.
+            // (measured and not kept: ONE 8-byte load per lane -- items 2 l and 2 l + 1 -- instead of two 4-byte
+            // ones, 1.26 against 1.17-1.21 ms per row block.  What the ablations say a row's walk IS
+            // (profiles/r05f_join_ablation.log, r05f_join_flush_ablation.log): the consume and its LDS atomics are free
+            // (1.165 without them, 1.166 with), every bucket read from ONE place in L1 still 0.94, no walk at all 0.57 of
+            // which 0.43 are the flush's STORES at the HBM write rate (5.9 TB/s) and 0.15 everything else; with the walk
+            // the stores cost 0.23: a wave's next loads wait behind its own flush stores -- vmcnt is one queue.)
+            const uint32_t lane4 = lane * 4u;
+            for (uint32_t j0 = 0; j0 < cnt; j0 += DENSE_U) {
+                uint32_t it[DENSE_U][2], len[DENSE_U];
+                __amdgpu_buffer_rsrc_t rs[DENSE_U];
+#pragma unroll
+                for (int u = 0; u < DENSE_U; ++u) {
+                    const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)m.beg, (int)(j0 + u));
+                    len[u] = (uint32_t)__builtin_amdgcn_readlane((int)m.end, (int)(j0 + u)) - b;
+                    rs[u] = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(items + b), 0, (int)(len[u] * 4u), 0x00020000);
+                    it[u][0] = __builtin_amdgcn_raw_buffer_load_b32(rs[u], (int)lane4, 0, 0);
+                    it[u][1] = __builtin_amdgcn_raw_buffer_load_b32(rs[u], (int)lane4, 256, 0);
+                }
+#pragma unroll
+                for (int u = 0; u < DENSE_U; ++u) {
+                    const uint32_t key = (uint32_t)__builtin_amdgcn_readlane((int)m.key, (int)(j0 + u));
+                    const uint32_t lim = (uint32_t)__builtin_amdgcn_readlane((int)m.lim, (int)(j0 + u));
+                    consume(it[u][0], key, lim);
+                    if (len[u] > 64u) { // wave-uniform
+                        consume(it[u][1], key, lim);
+                        for (uint32_t t = 128; t < len[u]; t += 64) // rest of a long bucket
+                            consume(__builtin_amdgcn_raw_buffer_load_b32(rs[u], (int)lane4, (int)(t * 4u), 0), key, lim);
+                    }
+                }
+            }
+        } else {
+            for (uint32_t j0 = 0; j0 < cnt; j0 += DENSE_U) {
+                uint2 it[DENSE_U][2];
+                uint32_t beg[DENSE_U], end[DENSE_U];
+#pragma unroll
+                for (int u = 0; u < DENSE_U; ++u) {
+                    beg[u] = (uint32_t)__builtin_amdgcn_readlane((int)m.beg, (int)(j0 + u));
+                    end[u] = (uint32_t)__builtin_amdgcn_readlane((int)m.end, (int)(j0 + u));
+                    it[u][0] = it[u][1] = make_uint2(0u, 0xFFFFFFFFu);
+                    const uint32_t t = beg[u] + lane;
+                    if (t < end[u])
+                        it[u][0] = items[t];
+                    if (t + 64 < end[u])
+                        it[u][1] = items[t + 64];
+                }
+#pragma unroll
+                for (int u = 0; u < DENSE_U; ++u) {
+                    const uint32_t key = (uint32_t)__builtin_amdgcn_readlane((int)m.key, (int)(j0 + u));
+                    const uint32_t lim = (uint32_t)__builtin_amdgcn_readlane((int)m.lim, (int)(j0 + u));
+                    consume(it[u][0], key, lim);
+                    if (end[u] - beg[u] > 64u) { // wave-uniform
+                        consume(it[u][1], key, lim);
+                        for (uint32_t t = beg[u] + 128 + lane; t < end[u]; t += 64) // rest of a long bucket
+                            consume(items[t], key, lim);
+                    }
+                }
+            }
+        }
+    }
+
+    // every bucket of the row that describe() made ready: consume(item, key, lim) for each of their items
+    template <class Consume>
+    __device__ __forceinline__ void walk(const Desc mine, const Consume &consume) const
+    {
+        const uint32_t lane = (uint32_t)tid & 63u, wave = (uint32_t)tid >> 6;
+        if constexpr (REG) {
+            // my wave's 64 consecutive elements of the row (the last wave of a 1000-hash row: 40)
+            const uint32_t w0 = wave * 64u;
+            if (w0 < sx)
+                walk_chunk(mine, min(64u, sx - w0), consume);
+        } else {
+            const uint32_t *dval = xv + sx, *dmul = xv + 2 * (size_t)sx, *dbeg = xv + 3 * (size_t)sx, *dend = xv + 4 * (size_t)sx;
+            const uint32_t nd = *ndist;
+            for (uint32_t jb = 0; wave + NWAVES * jb < nd; jb += 64) { // one LDS pass per 64 buckets
+                const uint32_t at = wave + NWAVES * (jb + lane);
+                Desc m; // beyond nd: an empty bucket
+                if (at < nd)
+                    m = descriptor(dval[at], dmul[at], dbeg[at], dend[at]);
+                walk_chunk(m, min(64u, (nd - wave - NWAVES * jb + NWAVES - 1) / NWAVES), consume); // my buckets in this chunk
+            }
+        }
+    }
+};
+
+// ---- dense join: a counter per COLUMN in LDS ------------------------------------------------------------
+// Same bucket walk as rowjoin_kernel, but the accumulator is a dense array of BITS-bit counters in LDS, one per
+// column of a stripe (PER = 32 / BITS per dword, bumped with one 32-bit LDS atomic: a count never exceeds the smaller
+// SketchSize < 2^BITS, so the fields cannot carry into each other).  No hash probing, no zero-fill of the
+// output (a stripe is flushed whole, zeros included: the 2 B per pair the matrix costs anyway), and the work
+// follows the shared hashes.  With 10-bit counters (SketchSize <= 1023) the ~138 KB of LDS next to a 1000-hash
+// row hold 105k columns: config 3's 100k sketches are ONE stripe, every bucket is read once per row.
+// Rows: all regular ones (`rows` == NULL), or the rows the sparse join handed over (hdr[H_NOVF] of them).
+template <int BITS, bool COMPACT, bool REG = false>
+__global__ __launch_bounds__(DENSE_THREADS) void rowjoin_dense_kernel(const uint32_t *__restrict__ X, uint64_t nx, uint32_t sx,
+                                                               const uint8_t *__restrict__ flagsX,
+                                                               const uint32_t *__restrict__ start,
+                                                               const void *__restrict__ items_v, uint32_t nbk,
+                                                               const uint32_t *__restrict__ hdr,
+                                                               const uint32_t *__restrict__ rows, uint64_t ny,
+                                                               uint32_t stripe_dwords, uint32_t id_bits,
+                                                               uint16_t *__restrict__ counts, uint64_t ld)
+{
+    if (hdr[H_MODE] != MODE_SPARSE)
+        return;
+    if ((hdr[H_FMT] != 0u) != COMPACT) // the index says which item format it holds; the other instantiation has nothing to do
+        return;
+    constexpr uint32_t PER = 32 / BITS, FMASK = (1u << BITS) - 1u;
+    typedef BucketWalk<COMPACT, REG> Walk;
+    // the counters come FIRST: their LDS address is then the item's own byte offset plus a constant the instruction carries
+    extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
+    uint32_t *dense = dyn;
+    __shared__ uint32_t ndist;
+    const int tid = threadIdx.x;
+    const uint32_t id_mask = (1u << id_bits) - 1u;
+    const Walk walk{X, sx, start, static_cast<const typename Walk::Item *>(items_v), nbk, hdr[H_SHIFT], id_bits, dyn + stripe_dwords, &ndist, tid};
+    const uint64_t nrows = rows ? hdr[H_NOVF] : nx;
+    const uint32_t stripe_cols = stripe_dwords * PER;
+    const bool one_stripe = ny <= stripe_cols;
+    // Workgroup b runs on XCD b % 8 (round-robin dispatch), each XCD with its own L2.  The rows in flight on one XCD
+    // are CONSECUTIVE ones (gridDim / 8 of them): neighbouring sketches share most of their hashes -- a family's
+    // copies -- so their buckets are fetched into that L2 once, not into all eight.
+    const uint32_t G = gridDim.x, per_xcd = G / 8u;
+    const bool by_xcd = per_xcd != 0 && G % 8u == 0;
+    const uint64_t off = by_xcd ? (uint64_t)(blockIdx.x % 8u) * per_xcd + blockIdx.x / 8u : blockIdx.x;
+    auto load_row = [&](uint64_t k, RowAhead &q) { // my k-th row: of the list, or of X without the irregular ones (the merge's)
+        const uint64_t r = k * G + off;
+        q = RowAhead{};
+        if (r < nrows) {
+            const uint64_t i = rows ? rows[r] : r;
+            walk.load_row(q, i, rows ? 0u : flagsX[i]);
+        }
+    };
+    // the counters start at zero and every flush leaves them so (a thread clears the dwords it has just written out)
+    for (uint32_t t = tid * 4; t < stripe_dwords; t += DENSE_THREADS * 4) // stripe_dwords is a multiple of 8
+        *reinterpret_cast<uint4 *>(dense + t) = make_uint4(0, 0, 0, 0);
+    lds_barrier();
+    RowAhead cur, nxt;
+    load_row(0, cur);
+    walk.load_bounds(cur);
+    load_row(1, nxt);
+    for (uint64_t k = 0; cur.i >= 0; ++k) {
+        const uint64_t i = (uint64_t)cur.i;
+        const bool work = !cur.skip; // wave-uniform (irregular rows belong to the merge)
+        typename Walk::Desc desc;
+        if (work)
+            desc = walk.describe(cur);
         // issue the loads of the rows ahead now: they land while this row's buckets are walked
-        Pre nn;
-        load_bounds(nxt);
+        RowAhead nn;
+        walk.load_bounds(nxt);
         load_row(k + 2, nn);
         cur = nxt;
         nxt = nn;
         if (!work)
             continue;
-        if (zahead) {
-            if (zeroed != (int64_t)i) { // the workgroup's first row, or the row behind one the merge took: its zeros now, in the open
-                zero_begin((int64_t)i, true);
-                zero_step(1 << 20);
-            }
-            zeroed = -1;
-            zpos = zend = 0;
-            if (cur.i >= 0 && !cur.skip) { // (cur is the NEXT row by now)
-                zero_begin(cur.i, false);
-                zeroed = cur.i;
-            }
-        }
-        const uint32_t nd = REG ? 0u : ndist;
-        (void)nd;
         for (uint64_t c0 = 0; c0 < ny; c0 += stripe_cols) {
             const uint32_t ncols = (uint32_t)min((uint64_t)stripe_cols, ny - c0);
             // column c of the stripe = field c / ndw of dword c % ndw: neighbouring columns (a bucket is a family's
@@ -1641,268 +1727,24 @@ __global__ __launch_bounds__(DENSE_THREADS) void rowjoin_dense_kernel(const uint
             // k = col / ndw by one multiply-high: kmul = ceil(2^32 / ndw) is exact for col < PER * ndw while PER * ndw^2 < 2^32
             // (the host caps the stripe accordingly)
             const uint32_t kmul = (uint32_t)(((1ull << 32) + ndw - 1) / ndw);
-            auto consume_wide = [&](const uint2 it, uint32_t v, uint32_t alim) {
-                // alim = multiplicity << id_bits: "occurrence number < multiplicity" is one compare of the whole word
-                // ((0, 0xFFFFFFFF) = no item fails it)
-                if (it.x != v || it.y >= alim)
-                    return;
-                uint32_t col = it.y & id_mask;
-                if (!one_stripe) {
-                    if (col < c0 || col - c0 >= ncols)
-                        return;
-                    col -= (uint32_t)c0;
-                }
-                const uint32_t k = __umulhi(col, kmul);
-                atomicAdd(&dense[col - k * ndw], 1u << (BITS * k));
-            };
-            // compact: key = the row value's low bits in the item's top field, alim = multiplicity << CK_LOW; "same value
-            // and occurrence number < multiplicity" is ONE subtract and ONE compare (an item of another value wraps or
-            // overshoots; the all-zero word = no item fails too), the counter's byte offset and field shift are in the item
-            auto consume_compact = [&](const uint32_t it, uint32_t key, uint32_t alim) {
-#if defined(PH_K2_J_NOCONSUME) // ablation probes (wrong counts): the walk without its consume / without its LDS atomics
-                if (it == 0x12345u && key == 77u)
-                    dense[0] = alim;
-#elif defined(PH_K2_J_NOATOM)
-                if (it - key < alim && it == 0x12345u)
-                    dense[0] = alim;
-#else
-                if (it - key < alim)
-                    atomicAdd(reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(dense) + ((it >> 3) & 0x3FFFCu)), 1u << (it & 31u));
-#endif
-            };
-            // Wave w owns the distinct values w, w + 16, w + 32, ...: lane l keeps the descriptor of the wave's l-th one
-            // in registers (one LDS pass per 64 buckets) and the walk takes them from there by v_readlane -- bucket
-            // bounds, value and multiplicity are scalars, no LDS round trip stands between two buckets.  DENSE_U
-            // buckets at a time: the first 128 items of each are loaded back to back (a family's copies of one hash are
-            // one bucket), then consumed.
-            constexpr uint32_t NW = DENSE_THREADS / 64;
-            // up to 64 buckets whose descriptors sit in the wave's lanes
-            auto walk_chunk = [&](const uint32_t mval, const uint32_t mlim, const uint32_t mbeg, const uint32_t mend,
-                                  const uint32_t cnt) __attribute__((always_inline)) {
-                if constexpr (COMPACT) {
-                    // Buffer loads: a bucket is its own little buffer (base and size are scalars built on the scalar
-                    // unit), every lane reads at the constant offset 4 * lane, and a lane beyond the bucket's end gets 0 =
-                    // no item -- no address arithmetic, no bounds compare, no select on the vector unit.
-                    // (round 5, measured and not kept: ONE 8-byte load per lane -- items 2 l and 2 l + 1 -- instead of two 4-byte
-                    // ones, 1.26 against 1.17-1.21 ms per row block.  What the ablations say a row's walk IS
-                    // (profiles/r05f_join_ablation.log, r05f_join_flush_ablation.log): the consume and its LDS atomics are free
-                    // (1.165 without them, 1.166 with), every bucket read from ONE place in L1 still 0.94, no walk at all 0.57 of
-                    // which 0.43 are the flush's STORES at the HBM write rate (5.9 TB/s) and 0.15 everything else; with the walk
-                    // the stores cost 0.23: a wave's next loads wait behind its own flush stores -- vmcnt is one queue.)
-                    const uint32_t lane4 = (uint32_t)lane * 4u;
-#if PH_K2_PIPE2
-                    // (round 6) two groups of DENSE_U buckets in flight: group g + 1's loads are issued BEFORE group g's items
-                    // are consumed (vmcnt counts in order: the wait in front of a group's consume leaves the younger group's
-                    // loads outstanding), so a wave's eight dependent load-wait-consume rounds per row become one wait plus
-                    // seven that overlap the consume in front of them
-                    {
-                        uint32_t itA[DENSE_U][2], lenA[DENSE_U], itB[DENSE_U][2], lenB[DENSE_U];
-                        __amdgpu_buffer_rsrc_t rsA[DENSE_U], rsB[DENSE_U];
-                        auto issue = [&](uint32_t j0, uint32_t (&it)[DENSE_U][2], uint32_t (&len)[DENSE_U],
-                                         __amdgpu_buffer_rsrc_t (&rs)[DENSE_U]) __attribute__((always_inline)) {
-#pragma unroll
-                            for (int u = 0; u < DENSE_U; ++u) {
-                                const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)mbeg, (int)(j0 + u));
-                                len[u] = (uint32_t)__builtin_amdgcn_readlane((int)mend, (int)(j0 + u)) - b;
-                                rs[u] = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(items + b), 0, (int)(len[u] * 4u), 0x00020000);
-                                it[u][0] = __builtin_amdgcn_raw_buffer_load_b32(rs[u], (int)lane4, 0, 0);
-                                it[u][1] = __builtin_amdgcn_raw_buffer_load_b32(rs[u], (int)lane4, 256, 0);
-                            }
-                        };
-                        auto eat = [&](uint32_t j0, uint32_t (&it)[DENSE_U][2], uint32_t (&len)[DENSE_U],
-                                       __amdgpu_buffer_rsrc_t (&rs)[DENSE_U]) __attribute__((always_inline)) {
-#pragma unroll
-                            for (int u = 0; u < DENSE_U; ++u) {
-                                const uint32_t key = (uint32_t)__builtin_amdgcn_readlane((int)mval, (int)(j0 + u));
-                                const uint32_t alim = (uint32_t)__builtin_amdgcn_readlane((int)mlim, (int)(j0 + u));
-                                consume_compact(it[u][0], key, alim);
-                                if (len[u] > 64u) { // wave-uniform
-                                    consume_compact(it[u][1], key, alim);
-                                    for (uint32_t t = 128; t < len[u]; t += 64) // rest of a long bucket
-                                        consume_compact(__builtin_amdgcn_raw_buffer_load_b32(rs[u], (int)lane4, (int)(t * 4u), 0), key, alim);
-                                }
-                            }
-                        };
-                        if (cnt)
-                            issue(0, itA, lenA, rsA);
-                        for (uint32_t j0 = 0; j0 < cnt; j0 += 2 * DENSE_U) {
-                            const bool second = j0 + DENSE_U < cnt;
-                            if (second)
-                                issue(j0 + DENSE_U, itB, lenB, rsB);
-                            zero_step(per_group);
-                            eat(j0, itA, lenA, rsA);
-                            if (second) {
-                                if (j0 + 2 * DENSE_U < cnt)
-                                    issue(j0 + 2 * DENSE_U, itA, lenA, rsA);
-                                zero_step(per_group);
-                                eat(j0 + DENSE_U, itB, lenB, rsB);
-                            }
-                        }
-                    }
-#elif defined(PH_K2_J_X4A) || defined(PH_K2_J_X2A)
-                    // PROBES (round 6; counts may be wrong: a foreign item in front of the bucket can pass the key test): ONE wide
-                    // load per bucket from the bucket's start rounded DOWN to 16 (8) bytes -- is the walk bound by the number of
-                    // vector-memory instructions (2000 dword loads per row through one CU's address unit)?
-                    {
-#ifdef PH_K2_J_X4A
-                        constexpr uint32_t W = 4;
-#else
-                        constexpr uint32_t W = 2;
-#endif
-                        const uint32_t laneW = (uint32_t)lane * 4u * W;
-                        for (uint32_t j0 = 0; j0 < cnt; j0 += DENSE_U) {
-                            uint32_t it[DENSE_U][W], len[DENSE_U];
-                            __amdgpu_buffer_rsrc_t rs[DENSE_U];
-#pragma unroll
-                            for (int u = 0; u < DENSE_U; ++u) {
-                                const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)mbeg, (int)(j0 + u));
-                                const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)mend, (int)(j0 + u));
-                                const uint32_t ba = b & ~(W - 1u);
-                                len[u] = e - ba;
-                                rs[u] = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(items + ba), 0, (int)(len[u] * 4u), 0x00020000);
-                                if constexpr (W == 4) {
-                                    const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs[u], (int)laneW, 0, 0);
-                                    it[u][0] = v[0], it[u][1] = v[1], it[u][2] = v[2], it[u][3] = v[3];
-                                } else {
-                                    const auto v = __builtin_amdgcn_raw_buffer_load_b64(rs[u], (int)laneW, 0, 0);
-                                    it[u][0] = v[0], it[u][1] = v[1];
-                                }
-                            }
-#pragma unroll
-                            for (int u = 0; u < DENSE_U; ++u) {
-                                const uint32_t key = (uint32_t)__builtin_amdgcn_readlane((int)mval, (int)(j0 + u));
-                                const uint32_t alim = (uint32_t)__builtin_amdgcn_readlane((int)mlim, (int)(j0 + u));
-#pragma unroll
-                                for (uint32_t w = 0; w < W; ++w)
-                                    consume_compact(it[u][w], key, alim);
-                                for (uint32_t t = 64u * W; t < len[u]; t += 64) // rest of a long bucket
-                                    consume_compact(__builtin_amdgcn_raw_buffer_load_b32(rs[u], (int)(lane * 4u), (int)(t * 4u), 0), key, alim);
-                            }
-                        }
-                    }
-#else
-                    for (uint32_t j0 = 0; j0 < cnt; j0 += DENSE_U) {
-                        uint32_t it[DENSE_U][2], len[DENSE_U];
-                        __amdgpu_buffer_rsrc_t rs[DENSE_U];
-#pragma unroll
-                        for (int u = 0; u < DENSE_U; ++u) {
-                            const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)mbeg, (int)(j0 + u));
-                            len[u] = (uint32_t)__builtin_amdgcn_readlane((int)mend, (int)(j0 + u)) - b;
-#ifdef PH_K2_J_L1 // ablation probe (wrong counts): every bucket's items from ONE place (L1 hits)
-                            rs[u] = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(items), 0, (int)(len[u] * 4u), 0x00020000);
-#else
-                            rs[u] = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(items + b), 0, (int)(len[u] * 4u), 0x00020000);
-#endif
-                            it[u][0] = __builtin_amdgcn_raw_buffer_load_b32(rs[u], (int)lane4, 0, 0);
-                            it[u][1] = __builtin_amdgcn_raw_buffer_load_b32(rs[u], (int)lane4, 256, 0);
-                        }
-                        zero_step(per_group); // (zero-ahead variant: the next row's zeros ride behind this group's loads)
-#pragma unroll
-                        for (int u = 0; u < DENSE_U; ++u) {
-                            const uint32_t key = (uint32_t)__builtin_amdgcn_readlane((int)mval, (int)(j0 + u));
-                            const uint32_t alim = (uint32_t)__builtin_amdgcn_readlane((int)mlim, (int)(j0 + u));
-                            consume_compact(it[u][0], key, alim);
-                            if (len[u] > 64u) { // wave-uniform
-                                consume_compact(it[u][1], key, alim);
-                                for (uint32_t t = 128; t < len[u]; t += 64) // rest of a long bucket
-                                    consume_compact(__builtin_amdgcn_raw_buffer_load_b32(rs[u], (int)lane4, (int)(t * 4u), 0), key, alim);
-                            }
-                        }
-                    }
-#endif
+            auto consume = [&](const typename Walk::Item it, uint32_t key, uint32_t lim) {
+                if constexpr (COMPACT) { // the counter's byte offset and field shift are in the item
+                    if (it - key < lim)
+                        atomicAdd(reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(dense) + ((it >> 3) & 0x3FFFCu)), 1u << (it & 31u));
                 } else {
-                    for (uint32_t j0 = 0; j0 < cnt; j0 += DENSE_U) {
-                        uint2 it[DENSE_U][2];
-                        uint32_t beg[DENSE_U], end[DENSE_U];
-#pragma unroll
-                        for (int u = 0; u < DENSE_U; ++u) {
-                            beg[u] = (uint32_t)__builtin_amdgcn_readlane((int)mbeg, (int)(j0 + u));
-                            end[u] = (uint32_t)__builtin_amdgcn_readlane((int)mend, (int)(j0 + u));
-                            it[u][0] = it[u][1] = make_uint2(0u, 0xFFFFFFFFu);
-                            const uint32_t t = beg[u] + lane;
-                            if (t < end[u])
-                                it[u][0] = items[t];
-                            if (t + 64 < end[u])
-                                it[u][1] = items[t + 64];
-                        }
-                        zero_step(per_group);
-#pragma unroll
-                        for (int u = 0; u < DENSE_U; ++u) {
-                            const uint32_t v = (uint32_t)__builtin_amdgcn_readlane((int)mval, (int)(j0 + u));
-                            const uint32_t alim = (uint32_t)__builtin_amdgcn_readlane((int)mlim, (int)(j0 + u));
-                            consume_wide(it[u][0], v, alim);
-                            if (end[u] - beg[u] > 64u) { // wave-uniform
-                                consume_wide(it[u][1], v, alim);
-                                for (uint32_t t = beg[u] + 128 + lane; t < end[u]; t += 64) // rest of a long bucket
-                                    consume_wide(items[t], v, alim);
-                            }
-                        }
+                    if (it.x != key || it.y >= lim)
+                        return;
+                    uint32_t col = it.y & id_mask;
+                    if (!one_stripe) {
+                        if (col < c0 || col - c0 >= ncols)
+                            return;
+                        col -= (uint32_t)c0;
                     }
+                    const uint32_t f = __umulhi(col, kmul);
+                    atomicAdd(&dense[col - f * ndw], 1u << (BITS * f));
                 }
             };
-            if constexpr (REG) {
-                // my wave's 64 consecutive elements of the row (the last wave of a 1000-hash row: 40)
-                const uint32_t w0 = (uint32_t)wave * 64u;
-#ifndef PH_K2_NOWALK
-                if (w0 < sx)
-                    walk_chunk(rval, rlim, rbeg, rend, min(64u, sx - w0));
-#endif
-            } else {
-#ifdef PH_K2_NOWALK // ablation probe (wrong counts): how long is a row without its bucket walk?
-                for (uint32_t jb = 0; false && wave + NW * jb < nd; jb += 64) {
-#else
-                for (uint32_t jb = 0; wave + NW * jb < nd; jb += 64) {
-#endif
-                    const uint32_t mine = wave + NW * (jb + lane);
-                    uint32_t mval = 0, mlim = 0, mbeg = 0, mend = 0; // beyond nd: an empty bucket
-                    if (mine < nd) {
-                        const uint32_t a = dmul[mine];
-                        mval = dval[mine];
-                        if (COMPACT) {
-                            // key = the value's low bits in the item's top field, + 1 in the occurrence field (items store
-                            // occurrence + 1); multiplicity capped at what the field numbers
-                            mval = (shift ? (mval & low_mask) << (32u - shift) : 0u) + (1u << CK_LOW);
-                            mlim = min(a, occ_cap) << CK_LOW;
-                        } else {
-                            mlim = a > (0xFFFFFFFFu >> id_bits) ? 0xFFFFFFFFu : a << id_bits;
-                        }
-                        mbeg = dbeg[mine];
-                        mend = dend[mine];
-                    }
-                    walk_chunk(mval, mlim, mbeg, mend, min(64u, (nd - wave - NW * jb + NW - 1) / NW)); // my buckets in this chunk
-                }
-            }
-            if (zahead) {
-                zero_step(1 << 20); // what the walk's groups did not carry (a wave with few buckets, a short row)
-                // every zero of the next row (and, a row ago, of this one) is in L2 before anybody patches over it
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                // the row's non-zero counts over its zeros; the counters go back to zero where they were touched
-                uint16_t *prow = counts + i * ld;
-#ifdef PH_K2_NOFLUSH
-                for (uint32_t t = tid * 8; false && t < ndw; t += DENSE_THREADS * 8) {
-#else
-                for (uint32_t t = tid * 8; t < ndw; t += DENSE_THREADS * 8) {
-#endif
-                    const uint4 d0 = *reinterpret_cast<const uint4 *>(dense + t);
-                    const uint4 d1 = *reinterpret_cast<const uint4 *>(dense + t + 4);
-                    if ((d0.x | d0.y | d0.z | d0.w | d1.x | d1.y | d1.z | d1.w) == 0u)
-                        continue;
-                    const uint32_t d[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
-#pragma unroll
-                    for (int q = 0; q < 8; ++q)
-                        if (d[q]) {
-                            dense[t + q] = 0;
-#pragma unroll
-                            for (uint32_t kf = 0; kf < PER; ++kf) {
-                                const uint32_t f = (d[q] >> (BITS * kf)) & FMASK, col = kf * ndw + t + (uint32_t)q;
-                                if (f && col < ncols)
-                                    prow[col] = (uint16_t)f;
-                            }
-                        }
-                }
-                lds_barrier();
-                continue;
-            }
+            walk.walk(desc, consume);
             lds_barrier();
             // flush the stripe whole, zeros included: field k of dwords [0, ndw) = columns [k * ndw, (k + 1) * ndw)
             uint16_t *crow = counts + i * ld + c0;
@@ -1912,19 +1754,11 @@ __global__ __launch_bounds__(DENSE_THREADS) void rowjoin_dense_kernel(const uint
                 // counter dwords once, clears them, and sends each of their PER fields to its own run of eight columns
                 // (field k = columns [k * ndw, (k + 1) * ndw), k * ndw a multiple of 8: all stores 16-byte aligned)
                 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-#ifdef PH_K2_NOFLUSH // ablation probe (nothing written): how long is a row without its flush?
-                for (uint32_t t = tid * 8; false && t < ndw; t += DENSE_THREADS * 8) {
-#else
                 for (uint32_t t = tid * 8; t < ndw; t += DENSE_THREADS * 8) {
-#endif
-#ifdef PH_K2_F_NOLDS // ablation probe: the flush without its LDS traffic (stores what the thread index says)
-                    const uint4 d0 = make_uint4(t, t, t, t), d1 = d0;
-#else
                     const uint4 d0 = *reinterpret_cast<const uint4 *>(dense + t);
                     const uint4 d1 = *reinterpret_cast<const uint4 *>(dense + t + 4);
                     *reinterpret_cast<uint4 *>(dense + t) = make_uint4(0, 0, 0, 0);
                     *reinterpret_cast<uint4 *>(dense + t + 4) = make_uint4(0, 0, 0, 0);
-#endif
                     const uint32_t d[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
 #pragma unroll
                     for (uint32_t k = 0; k < PER; ++k) {
@@ -1938,14 +1772,7 @@ __global__ __launch_bounds__(DENSE_THREADS) void rowjoin_dense_kernel(const uint
                         if (cb + t + 8 <= ncols) {
                             // written once, never read here: nontemporal, so the 2 B per pair do not push the index out of L2
                             const u32x4_t o = {f[0] | (f[1] << 16), f[2] | (f[3] << 16), f[4] | (f[5] << 16), f[6] | (f[7] << 16)};
-#ifdef PH_K2_F_NOSTORE // ablation probe: the flush without its global stores
-                            if (o.x == 0x12345u)
-#endif
-#ifdef PH_K2_F_PLAIN // measured: ordinary (temporal) stores instead of nontemporal ones
-                            *reinterpret_cast<u32x4_t *>(crow + cb + t) = o;
-#else
                             __builtin_nontemporal_store(o, reinterpret_cast<u32x4_t *>(crow + cb + t));
-#endif
                         } else {
 #pragma unroll
                             for (int q = 0; q < 8; ++q)
@@ -1967,31 +1794,7 @@ __global__ __launch_bounds__(DENSE_THREADS) void rowjoin_dense_kernel(const uint
                 // every pass: no barrier needed in between)
                 const bool last = cb + ndw >= ncols;
                 const uint32_t lim = last ? ndw : n;
-                if (al == 0) { // eight columns per 16-byte store (kept for reference: aligned rows take the single pass above)
-                    for (uint32_t t = tid * 8; t < lim; t += DENSE_THREADS * 8) {
-                        const uint4 d0 = *reinterpret_cast<const uint4 *>(dense + t);
-                        const uint4 d1 = *reinterpret_cast<const uint4 *>(dense + t + 4);
-                        if (last) {
-                            *reinterpret_cast<uint4 *>(dense + t) = make_uint4(0, 0, 0, 0);
-                            *reinterpret_cast<uint4 *>(dense + t + 4) = make_uint4(0, 0, 0, 0);
-                        }
-                        uint32_t f[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
-#pragma unroll
-                        for (int q = 0; q < 8; ++q)
-                            f[q] = (f[q] >> (BITS * k)) & FMASK;
-                        if (t + 8 <= n) {
-                            // written once, never read here: nontemporal, so the 2 B per pair do not push the index out of L2
-                            typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-                            const u32x4_t o = {f[0] | (f[1] << 16), f[2] | (f[3] << 16), f[4] | (f[5] << 16), f[6] | (f[7] << 16)};
-                            __builtin_nontemporal_store(o, reinterpret_cast<u32x4_t *>(crow + cb + t));
-                        } else {
-#pragma unroll
-                            for (int q = 0; q < 8; ++q)
-                                if (t + q < n)
-                                    crow[cb + t + q] = (uint16_t)f[q];
-                        }
-                    }
-                } else if ((al & 7u) == 0) { // four columns per 8-byte store
+                if ((al & 7u) == 0) { // four columns per 8-byte store
                     for (uint32_t t = tid * 4; t < lim; t += DENSE_THREADS * 4) {
                         const uint4 d = *reinterpret_cast<const uint4 *>(dense + t);
                         if (last)
@@ -2252,6 +2055,22 @@ static DenseGeom dense_geom(uint32_t sx, uint32_t sy, uint64_t ny)
     return g;
 }
 
+// bits of a Y sketch id among ny; the rest of an item's second dword numbers the copies of a value
+static uint32_t id_bits_of(uint64_t ny)
+{
+    uint32_t id_bits = 1;
+    while ((1ull << id_bits) < ny && id_bits < k2::ID_BITS_MAX)
+        ++id_bits;
+    return id_bits;
+}
+
+// rows of at most 1024 hashes: a thread per element, no staging of the row (BucketWalk's REG; POLYHIP_K2_REGROW=0: the
+// staged form, a testing aid)
+static bool reg_rows(uint32_t sx)
+{
+    return sx <= (uint32_t)k2::DENSE_THREADS && !env_is("POLYHIP_K2_REGROW", '0');
+}
+
 // what: 1 = build the index of Y, 2 = join X against the index in the workspace, 3 = both
 static int shared_counts_impl(int what, const uint32_t *d_X, uint64_t nx, uint32_t sx, const uint32_t *d_Y, uint64_t ny,
                               uint32_t sy, uint16_t *d_counts, uint64_t ld, void *d_work, size_t work_bytes,
@@ -2293,11 +2112,8 @@ static int shared_counts_impl(int what, const uint32_t *d_X, uint64_t nx, uint32
     uint2 *duplist = reinterpret_cast<uint2 *>(w + L.off_duplist);
 
     // the join packs the Y sketch id into 24 bits and stages an X row in LDS
-    const int force = (ny > (1ull << k2::ID_BITS_MAX) || sx > k2::S_MAX) ? 1 : 0;
-    (void)stripe_sketches;
-    uint32_t id_bits = 1; // bits of a Y sketch id; the rest of an item's second dword numbers the copies of a value
-    while ((1ull << id_bits) < ny && id_bits < k2::ID_BITS_MAX)
-        ++id_bits;
+    const int force = dense_geom(sx, sy, ny).force ? 1 : 0;
+    const uint32_t id_bits = id_bits_of(ny);
     const uint32_t max_occ = (1u << (32 - id_bits)) - 2u; // all-ones stays free (the join's "no item" marker)
 
     // Item format.  An index built on its own assumes that the X sets to come have Y's SketchSize (an all-vs-all, a
@@ -2430,15 +2246,13 @@ static int shared_counts_impl(int what, const uint32_t *d_X, uint64_t nx, uint32
     auto launch_dense = [&](const uint32_t *rows, unsigned blocks) -> int {
         const uint32_t sdw = (uint32_t)std::min<uint64_t>(stripe_dwords, (((ny + per - 1) / per) + 7) & ~7ull);
         const size_t smem = row_bytes + (size_t)sdw * 4;
-        // rows of at most 1024 hashes: a thread per element, no staging of the row (REG; POLYHIP_K2_REGROW=0: the staged form)
-        const bool regrow = sx <= (uint32_t)k2::DENSE_THREADS && !env_is("POLYHIP_K2_REGROW", '0');
+        const bool regrow = reg_rows(sx);
 #define PH_K2_DENSE_LAUNCH(BITS_, COMPACT_)                                                                                   \
     do {                                                                                                                      \
         auto kern = regrow ? k2::rowjoin_dense_kernel<BITS_, COMPACT_, true> : k2::rowjoin_dense_kernel<BITS_, COMPACT_, false>; \
         PH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
         hipLaunchKernelGGL(kern, dim3(blocks), dim3(k2::DENSE_THREADS), smem, st, d_X, nx, sx, flagsX, start,                 \
-                           static_cast<const void *>(items), L.nbk, hdr, rows, ny, sdw, id_bits, d_counts, ld,                \
-                           env_is("POLYHIP_K2_ZAHEAD", '1') ? 1 : 0);                                                         \
+                           static_cast<const void *>(items), L.nbk, hdr, rows, ny, sdw, id_bits, d_counts, ld);               \
     } while (0)
         // both item formats are launched when the index MAY be compact: the device decided (H_FMT), the instantiation
         // that does not match returns at once
@@ -2825,9 +2639,7 @@ int polyhip::k2_exchange_index(md::Pool &P, std::vector<K2XShard> &sh, uint64_t 
     if (gY.force || !gY.dense_all)
         return POLYHIP_OK;
     const bool allow_compact = gY.compact_ok;
-    uint32_t id_bits = 1;
-    while ((1ull << id_bits) < n && id_bits < k2::ID_BITS_MAX)
-        ++id_bits;
+    const uint32_t id_bits = id_bits_of(n);
     const uint32_t max_occ = (1u << (32 - id_bits)) - 2u;
     const bool staged = s <= k2::STAGE_ITEMS && L.nc <= 1024 && !env_is("POLYHIP_K2_STAGE", '0');
     struct View { // one device's workspace

@@ -5,8 +5,8 @@
 //
 //   blocks    Y is processed in column blocks of at most one dense stripe (about 105k columns at SketchSize <= 1023); the
 //             existing index is built per block, in the same workspace, and all rows of X are joined against it
-//   join      rowjoin_nbr_kernel: rowjoin_dense_kernel's walk (descriptors a row ahead, DENSE_U buckets per wave, one LDS
-//             atomic per item, 10- or 16-bit counters), then a flush that COMPACTS: the counter dwords are read, tested
+//   join      rowjoin_nbr_kernel: the walk rowjoin_dense_kernel uses (BucketWalk: descriptors a row ahead, DENSE_U buckets per
+//             wave; one LDS atomic per item, 10- or 16-bit counters), then a flush that COMPACTS: the counter dwords are read, tested
 //             against min_shared and the self column, and the survivors -- (column, shared), ascending column -- go to a
 //             segment of a temporary list that the row reserves with one atomic; the counters are cleared in the same pass.
 //             An irregular row (flagsX) fills the same counters from the reference's merge, a regular row adds its irregular
@@ -38,228 +38,63 @@ __global__ __launch_bounds__(DENSE_THREADS) void rowjoin_nbr_kernel(
         return;
     constexpr uint32_t PER = 32 / BITS, FMASK = (1u << BITS) - 1u;
     static_assert(PER <= NBR_PER_MAX && PER * NWAVES <= 64, "the flush scans PER * NWAVES wave totals in one wave");
-    typedef typename std::conditional<COMPACT, uint32_t, uint2>::type Item;
-    const Item *__restrict__ items = static_cast<const Item *>(items_v);
+    typedef BucketWalk<COMPACT, REG> Walk;
     extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
-    uint32_t *dense = dyn, *xv = dyn + ndw, *dval = xv + sx, *dmul = xv + 2 * (size_t)sx, *dbeg = xv + 3 * (size_t)sx,
-             *dend = xv + 4 * (size_t)sx; // (REG: no row stage behind the counters)
+    uint32_t *dense = dyn; // (REG: no row stage behind the counters)
     __shared__ uint32_t ndist;
     __shared__ uint32_t wcnt[NBR_PER_MAX * NWAVES];
     __shared__ unsigned long long rowpos;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t shift = hdr[H_SHIFT], id_mask = (1u << id_bits) - 1u;
-    const uint32_t low_mask = (1u << shift) - 1u, occ_cap = (1u << (11u - (COMPACT ? shift : 0u))) - 1u;
+    const uint32_t id_mask = (1u << id_bits) - 1u;
+    const Walk walk{X, sx, start, static_cast<const typename Walk::Item *>(items_v), nbk, hdr[H_SHIFT], id_bits, dyn + ndw, &ndist, tid};
     const uint32_t nirr = hdr[H_NIRRY];
     // consecutive rows on one XCD, as in rowjoin_dense_kernel
     const uint32_t G = gridDim.x, per_xcd = G / 8u;
     const bool by_xcd = per_xcd != 0 && G % 8u == 0;
     const uint64_t off = by_xcd ? (uint64_t)(blockIdx.x % 8u) * per_xcd + blockIdx.x / 8u : blockIdx.x;
-    const bool ahead = sx <= (uint32_t)DENSE_THREADS;
     // column c = field c / ndw of dword c % ndw (what a compact item has worked out already)
     const uint32_t kmul = (uint32_t)(((1ull << 32) + ndw - 1) / ndw);
     auto bump = [&](uint32_t col, uint32_t by) {
         const uint32_t k = __umulhi(col, kmul);
         atomicAdd(&dense[col - k * ndw], by << (BITS * k));
     };
-    struct Pre {
-        int64_t i;       // row of X, -1: past the end
-        uint32_t skip;   // irregular row (flagsX): the merge's
-        uint32_t v;      // my hash of it
-        uint32_t bs, be; // its bucket
-        uint32_t pv, nv; // REG: the hashes in front of and behind mine
+    auto consume = [&](const typename Walk::Item it, uint32_t key, uint32_t lim) {
+        if constexpr (COMPACT) {
+            if (it - key < lim)
+                atomicAdd(reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(dense) + ((it >> 3) & 0x3FFFCu)), 1u << (it & 31u));
+        } else {
+            if (it.x == key && it.y < lim)
+                bump(it.y & id_mask, 1u);
+        }
     };
-    auto load_row = [&](uint64_t k, Pre &q) {
+    auto load_row = [&](uint64_t k, RowAhead &q) { // my k-th row of X; an irregular one (or every one) is the merge's
         const uint64_t r = k * G + off;
-        q.i = -1;
-        q.skip = 0;
-        q.v = 0;
-        q.pv = q.nv = 0;
-        if (r < nx) {
-            q.i = (int64_t)r;
-            q.skip = merge_all ? 1u : flagsX[r];
-            if (ahead && !q.skip && (uint32_t)tid < sx) {
-                const uint32_t *xp = X + r * sx;
-                q.v = xp[tid];
-                if constexpr (REG) {
-                    q.pv = tid ? xp[tid - 1] : 0u;
-                    q.nv = (uint32_t)tid + 1u < sx ? xp[tid + 1] : 0u;
-                }
-            }
-        }
-    };
-    auto load_bounds = [&](Pre &q) {
-        q.bs = q.be = 0;
-        if (ahead && q.i >= 0 && !q.skip && (uint32_t)tid < sx) {
-            const uint32_t b = q.v >> shift;
-            if (b < nbk) {
-                q.bs = start[b];
-                q.be = start[b + 1];
-            }
-        }
+        q = RowAhead{};
+        if (r < nx)
+            walk.load_row(q, r, merge_all ? 1u : flagsX[r]);
     };
     // the counters start at zero and every flush leaves them so
     for (uint32_t t = tid * 4; t < ndw; t += DENSE_THREADS * 4) // ndw is a multiple of 8
         *reinterpret_cast<uint4 *>(dense + t) = make_uint4(0, 0, 0, 0);
     lds_barrier();
-    Pre cur, nxt;
+    RowAhead cur, nxt;
     load_row(0, cur);
-    load_bounds(cur);
+    walk.load_bounds(cur);
     load_row(1, nxt);
     for (uint64_t k = 0; cur.i >= 0; ++k) {
         const uint64_t i = (uint64_t)cur.i;
         const bool work = !cur.skip; // wave-uniform
-        uint32_t rval = 0, rlim = 0, rbeg = 0, rend = 0; // REG: my element as a bucket descriptor (empty unless it is a first copy)
-        if constexpr (REG) {
-            const bool first = work && (uint32_t)tid < sx && (tid == 0 || cur.pv != cur.v);
-            if (first && cur.be > cur.bs) {
-                uint32_t a = 1;
-                if ((uint32_t)tid + 1u < sx && cur.nv == cur.v) { // a value the row repeats (rare)
-                    const uint32_t *xp = X + i * sx;
-                    while ((uint32_t)tid + a < sx && xp[tid + a] == cur.v)
-                        ++a;
-                }
-                if (COMPACT) {
-                    rval = (shift ? (cur.v & low_mask) << (32u - shift) : 0u) + (1u << CK_LOW);
-                    rlim = min(a, occ_cap) << CK_LOW;
-                } else {
-                    rval = cur.v;
-                    rlim = a > (0xFFFFFFFFu >> id_bits) ? 0xFFFFFFFFu : a << id_bits;
-                }
-                rbeg = cur.bs;
-                rend = cur.be;
-            }
-        }
-        if (work && !REG) {
-            if (tid == 0)
-                ndist = 0;
-            if (ahead) {
-                if ((uint32_t)tid < sx)
-                    xv[tid] = cur.v;
-            } else {
-                const uint32_t *xp = X + i * sx;
-                for (uint32_t p = tid; p < sx; p += DENSE_THREADS)
-                    xv[p] = xp[p];
-            }
-            lds_barrier();
-            for (uint32_t p = tid; p < sx; p += DENSE_THREADS) { // distinct values of the row and their buckets
-                const uint32_t v = xv[p];
-                if (p != 0 && xv[p - 1] == v)
-                    continue;
-                const uint32_t b = v >> shift;
-                if (b >= nbk)
-                    continue;
-                const uint32_t bs = ahead ? cur.bs : start[b], be = ahead ? cur.be : start[b + 1];
-                if (be == bs)
-                    continue;
-                uint32_t a = 1;
-                while (p + a < sx && xv[p + a] == v)
-                    ++a;
-                const uint32_t slot = atomicAdd(&ndist, 1u);
-                dval[slot] = v;
-                dmul[slot] = a;
-                dbeg[slot] = bs;
-                dend[slot] = be;
-            }
-            lds_barrier();
-        }
+        typename Walk::Desc desc;
+        if (work)
+            desc = walk.describe(cur);
         // issue the loads of the rows ahead now: they land while this row's buckets are walked
-        Pre nn;
-        load_bounds(nxt);
+        RowAhead nn;
+        walk.load_bounds(nxt);
         load_row(k + 2, nn);
         cur = nxt;
         nxt = nn;
         if (work) {
-            const uint32_t nd = REG ? 0u : ndist;
-            (void)nd;
-            auto consume_wide = [&](const uint2 it, uint32_t v, uint32_t alim) {
-                if (it.x != v || it.y >= alim)
-                    return;
-                bump(it.y & id_mask, 1u);
-            };
-            auto consume_compact = [&](const uint32_t it, uint32_t key, uint32_t alim) {
-                if (it - key < alim)
-                    atomicAdd(reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(dense) + ((it >> 3) & 0x3FFFCu)), 1u << (it & 31u));
-            };
-            // up to 64 buckets whose descriptors sit in the wave's lanes (rowjoin_dense_kernel's walk_chunk)
-            auto walk_chunk = [&](const uint32_t mval, const uint32_t mlim, const uint32_t mbeg, const uint32_t mend,
-                                  const uint32_t cnt) __attribute__((always_inline)) {
-                if constexpr (COMPACT) {
-                    const uint32_t lane4 = (uint32_t)lane * 4u;
-                    for (uint32_t j0 = 0; j0 < cnt; j0 += DENSE_U) {
-                        uint32_t it[DENSE_U][2], len[DENSE_U];
-                        __amdgpu_buffer_rsrc_t rs[DENSE_U];
-#pragma unroll
-                        for (int u = 0; u < DENSE_U; ++u) {
-                            const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)mbeg, (int)(j0 + u));
-                            len[u] = (uint32_t)__builtin_amdgcn_readlane((int)mend, (int)(j0 + u)) - b;
-                            rs[u] = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(items + b), 0, (int)(len[u] * 4u), 0x00020000);
-                            it[u][0] = __builtin_amdgcn_raw_buffer_load_b32(rs[u], (int)lane4, 0, 0);
-                            it[u][1] = __builtin_amdgcn_raw_buffer_load_b32(rs[u], (int)lane4, 256, 0);
-                        }
-#pragma unroll
-                        for (int u = 0; u < DENSE_U; ++u) {
-                            const uint32_t key = (uint32_t)__builtin_amdgcn_readlane((int)mval, (int)(j0 + u));
-                            const uint32_t alim = (uint32_t)__builtin_amdgcn_readlane((int)mlim, (int)(j0 + u));
-                            consume_compact(it[u][0], key, alim);
-                            if (len[u] > 64u) { // wave-uniform
-                                consume_compact(it[u][1], key, alim);
-                                for (uint32_t t = 128; t < len[u]; t += 64) // rest of a long bucket
-                                    consume_compact(__builtin_amdgcn_raw_buffer_load_b32(rs[u], (int)lane4, (int)(t * 4u), 0), key, alim);
-                            }
-                        }
-                    }
-                } else {
-                    for (uint32_t j0 = 0; j0 < cnt; j0 += DENSE_U) {
-                        uint2 it[DENSE_U][2];
-                        uint32_t beg[DENSE_U], end[DENSE_U];
-#pragma unroll
-                        for (int u = 0; u < DENSE_U; ++u) {
-                            beg[u] = (uint32_t)__builtin_amdgcn_readlane((int)mbeg, (int)(j0 + u));
-                            end[u] = (uint32_t)__builtin_amdgcn_readlane((int)mend, (int)(j0 + u));
-                            it[u][0] = it[u][1] = make_uint2(0u, 0xFFFFFFFFu);
-                            const uint32_t t = beg[u] + lane;
-                            if (t < end[u])
-                                it[u][0] = items[t];
-                            if (t + 64 < end[u])
-                                it[u][1] = items[t + 64];
-                        }
-#pragma unroll
-                        for (int u = 0; u < DENSE_U; ++u) {
-                            const uint32_t v = (uint32_t)__builtin_amdgcn_readlane((int)mval, (int)(j0 + u));
-                            const uint32_t alim = (uint32_t)__builtin_amdgcn_readlane((int)mlim, (int)(j0 + u));
-                            consume_wide(it[u][0], v, alim);
-                            if (end[u] - beg[u] > 64u) { // wave-uniform
-                                consume_wide(it[u][1], v, alim);
-                                for (uint32_t t = beg[u] + 128 + lane; t < end[u]; t += 64) // rest of a long bucket
-                                    consume_wide(items[t], v, alim);
-                            }
-                        }
-                    }
-                }
-            };
-            if constexpr (REG) {
-                const uint32_t w0 = (uint32_t)wave * 64u;
-                if (w0 < sx)
-                    walk_chunk(rval, rlim, rbeg, rend, min(64u, sx - w0));
-            } else {
-                for (uint32_t jb = 0; wave + NWAVES * jb < nd; jb += 64) {
-                    const uint32_t mine = wave + NWAVES * (jb + lane);
-                    uint32_t mval = 0, mlim = 0, mbeg = 0, mend = 0; // beyond nd: an empty bucket
-                    if (mine < nd) {
-                        const uint32_t a = dmul[mine];
-                        mval = dval[mine];
-                        if (COMPACT) {
-                            mval = (shift ? (mval & low_mask) << (32u - shift) : 0u) + (1u << CK_LOW);
-                            mlim = min(a, occ_cap) << CK_LOW;
-                        } else {
-                            mlim = a > (0xFFFFFFFFu >> id_bits) ? 0xFFFFFFFFu : a << id_bits;
-                        }
-                        mbeg = dbeg[mine];
-                        mend = dend[mine];
-                    }
-                    walk_chunk(mval, mlim, mbeg, mend, min(64u, (nd - wave - NWAVES * jb + NWAVES - 1) / NWAVES));
-                }
-            }
+            walk.walk(desc, consume);
             // the row's irregular columns never entered the index: the reference's merge, into the same counters
             for (uint32_t q = tid; q < nirr; q += DENSE_THREADS) {
                 const uint32_t j = irrY[q];
@@ -520,7 +355,7 @@ static k2::NbrGeom nbr_geom(uint32_t sx, uint32_t sy)
     k2::NbrGeom g;
     g.bits = sy <= 1023u ? 10 : 16;
     g.per = 32u / (uint32_t)g.bits;
-    g.reg = sx <= (uint32_t)k2::DENSE_THREADS;
+    g.reg = reg_rows(sx);
     const size_t lds_max = 160 * 1024 - 1024, stage = g.reg ? 0 : (size_t)5 * sx * 4;
     g.merge_all = stage + 32 * 1024 > lds_max;
     g.row_bytes = g.merge_all ? 0 : stage;
@@ -617,9 +452,7 @@ static int nbr_rows(NbrCall &c, uint64_t r0, uint64_t nr, uint64_t *out_base)
             c.block_in_index = (int64_t)b;
             ++c.info.index_builds;
         }
-        uint32_t id_bits = 1;
-        while ((1ull << id_bits) < m && id_bits < ID_BITS_MAX)
-            ++id_bits;
+        const uint32_t id_bits = id_bits_of(m);
         const uint32_t ndw = (uint32_t)((((m + c.g.per - 1) / c.g.per) + 7) & ~7ull);
         const size_t smem = (size_t)ndw * 4 + c.g.row_bytes;
         // the build makes compact items for dense_geom(sy, sy, m) alone: where that rules them out only the 8-byte

@@ -14,8 +14,8 @@ nrows = N // 8
 X = sk[:nrows]
 counts = torch.full((nrows, N), -1, dtype=torch.int16, device=dev)
 work = torch.empty(mash.shared_counts_workspace_bytes(nrows, s, N, s), dtype=torch.uint8, device=dev)
-KEYS = ("POLYHIP_K2_B4", "POLYHIP_K2_B4_SLOTS", "POLYHIP_K2_B4_TL", "POLYHIP_K2_ZAHEAD")
-variants = [("two-level", {"POLYHIP_K2_B4": "0"}), ("b4 default", {}), ("b4, zero-ahead join", {"POLYHIP_K2_ZAHEAD": "1"})]
+KEYS = ("POLYHIP_K2_B4", "POLYHIP_K2_B4_SLOTS", "POLYHIP_K2_B4_TL")
+variants = [("two-level", {"POLYHIP_K2_B4": "0"}), ("b4 default", {})]
 if len(sys.argv) > 1 and sys.argv[1] == "sweep":
     variants += [(f"b4 slots128 tl{t}", {"POLYHIP_K2_B4_SLOTS": "128", "POLYHIP_K2_B4_TL": str(t)}) for t in (72, 83, 92)]
     variants += [(f"b4 slots64 tl{t}", {"POLYHIP_K2_B4_SLOTS": "64", "POLYHIP_K2_B4_TL": str(t)}) for t in (36, 41, 46)]

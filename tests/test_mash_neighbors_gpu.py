@@ -5,6 +5,7 @@ and its distance kernel are not the code under test)."""
 import numpy as np
 import pytest
 
+import k2_walk_shapes
 import oracle as orc
 import mash_neighbors_oracle as nbo
 
@@ -25,9 +26,27 @@ def dev():
     return torch.device("cuda:0")
 
 
+WALKS = ("default", "staged", "wide", "staged-wide")
+
+
+@pytest.fixture
+def walk(request, monkeypatch):
+    """the join's walk in one of its forms: a row of at most 1024 hashes in registers or staged in LDS
+    (POLYHIP_K2_REGROW=0), compact 4-byte items where they fit or 8-byte ones (POLYHIP_K2_COMPACT=0).  A test that does
+    not parametrise it (indirect) runs the default form, with both variables unset."""
+    form = getattr(request, "param", "default")
+    monkeypatch.delenv("POLYHIP_K2_REGROW", raising=False)
+    monkeypatch.delenv("POLYHIP_K2_COMPACT", raising=False)
+    if "staged" in form:
+        monkeypatch.setenv("POLYHIP_K2_REGROW", "0")
+    if "wide" in form:
+        monkeypatch.setenv("POLYHIP_K2_COMPACT", "0")
+    return form
+
+
 def _t(a, dev):
     import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.uint32).view(np.int32)).to(dev)
+    return torch.from_numpy(np.array(a, np.uint32, order="C").view(np.int32)).to(dev)  # (a copy: shared inputs are read-only)
 
 
 def run_dev(mash, dev, X, Y, min_shared=1, k=0, exclude_self=False, self_offset=0, capacity=None, want_dist=True, Xt=None,
@@ -138,7 +157,7 @@ def _families(rng, nfam, copies, L, sub, k, s):
 
 
 @pytest.mark.parametrize("s,nfam,copies,L", [(200, 6, 8, 1500), (1000, 4, 6, 4000), (2000, 3, 5, 6000)])
-def test_families_threshold_and_topk(mash, dev, s, nfam, copies, L):
+def test_families_threshold_and_topk(mash, dev, walk, s, nfam, copies, L):
     """10-bit counters (s = 200, 1000) and 16-bit ones (s = 2000; rows beyond 1024 hashes are staged in LDS)"""
     rng = np.random.default_rng(s)
     S = _families(rng, nfam, copies, L, 0.01, 21, s)
@@ -151,6 +170,13 @@ def test_families_threshold_and_topk(mash, dev, s, nfam, copies, L):
         check_all(mash, dev, S, S, f"s={s} k={k} no self", oracle_counts=M, k=k, exclude_self=True, min_shared=2)
     info = mash.neighbors_last_info()
     assert info["column_blocks"] == 1 and info["assembly"] == 1 and info["row_chunks"] == 1
+
+
+@pytest.mark.parametrize("walk", WALKS[1:], indirect=True)
+@pytest.mark.parametrize("s,nfam,copies,L", [(200, 6, 8, 1500), (1000, 4, 6, 4000), (2000, 3, 5, 6000)])
+def test_families_threshold_and_topk_in_the_other_walk_forms(mash, dev, walk, s, nfam, copies, L):
+    """the test above (the default walk) with the row staged, with 8-byte items, and with both: the same assertions"""
+    test_families_threshold_and_topk(mash, dev, walk, s, nfam, copies, L)
 
 
 def test_forced_ties_in_topk(mash, dev):
@@ -173,7 +199,7 @@ def test_forced_ties_in_topk(mash, dev):
     check_all(mash, dev, X, Y, "ties k=3 no self", oracle_counts=M, k=3, exclude_self=True, self_offset=3)  # row 1 is column 4
 
 
-def test_different_sketch_sizes_and_duplicates(mash, dev):
+def test_different_sketch_sizes_and_duplicates(mash, dev, walk):
     rng = np.random.default_rng(5)
     X = np.sort(rng.integers(0, 40, (30, 64), dtype=np.uint32), axis=1)  # heavy duplication: multiset semantics
     Y = np.sort(rng.integers(0, 40, (25, 48), dtype=np.uint32), axis=1)
@@ -193,6 +219,21 @@ def test_different_sketch_sizes_and_duplicates(mash, dev):
     D = np.concatenate([S, S, S[:1], S])
     got = check_all(mash, dev, D, D, "duplicated sketches", exclude_self=True, min_shared=200)
     assert (np.diff(got[0].astype(np.int64)) >= 2).all()
+
+
+@pytest.mark.parametrize("walk", WALKS[1:], indirect=True)
+def test_different_sketch_sizes_and_duplicates_in_the_other_walk_forms(mash, dev, walk):
+    """the test above (the default walk) with the row staged, with 8-byte items, and with both: the same assertions"""
+    test_different_sketch_sizes_and_duplicates(mash, dev, walk)
+
+
+@pytest.mark.parametrize("walk", WALKS, indirect=True)
+@pytest.mark.parametrize("sx", k2_walk_shapes.ROW_LENGTHS)
+def test_walk_shapes(mash, dev, walk, sx):
+    """the bucket walk at its edges (tests/k2_walk_shapes.py), as lists: every non-zero cell, and the 3 best per row"""
+    X, Y, M = k2_walk_shapes.case(sx)
+    check_all(mash, dev, X, Y, f"walk shapes sx={sx} {walk}", oracle_counts=M, min_shared=1)
+    check_all(mash, dev, X, Y, f"walk shapes sx={sx} {walk} k=3", oracle_counts=M, k=3)
 
 
 def test_exclude_self_in_a_row_block(mash, dev):
