@@ -481,6 +481,8 @@ int polyhip_sw_align_batch_packed(const polyhip_scoring *sc, const uint8_t *A,
  * Strings: last d_alnLen[p] bytes of the aln_stride-byte slots, aln_stride >=
  * max_lenA + lenB.  Workspace: polyhip_nw_workspace_bytes (whole direction matrix
  * per pair; the call loops over chunks of pairs if given less, >= 256 pairs' worth).
+ * Range: |gap| and |scores| such that  max|score| * (max_lenA + lenB) < 2^31; beyond
+ * that the call is refused with POLYHIP_ERR_UNSUPPORTED.
  */
 size_t polyhip_nw_workspace_bytes(uint64_t npairs, uint32_t max_lenA,
                                   uint64_t max_lenB);
@@ -536,8 +538,8 @@ int polyhip_sw_traceback_last_path(void);
  * (every H < 2048) for reads of <= 152 symbols while the table of halves fits twice into a CU's LDS.
  * POLYHIP_TB_F16=0 keeps the 32-bit form (testing aid). */
 int polyhip_sw_traceback_last_half(void);
-/* ... and the last polyhip_nw_align_batch_dev call: 1 = register-tiled kernel (lenA <= 256), 2 = generic kernel
- * (POLYHIP_NW_GENERIC=1 forces it), 3 = one-wave-per-pair kernel (lenA 257..4096); tests. */
+/* ... and the last polyhip_nw_align_batch_dev call: 1 = register-tiled kernel (lenA <= 64), 2 = generic kernel
+ * (POLYHIP_NW_GENERIC=1 forces it), 3 = one-wave-per-pair kernel (lenA 65..4096); tests. */
 int polyhip_nw_last_path(void);
 
 /* ---- K4: primers SantaLucia / MarmurDoty / MeltingTemp  (primers/primers.go:70-128) */

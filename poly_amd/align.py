@@ -150,7 +150,8 @@ def sw_traceback_last_half() -> bool:
 
 
 def nw_last_path() -> int:
-    """1 = register-tiled NeedlemanWunsch kernel, 2 = generic (tests)"""
+    """1 = register-tiled NeedlemanWunsch kernel (longest A <= 64), 2 = generic (longer than 4096, a table that does not
+    fit LDS, an empty side, POLYHIP_NW_GENERIC=1), 3 = one wave per pair with 2..64 rows per lane (65..4096); tests"""
     return int(_lib.lib().polyhip_nw_last_path())
 
 

@@ -2148,7 +2148,7 @@ __global__ __launch_bounds__(THREADS) void nw_kernel(const uint8_t *__restrict__
     alnLen[pair] = len;
 }
 
-// ---- NeedlemanWunsch, register-tiled (lenA <= 256, compact table in LDS) -------------------------
+// ---- NeedlemanWunsch, register-tiled (lenA <= 64, compact table in LDS) --------------------------
 // Same cell and bit recording as tb_prof_kernel minus the zero: d = diag + s, t = max(up, left) + gap,
 // h = max(d, t), G = t > d (the diagonal wins ties, align.go:146), L = left > up ("up" is tested before the
 // final else, :150-158); boundary column H[i][0] = i*gap in the registers, boundary row carried in `top`.
@@ -2302,7 +2302,7 @@ __global__ __launch_bounds__(THREADS) void nw_reg_kernel(const uint8_t *__restri
     alnLen[pair] = len;
 }
 
-// ---- NeedlemanWunsch for 256 < lenA <= 4096: one wave per pair (same sweep as tb_wave_kernel) ----------
+// ---- NeedlemanWunsch for 64 < lenA <= 4096: one wave per pair, nw_wave_r rows per lane (same sweep as tb_wave_kernel) ----
 // Boundaries H[i][0] = i*gap (the lanes' initial registers), H[0][j] = j*gap (fed to lane 0); the whole matrix's
 // G / L bits are kept (no window in a global alignment); the walk stops when either index reaches 0 (align.go:141).
 

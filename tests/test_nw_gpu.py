@@ -51,9 +51,8 @@ def test_TestNeedlemanWunsch(al):
 @pytest.mark.parametrize("maxlen,generic", [(60, False), (150, False), (150, True), (250, False), (300, False), (300, True),
                                             (700, False), (1500, False), (3000, False), (4500, False)])
 def test_batch_matches_oracle(al, monkeypatch, maxlen, generic):
-    """ragged batches against the oracle: the register-tiled kernel (lenA <= 64 / 152 / 256 rows), the
-    one-wave-per-pair kernel (257..4096) and the generic one (longer A, or POLYHIP_NW_GENERIC=1); invalid symbols;
-    per-pair and shared B"""
+    """ragged batches against the oracle: the register-tiled kernel (lenA <= 64 rows), the one-wave-per-pair kernel
+    (65..4096) and the generic one (longer A, or POLYHIP_NW_GENERIC=1); invalid symbols; per-pair and shared B"""
     if generic:
         monkeypatch.setenv("POLYHIP_NW_GENERIC", "1")
     rng = np.random.default_rng(5)
