@@ -62,11 +62,9 @@
 #define PH_SEL_ATOMIC 0 // EXPERIMENT (round 6): 1 = a survivor's slot from a returning LDS increment on the wave's own counter
 #endif                  // (compare + shift per hash) instead of its ballot rank (compare + two mbcnt + shift-add)
 #ifndef PH_BS_WIN
-#define PH_BS_WIN 4 // the fast bottom-s ranks an element against its PH_BS_WIN neighbours on either side (0: against its whole bin)
+#define PH_BS_WIN 4 // the fast bottom-s ranks an element against its 4 neighbours on either side (0: against its whole bin)
 #endif
-#ifndef PH_BS_U
-#define PH_BS_U 4 // candidates a thread takes per trip of the bottom-s's loops (bottom_s_fast): 4 / 5 / 6 measure the same
-#endif
+static_assert(PH_BS_WIN == 0 || PH_BS_WIN == 4, "the rank pass takes four slots per thread: its window is four");
 // slab pass (scripts/ubench/k1_ablate.hip sweeps these): sigmas of head-room of the survivor target over s, of a
 // wave's segment and of the sorted buffer over their expectations, and the waves per SIMD it is allocated for
 #ifndef PH_SLAB_SIG
@@ -98,6 +96,7 @@ constexpr int NB = 2048;  // counting-sort bins
 // out[0] = 0xFFFFFFFF > out[1] = 0, which no sketch of a read with >= s windows can be (those are ascending) -- and the
 // general kernel, which scans the batch for marks, redoes it.  No side list: the _dev entry point needs no scratch.
 constexpr uint32_t MARK0 = 0xFFFFFFFFu, MARK1 = 0u;
+constexpr uint32_t LUT_DW = 256; // dwords of the tail-byte table; in the slab kernel it is the first thing in LDS and the span follows it
 constexpr int GBATCH = 32; // reads a general-kernel workgroup scans at a time
 constexpr uint32_t WL_POSITIONAL = 0x80000000u; // work-list flag of the general kernel: fewer windows than SketchSize
 constexpr uint32_t C1 = 0xcc9e2d51u, C2 = 0x1b873593u;
@@ -550,8 +549,14 @@ __device__ __forceinline__ void append4(uint32_t *__restrict__ counter, uint32_t
 // `src` / `first` / `step` / `cnt`: where this thread's candidates are -- the shared buffer (sm.cand, tid, THREADS, C)
 // or, for the slab pass, the thread's own wave's segment (segment, lane, 64, that wave's count).  FIN: the
 // candidates still lack fmix32's last `h ^= h >> 16` (the slab pass thresholds on the bits that step leaves alone).
-constexpr int BSU = PH_BS_U;
+// (Round 5 found 4, 5 and 6 candidates per trip of the LOOPED passes to measure the same, profiles/r05_k1_bottom_s_unroll.log:
+// each guarded load and each returning add of those loops waits for itself whatever the unroll, so that says nothing about
+// the register form below, which took the loops' place for up to BS_R candidates.)
+constexpr int BSU = 4;   // candidates a thread takes per trip of the looped count and scatter passes
+constexpr int BS_R = 7;  // trips the register form of those passes covers (7 x 64 = the slab pass's segment at s = 1000) ...
+constexpr int BS_R0 = 5; // ... the first BS_R0 of them in one block without a branch (87 % of the waves at s = 1000)
 constexpr uint32_t BS_MARGIN = (PH_BS_WIN + 3u) & ~3u; // dwords kept free before binned[0] and behind binned[capf)
+static_assert(BS_MARGIN % 4u == 0 && LUT_DW % 4u == 0, "the rank pass reads binned by 16 bytes: binned[0] is 16-byte aligned");
 // (PH_ABL 21: the fast bottom-s without its workgroup barriers -- wrong results, timing only: the upper bound of what
 // overlapping one read's bottom-s with the next read's hashing could give)
 #define BS_SYNC()              \
@@ -559,16 +564,63 @@ constexpr uint32_t BS_MARGIN = (PH_BS_WIN + 3u) & ~3u; // dwords kept free befor
         if (PH_ABL != 21)      \
             __syncthreads();   \
     } while (0)
+typedef __attribute__((address_space(3))) uint32_t lds_u32;
+__device__ __forceinline__ uint32_t lds_addr(const uint32_t *p)
+{
+    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint32_t *)p;
+}
+// ds_write_b32 of value c by the lanes in mask[c] alone, c = 0..3, with no branch: hipcc guards each `if (a) store`
+// with a saveexec and a skip branch (four per slab, and out of line).  Only for code that runs with all 64 lanes
+// active, where exec = mask is exec & mask; a store under an empty mask writes nothing.
+__device__ __forceinline__ void lds_store4_masked(const uint32_t (&addr)[4], const uint32_t (&v)[4], const uint64_t (&mask)[4])
+{
+    uint64_t saved;
+    asm volatile("s_mov_b64 %0, exec\n\t"
+                 "s_mov_b64 exec, %9\n\t"
+                 "ds_write_b32 %1, %5\n\t"
+                 "s_mov_b64 exec, %10\n\t"
+                 "ds_write_b32 %2, %6\n\t"
+                 "s_mov_b64 exec, %11\n\t"
+                 "ds_write_b32 %3, %7\n\t"
+                 "s_mov_b64 exec, %12\n\t"
+                 "ds_write_b32 %4, %8\n\t"
+                 "s_mov_b64 exec, %0"
+                 : "=&s"(saved)
+                 : "v"(addr[0]), "v"(addr[1]), "v"(addr[2]), "v"(addr[3]), "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]),
+                   "s"(mask[0]), "s"(mask[1]), "s"(mask[2]), "s"(mask[3])
+                 : "memory");
+}
+// The same for one store (the bottom-s's scatter): a form of its own because the four-store form saves and restores exec
+// once for all four, which the slab loop, where it is issued per slab, should keep.
+__device__ __forceinline__ void lds_store_masked(uint32_t addr, uint32_t v, uint64_t mask)
+{
+    uint64_t saved;
+    asm volatile("s_mov_b64 %0, exec\n\t"
+                 "s_mov_b64 exec, %3\n\t"
+                 "ds_write_b32 %1, %2\n\t"
+                 "s_mov_b64 exec, %0"
+                 : "=&s"(saved)
+                 : "v"(addr), "v"(v), "s"(mask)
+                 : "memory");
+}
+
 // The bins are 16-BIT counters, two per dword (bin b in half b & 1 of dword b >> 1, i.e. element b of a uint16_t view):
 // there is no 16-bit LDS atomic, so a count adds 1 << 16 * (b & 1) to the dword.  Exact because no count and no bin
 // end exceeds C <= capf < 65,536 (s <= 8192 here), so a half never carries into its neighbour.  2048 bins are 4 KB,
 // which lets the slab pass keep its whole bottom-s inside the LDS its rings leave free after the last slab.
-template <bool FIN>
+// BINS_AT: the LDS byte address of the bins where the caller knows it at compile time (the slab kernel: they follow the
+// 1 KB table at address 0), else -1.  hipcc learns the address of `sm.bins` only at link time and adds it, as a
+// v_add_u32 of 0, in front of every atomic.
+template <bool FIN, int BINS_AT = -1>
 __device__ void bottom_s_fast(const Smem &sm, uint32_t s, uint32_t tau, uint32_t C, uint32_t nbf_log2,
                               uint32_t *__restrict__ outp, const uint32_t *__restrict__ src, uint32_t first,
                               uint32_t step, uint32_t cnt)
 {
+    // tid_o for addresses (opaque, like z below): else every address that depends on the thread alone is hoisted out of the
+    // slab kernel's read loop and held in a VGPR across the hot loop, and the loop spills
     const int tid = threadIdx.x;
+    uint32_t tid_o = (uint32_t)tid;
+    asm volatile("" : "+v"(tid_o));
     auto fin = [](uint32_t h) { return FIN ? h ^ (h >> 16) : h; };
     uint32_t *bins = sm.bins;
     const uint16_t *bins16 = reinterpret_cast<const uint16_t *>(bins);
@@ -582,43 +634,93 @@ __device__ void bottom_s_fast(const Smem &sm, uint32_t s, uint32_t tau, uint32_t
     uint32_t z;
     asm volatile("v_mov_b32 %0, 0" : "=v"(z));
     if (wide)
-        reinterpret_cast<uint4 *>(bins)[tid] = make_uint4(z, z, z, z);
+        reinterpret_cast<uint4 *>(bins)[tid_o] = make_uint4(z, z, z, z);
     else
-        reinterpret_cast<uint2 *>(bins)[tid] = make_uint2(z, z);
+        reinterpret_cast<uint2 *>(bins)[tid_o] = make_uint2(z, z);
     if (tid == 0)
         sm.misc[8] = 0; // bins with more than BIG_BIN values
     if (PH_BS_WIN) { // the window pass below reads PH_BS_WIN entries on either side of binned[0, C): nothing there may count
         if (tid < PH_BS_WIN)
-            sm.binned[-1 - tid] = 0u;
+            sm.binned[-1 - (int)tid_o] = 0u;
         else if (tid < 2 * PH_BS_WIN)
-            sm.binned[C + (uint32_t)tid - PH_BS_WIN] = 0xFFFFFFFFu;
+            sm.binned[C + tid_o - PH_BS_WIN] = 0xFFFFFFFFu;
+    }
+    // The count and the scatter pass from REGISTERS, whenever the thread's share is at most BS_R candidates (`cnt` and so
+    // `ntrip` are wave-uniform): each candidate is loaded and finished once, all loads of the pass are in flight together,
+    // and it stays in its register over the barriers and the scan until it is scattered.  No candidate has an exec branch
+    // of its own: a lane whose index is past `cnt` reads the segment's last candidate instead, adds 0 to a dword of
+    // the bins that is its own (4 * first), and its store is masked.  With a = h >> (shift - 1), the bin's dword is at
+    // byte a & ~3 of the bins and bit 1 of `a` says which half of it (shift 0, a threshold below the number of bins, keeps
+    // the loops).  The loads are issued before the barrier that follows the zeroing: they touch neither bins nor binned.
+    const uint32_t ntrip = (cnt + step - 1u) / step;
+    const bool regs = ntrip <= (uint32_t)BS_R && shift >= 1;
+    const bool more = ntrip > (uint32_t)BS_R0;
+    const uint32_t bins_at = BINS_AT >= 0 ? (uint32_t)BINS_AT : lds_addr(bins);
+    uint32_t hr[BS_R], bin_at[BS_R], bin_inc[BS_R];
+    uint32_t first_o = first; // (opaque, like tid)
+    asm volatile("" : "+v"(first_o));
+    // candidate first + u * step is there: against a scalar, with no index per candidate
+    auto reg_valid = [&](int u) { return first_o < (cnt > (uint32_t)u * step ? cnt - (uint32_t)u * step : 0u); };
+    const uint32_t src_at = lds_addr(src) + 4u * first_o, last_at = lds_addr(src) + 4u * ((cnt ? cnt : 1u) - 1u);
+    auto reg_load = [&](int u) {
+        hr[u] = fin(*reinterpret_cast<const lds_u32 *>((uintptr_t)min(src_at + 4u * (uint32_t)u * step, last_at)));
+    };
+    // the bin's address and the increment are made once, for both passes (opaque: else they are made again in the scatter)
+    auto reg_count = [&](int u) {
+        const uint32_t a = hr[u] >> (shift - 1);
+        const bool there = reg_valid(u);
+        bin_at[u] = there ? a & ~3u : 4u * first_o; // (adds of 0 to ONE dword would queue up behind each other)
+        bin_inc[u] = there ? 1u << ((a & 2u) << 3) : 0u;
+        asm volatile("" : "+v"(bin_at[u]), "+v"(bin_inc[u]));
+        __hip_atomic_fetch_add(reinterpret_cast<lds_u32 *>((uintptr_t)(bin_at[u] + bins_at)), bin_inc[u], __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_WORKGROUP);
+    };
+    if (regs) {
+#pragma unroll
+        for (int u = 0; u < BS_R0; ++u)
+            reg_load(u);
+#pragma unroll
+        for (int u = BS_R0; u < BS_R; ++u)
+            hr[u] = z; // (never used unless `more`: defined on both paths, so that no undefined value reaches the join)
+        if (more) {
+#pragma unroll
+            for (int u = BS_R0; u < BS_R; ++u)
+                reg_load(u);
+        }
     }
     BS_SYNC();
-    // the loops over candidates are unrolled (PH_BS_U) so that the LDS round trips of a thread's elements overlap instead of
-    // queueing behind each other.  A wave's segment holds ~300 survivors and the sorted buffer ~1200, i.e. 4.7 per lane / per
-    // thread, so by four every loop runs a second, nearly empty trip -- but by five or six the kernel measures the same
-    // (1.46-1.50 ms per 100k reads all three, profiles/r05_k1_bottom_s_unroll.log): the bottom-s is its five barriers and
-    // the atomics' round trips, not its instruction count.
-    for (uint32_t i0 = first; i0 < cnt; i0 += BSU * step) {
-        uint32_t h[BSU];
+    if (regs) {
 #pragma unroll
-        for (int u = 0; u < BSU; ++u)
-            h[u] = i0 + u * step < cnt ? fin(src[i0 + u * step]) : 0u;
+        for (int u = 0; u < BS_R0; ++u)
+            reg_count(u);
+        if (more) {
 #pragma unroll
-        for (int u = 0; u < BSU; ++u)
-            if (i0 + u * step < cnt) {
-                const uint32_t b = h[u] >> shift;
-                atomicAdd(&bins[b >> 1], one(b));
-            }
+            for (int u = BS_R0; u < BS_R; ++u)
+                reg_count(u);
+        }
+    } else {
+        // more than BS_R candidates per thread (s > ~1500): by trips of BSU
+        for (uint32_t i0 = first; i0 < cnt; i0 += BSU * step) {
+            uint32_t h[BSU];
+#pragma unroll
+            for (int u = 0; u < BSU; ++u)
+                h[u] = i0 + u * step < cnt ? fin(src[i0 + u * step]) : 0u;
+#pragma unroll
+            for (int u = 0; u < BSU; ++u)
+                if (i0 + u * step < cnt) {
+                    const uint32_t b = h[u] >> shift;
+                    atomicAdd(&bins[b >> 1], one(b));
+                }
+        }
     }
     BS_SYNC();
     {
         uint32_t w[4];
         if (wide) {
-            const uint4 t = reinterpret_cast<const uint4 *>(bins)[tid];
+            const uint4 t = reinterpret_cast<const uint4 *>(bins)[tid_o];
             w[0] = t.x, w[1] = t.y, w[2] = t.z, w[3] = t.w;
         } else {
-            const uint2 t = reinterpret_cast<const uint2 *>(bins)[tid];
+            const uint2 t = reinterpret_cast<const uint2 *>(bins)[tid_o];
             w[0] = t.x, w[1] = t.y, w[2] = 0u, w[3] = 0u;
         }
         uint32_t c[8], sum = 0;
@@ -634,16 +736,16 @@ __device__ void bottom_s_fast(const Smem &sm, uint32_t s, uint32_t tau, uint32_t
         uint32_t run = incl - sum;
         for (int w8 = 0; w8 < (tid >> 6); ++w8)
             run += sm.misc[4 + w8];
-        const uint32_t b0 = (uint32_t)tid << (wide ? 3 : 2);
+        const uint32_t b0 = tid_o << (wide ? 3 : 2);
 #pragma unroll
         for (int i = 0; i < 4; ++i) { // start of each bin
             w[i] = run | ((run + c[2 * i]) << 16);
             run += c[2 * i] + c[2 * i + 1];
         }
         if (wide)
-            reinterpret_cast<uint4 *>(bins)[tid] = make_uint4(w[0], w[1], w[2], w[3]);
+            reinterpret_cast<uint4 *>(bins)[tid_o] = make_uint4(w[0], w[1], w[2], w[3]);
         else
-            reinterpret_cast<uint2 *>(bins)[tid] = make_uint2(w[0], w[1]);
+            reinterpret_cast<uint2 *>(bins)[tid_o] = make_uint2(w[0], w[1]);
         if (max(max(max(c[0], c[1]), max(c[2], c[3])), max(max(c[4], c[5]), max(c[6], c[7]))) > BIG_BIN) { // rare: repeated k-mers
 #pragma unroll
             for (int i = 0; i < 8; ++i)
@@ -655,21 +757,53 @@ __device__ void bottom_s_fast(const Smem &sm, uint32_t s, uint32_t tau, uint32_t
         }
     }
     BS_SYNC();
-    for (uint32_t i0 = first; i0 < cnt; i0 += BSU * step) { // afterwards bins[b] = end of bin b
-        uint32_t h[BSU], at[BSU];
+    // afterwards bins[b] = end of bin b
+    if (regs) {
+        // every returning add first, one wait, then the stores
+        uint32_t ret[BS_R];
+        const uint32_t binned_at = __builtin_amdgcn_readfirstlane(lds_addr(sm.binned)); // (one SGPR: else base + offset, an add each)
+        auto reg_add = [&](int u) {
+            ret[u] = __hip_atomic_fetch_add(reinterpret_cast<lds_u32 *>((uintptr_t)(bin_at[u] + bins_at)), bin_inc[u], __ATOMIC_RELAXED,
+                                            __HIP_MEMORY_SCOPE_WORKGROUP);
+        };
+        auto reg_put = [&](int u) { // (a lane without a candidate added 0 and stores nothing)
+            const uint32_t at = __builtin_amdgcn_ubfe(ret[u], bin_inc[u] >> 12, 16u); // (1 or 1 << 16: the half at bit 0 or 16)
+            lds_store_masked(binned_at + 4u * at, hr[u], __ballot(bin_inc[u] != 0u));
+        };
 #pragma unroll
-        for (int u = 0; u < BSU; ++u)
-            h[u] = i0 + u * step < cnt ? fin(src[i0 + u * step]) : 0u;
+        for (int u = 0; u < BS_R0; ++u)
+            reg_add(u);
+        if (more) {
 #pragma unroll
-        for (int u = 0; u < BSU; ++u)
-            if (i0 + u * step < cnt) {
-                const uint32_t b = h[u] >> shift;
-                at[u] = (atomicAdd(&bins[b >> 1], one(b)) >> ((b & 1u) << 4)) & 0xFFFFu;
-            }
+            for (int u = BS_R0; u < BS_R; ++u)
+                reg_add(u);
+        }
 #pragma unroll
-        for (int u = 0; u < BSU; ++u)
-            if (i0 + u * step < cnt)
-                sm.binned[at[u]] = h[u];
+        for (int u = 0; u < BS_R0; ++u)
+            reg_put(u);
+        if (more) {
+#pragma unroll
+            for (int u = BS_R0; u < BS_R; ++u)
+                reg_put(u);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // (hipcc does not count the stores of an asm block before the barrier)
+    } else {
+        for (uint32_t i0 = first; i0 < cnt; i0 += BSU * step) {
+            uint32_t h[BSU], at[BSU];
+#pragma unroll
+            for (int u = 0; u < BSU; ++u)
+                h[u] = i0 + u * step < cnt ? fin(src[i0 + u * step]) : 0u;
+#pragma unroll
+            for (int u = 0; u < BSU; ++u)
+                if (i0 + u * step < cnt) {
+                    const uint32_t b = h[u] >> shift;
+                    at[u] = (atomicAdd(&bins[b >> 1], one(b)) >> ((b & 1u) << 4)) & 0xFFFFu;
+                }
+#pragma unroll
+            for (int u = 0; u < BSU; ++u)
+                if (i0 + u * step < cnt)
+                    sm.binned[at[u]] = h[u];
+        }
     }
     BS_SYNC();
     const uint32_t nbig = sm.misc[8];
@@ -699,31 +833,54 @@ __device__ void bottom_s_fast(const Smem &sm, uint32_t s, uint32_t tau, uint32_t
     // no bins[] lookup -- one compare and one add-with-carry per neighbour.  Exact whenever the bin cannot reach beyond
     // the window, i.e. when the farthest neighbour on either side is of another bin; the few elements for which it is not
     // (a bin of five or more: 0.2 % of them) are ranked against their whole bin as before.
+    // A thread takes FOUR consecutive slots, 4t .. 4t + 3: binned is 16-byte aligned, so the twelve values it needs are
+    // three 16-byte reads (nine 4-byte reads per slot before), and each of the six pairs inside the quad is compared once
+    // for both its slots.  The quad that holds e* - 1 may reach past e* and, with its right neighbours, up to 10 dwords
+    // past C: into the margin and the big-bin list (slab pass) or misc and the table (tile pass) behind it, all inside the
+    // workgroup's LDS.  Those slots are switched off (`n`), and whatever they read is never used.  launch() checks the
+    // alignment of binned[0] and binned[capf].
     if (PH_ABL != 22) { // (PH_ABL 22: no rank pass -- timing only)
         const uint32_t lim = 1u << shift; // (a ^ b) < lim: same bin
-        for (uint32_t j = tid; j < e_star; j += THREADS) {
-            const uint32_t *__restrict__ w = sm.binned + j;
-            const uint32_t hv = w[0];
-            uint32_t pos = j;
-            bool far;
-            {
-                uint32_t l[PH_BS_WIN], r[PH_BS_WIN];
+        auto put = [&](uint32_t pos, uint32_t hv) {
+            // the row's scalar base + a 32-bit byte offset (pos < s <= 8192): no 64-bit address per lane
+            *reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(outp) + (pos << 2)) = hv;
+        };
+        for (uint32_t j = 4u * tid_o; j < e_star; j += 4u * THREADS) {
+            const uint4 *__restrict__ w4 = reinterpret_cast<const uint4 *>(sm.binned + j);
+            const uint4 q0 = w4[-1], q1 = w4[0], q2 = w4[1];
+            const uint32_t v[12] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w};
+            const uint32_t n = e_star - j; // slots of this quad that are there (>= 1)
+            uint32_t pos[4] = {j, j + 1u, j + 2u, j + 3u};
+            bool far[4];
 #pragma unroll
-                for (int d = 0; d < PH_BS_WIN; ++d) {
-                    l[d] = w[-1 - d];
-                    r[d] = w[1 + d];
-                }
+            for (int q = 0; q < 4; ++q) {
+                const uint32_t hv = v[4 + q];
 #pragma unroll
-                for (int d = 0; d < PH_BS_WIN; ++d) {
-                    pos -= l[d] > hv ? 1u : 0u;
-                    pos += r[d] < hv ? 1u : 0u;
+                for (int d = 0; d < 4; ++d) { // the neighbours outside the quad
+                    if (d > q - 1)
+                        pos[q] -= v[3 + q - d] > hv ? 1u : 0u;
+                    if (d > 2 - q)
+                        pos[q] += v[5 + q + d] < hv ? 1u : 0u;
                 }
-                far = ((l[PH_BS_WIN - 1] ^ hv) < lim) | ((r[PH_BS_WIN - 1] ^ hv) < lim);
+                far[q] = ((v[q] ^ hv) < lim) | ((v[8 + q] ^ hv) < lim);
             }
-            if (__builtin_expect(far, 0))
-                rank_in_bin(j, hv);
-            else if (pos < s)
-                outp[pos] = hv;
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = a + 1; b < 4; ++b) { // a pair inside the quad: the left one moves up, or the right one down
+                    const uint32_t gt = v[4 + a] > v[4 + b] ? 1u : 0u;
+                    pos[a] += gt;
+                    pos[b] -= gt;
+                }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (__builtin_expect(far[q], 0)) {
+                    if ((uint32_t)q < n)
+                        rank_in_bin(j + (uint32_t)q, v[4 + q]);
+                } else if (pos[q] < s && (uint32_t)q < n) {
+                    put(pos[q], v[4 + q]);
+                }
+            }
         }
     }
 #else
@@ -988,33 +1145,6 @@ template <int KS> struct Slabs {
     }
 };
 
-__device__ __forceinline__ uint32_t lds_addr(const uint32_t *p)
-{
-    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint32_t *)p;
-}
-
-// ds_write_b32 of value c by the lanes in mask[c] alone, c = 0..3, with no branch: hipcc guards each `if (a) store`
-// with a saveexec and a skip branch (four per slab, and out of line).  Only for code that runs with all 64 lanes
-// active, where exec = mask is exec & mask; a store under an empty mask writes nothing.
-__device__ __forceinline__ void lds_store4_masked(const uint32_t (&addr)[4], const uint32_t (&v)[4], const uint64_t (&mask)[4])
-{
-    uint64_t saved;
-    asm volatile("s_mov_b64 %0, exec\n\t"
-                 "s_mov_b64 exec, %9\n\t"
-                 "ds_write_b32 %1, %5\n\t"
-                 "s_mov_b64 exec, %10\n\t"
-                 "ds_write_b32 %2, %6\n\t"
-                 "s_mov_b64 exec, %11\n\t"
-                 "ds_write_b32 %3, %7\n\t"
-                 "s_mov_b64 exec, %12\n\t"
-                 "ds_write_b32 %4, %8\n\t"
-                 "s_mov_b64 exec, %0"
-                 : "=&s"(saved)
-                 : "v"(addr[0]), "v"(addr[1]), "v"(addr[2]), "v"(addr[3]), "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]),
-                   "s"(mask[0]), "s"(mask[1]), "s"(mask[2]), "s"(mask[3])
-                 : "memory");
-}
-
 // survivors of the lane's 4 hashes -> the wave's own segment; `cnt` is wave-uniform (kept in a scalar register)
 template <bool PARTIAL>
 __device__ __forceinline__ void append_own(uint32_t *__restrict__ seg, uint32_t capw, uint32_t &cnt, const uint32_t (&h)[4],
@@ -1178,7 +1308,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(PH_SLAB
     extern __shared__ __attribute__((aligned(16))) uint32_t smem_raw[];
     Smem sm;
     sm.lut = smem_raw;                 // first, so that a tail byte's entry is at LDS address 4 * byte (no base to add)
-    sm.seqb = smem_raw + 256;          // WAVES rings of n_seq_dw
+    sm.seqb = smem_raw + LUT_DW;       // WAVES rings of n_seq_dw
     sm.P = sm.seqb + WAVES * n_seq_dw; // WAVES rings of n_P_w
     sm.bins = sm.seqb;                 // after the slabs
     sm.binned = sm.bins + ((1u << nbf_log2) >> 1) + BS_MARGIN;
@@ -1214,7 +1344,8 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(PH_SLAB
         const uint32_t C = c0 + c1 + c2 + c3;
         const bool ok = max(max(c0, c1), max(c2, c3)) <= capw - (PH_SEL_ATOMIC ? 1u : 0u) && C >= s && C <= capf; // enough survivors, none lost
         if (ok)
-            bottom_s_fast<true>(sm, s, tauq, C, nbf_log2, outp, seg, (uint32_t)(tid & 63), 64u, cw);
+            // (sm.bins = smem_raw + LUT_DW, and the dynamic LDS starts at address 0: tests/test_k1_slab_resources_cpu.py)
+            bottom_s_fast<true, (int)(LUT_DW * 4u)>(sm, s, tauq, C, nbf_log2, outp, seg, (uint32_t)(tid & 63), 64u, cw);
         else if (tid == 0) {
             outp[0] = MARK0;
             outp[1] = MARK1;
@@ -1498,7 +1629,7 @@ static Launch plan(uint32_t k, uint32_t s)
         const uint32_t sorted = ((1u << L.nbf_log2_slab) >> 1) + L.capf_slab + 2 * BS_MARGIN + L.capf_slab / (BIG_BIN + 1) + 1;
         L.n_span = rings > sorted ? rings : sorted;
     }
-    L.smem_slab = ((size_t)256 + L.n_span + 16 + (size_t)WAVES * L.capw) * 4;
+    L.smem_slab = ((size_t)LUT_DW + L.n_span + 16 + (size_t)WAVES * L.capw) * 4;
 #ifdef PH_LDS_PAD
     L.smem_slab += PH_LDS_PAD; // occupancy probe
 #endif
@@ -1516,6 +1647,12 @@ template <int KS>
 static int launch(const uint8_t *d_seqs, const uint64_t *d_offs, uint64_t n, uint32_t k, uint32_t s,
                   uint32_t *d_out, const Launch &L, hipStream_t st)
 {
+    // the rank pass of bottom_s_fast reads binned[] by aligned 16 bytes, a quad of slots at a time: binned[0] (the tile
+    // pass: behind seqb, P, cand[capf] and the margin; the slab pass: behind the table, the bins and the margin) and
+    // binned[capf] must lie on 16 bytes
+    PH_REQUIRE(L.capf % 4u == 0 && L.capf_slab % 4u == 0 && (WAVES * L.n_seq_dw + L.n_P_fast + L.capf + BS_MARGIN) % 4u == 0 &&
+                   (LUT_DW + ((1u << L.nbf_log2_slab) >> 1) + BS_MARGIN) % 4u == 0,
+               "polyhip_mash_sketch_batch: the sorted buffer of the LDS layout is not 16-byte aligned");
     auto general = sketch_general_kernel<KS>;
     PH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(general), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)L.smem_general));
