@@ -121,3 +121,62 @@ func (ix *Index) Extract(start, end int) (string, error) {
 	}
 	return string(out), nil
 }
+
+// MismatchHit is one position of the sequence at which a pattern occurs with Mismatches substitutions.
+type MismatchHit struct{ Pos, Mismatches int }
+
+// CountMismatchBatch: per pattern, the positions at Hamming distance exactly 0..k (k <= 4):
+// substitutions only, matches inside the sequence, bytes compared raw.  An empty pattern fails the batch as Count does.
+func (ix *Index) CountMismatchBatch(patterns []string, k int) ([][]int, error) {
+	buf, offs := polyhip.Pack(patterns)
+	counts, errs, err := ix.dev.CountMismatchBatch(buf, offs, k)
+	if err != nil {
+		return nil, err
+	}
+	res := make([][]int, len(patterns))
+	for i := range res {
+		if errs[i] != 0 {
+			return nil, errors.New("Pattern can not be empty")
+		}
+		res[i] = make([]int, k+1)
+		for d := range res[i] {
+			res[i][d] = int(counts[i*(k+1)+d])
+		}
+	}
+	return res, nil
+}
+
+// LocateMismatchBatch: per pattern, every hit with at most k mismatches, ascending by position; nil where there is none.
+func (ix *Index) LocateMismatchBatch(patterns []string, k int) ([][]MismatchHit, error) {
+	buf, offs := polyhip.Pack(patterns)
+	first, pos, mm, errs, err := ix.dev.LocateMismatchBatch(buf, offs, k, 4*len(patterns))
+	if err != nil {
+		return nil, err
+	}
+	res := make([][]MismatchHit, len(patterns))
+	for i := range res {
+		if errs[i] != 0 {
+			return nil, errors.New("Pattern can not be empty")
+		}
+		for j := first[i]; j < first[i+1]; j++ {
+			res[i] = append(res[i], MismatchHit{Pos: int(pos[j]), Mismatches: int(mm[j])})
+		}
+	}
+	return res, nil
+}
+
+func (ix *Index) CountMismatch(pattern string, k int) ([]int, error) {
+	c, err := ix.CountMismatchBatch([]string{pattern}, k)
+	if err != nil {
+		return nil, err
+	}
+	return c[0], nil
+}
+
+func (ix *Index) LocateMismatch(pattern string, k int) ([]MismatchHit, error) {
+	r, err := ix.LocateMismatchBatch([]string{pattern}, k)
+	if err != nil {
+		return nil, err
+	}
+	return r[0], nil
+}

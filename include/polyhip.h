@@ -776,6 +776,49 @@ int polyhip_bwt_extract(const polyhip_bwt *h, const int64_t *start,
                         const int64_t *end, uint64_t nreq,
                         const uint64_t *out_off, uint8_t *out, uint32_t *err);
 
+/* ---- search/bwt with mismatches: where a pattern almost occurs (no counterpart in the reference) ---- */
+/*
+ * S = the handle's sequence (n bytes, without the '$'), P a pattern of m >= 1 bytes, 0 <= k <= POLYHIP_BWT_MAX_MISMATCHES:
+ *   hits(P, k) = { (p, d) : 0 <= p <= n - m,  d = #{ j : S[p + j] != P[j] } <= k }
+ * Mismatches are substitutions only (no insertions or deletions).  Bytes are compared raw, as count does (no case
+ * folding); a pattern byte that is '$' or does not occur in S costs one mismatch wherever it stands; m > n gives no hits.
+ * Matches lie inside the sequence: they never run through the '$'.  For k = 0 this is count / locate restricted to
+ * patterns without '$' and with m <= n -- the cyclic cases of the exact count ("a$" on "banana": 1 row) are NOT
+ * reproduced here (0 hits).
+ * The search is a backward search with backtracking over the handle's index (every symbol of the sequence's alphabet is
+ * tried at cost 1 while mismatches are left; '$' is never tried), one pattern per lane.
+ *
+ * count_mismatch: counts[p * (k + 1) + d] = the positions at which pattern p has exactly d mismatches (each <= n).
+ * locate_mismatch: first[0..npat] = exclusive scan of the per-pattern totals; pattern p's hits are pos[first[p] ..
+ *   first[p + 1]), sorted by position ascending, and mm[] holds each hit's d.  Capacity as in polyhip_bwt_locate: first[] is
+ *   always filled; if first[npat] > capacity nothing is written to pos / mm and the call fails with POLYHIP_ERR_INVALID
+ *   naming the size needed.  No device buffer for hits is allocated before that check, so the caller's capacity bounds
+ *   the allocation (29 bytes per hit: two (key, value) buffers of the sort and the result).
+ * err[p] = 1 for an empty pattern ("Pattern can not be empty"), with zero counts and no hits; otherwise 0.  npat == 0 is
+ * an empty, successful call (first[0] = 0).
+ * Errors, in this order: k > POLYHIP_BWT_MAX_MISMATCHES is POLYHIP_ERR_UNSUPPORTED (before the handle is looked at); a
+ * NULL handle or NULL arguments are POLYHIP_ERR_INVALID; offsets that do not ascend are POLYHIP_ERR_INVALID.
+ * The calls run on the handle's device and stream, as polyhip_bwt_count does; the device list does not apply.
+ * mismatch_last_info: the calling thread's last count_mismatch / locate_mismatch call: patterns = npat; nodes = live nodes
+ *   of the search tree visited: the expanded ones and the leaves, which are not expanded, so nodes - leaves is the number
+ *   of expansions; occ_lines = distinct 128-byte lines (nucleotide layout) or checkpoint blocks (general layout) that the
+ *   expansions read: one per range end, one in all where both ends share it, so in the nucleotide layout
+ *   nodes - leaves <= occ_lines <= 2 * (nodes - leaves) whatever k is; leaves = leaf intervals; hits = positions
+ *   (= first[npat]).  locate runs the search twice (totals, then positions); the figures are those of one search.
+ */
+#define POLYHIP_BWT_MAX_MISMATCHES 4u
+typedef struct polyhip_bwt_mismatch_info {
+    uint64_t patterns, nodes, occ_lines, leaves, hits;
+} polyhip_bwt_mismatch_info;
+int polyhip_bwt_count_mismatch(const polyhip_bwt *h, const uint8_t *pat,
+                               const uint64_t *off, uint64_t npat, uint32_t k,
+                               uint32_t *counts, uint32_t *err);
+int polyhip_bwt_locate_mismatch(const polyhip_bwt *h, const uint8_t *pat,
+                                const uint64_t *off, uint64_t npat, uint32_t k,
+                                uint64_t *first, uint32_t *pos, uint8_t *mm,
+                                uint64_t capacity, uint32_t *err);
+int polyhip_bwt_mismatch_last_info(polyhip_bwt_mismatch_info *info);
+
 /* ---- read mapping: FM-index seeds, diagonal clusters, SmithWaterman extension (no counterpart in the reference) ---- */
 /*
  * Places every read of a packed batch on the text T (n bytes) of a polyhip_bwt handle.  For a read r of m bytes:

@@ -124,6 +124,9 @@ SIGNATURES = {
     "polyhip_bwt_locate": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp]),
     "polyhip_bwt_extract_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     "polyhip_bwt_extract": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "polyhip_bwt_count_mismatch": (C.c_int, [_vp, _vp, _vp, _u64, _u32, _vp, _vp]),
+    "polyhip_bwt_locate_mismatch": (C.c_int, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _u64, _vp]),
+    "polyhip_bwt_mismatch_last_info": (C.c_int, [_vp]),
     "polyhip_map_workspace_bytes": (C.c_size_t, [_vp, _vp, _vp, _u64, _u32]),
     "polyhip_map_reads_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                         _vp, _u64, _vp, C.c_size_t, _vp]),

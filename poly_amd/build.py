@@ -105,6 +105,21 @@ def build_abi_threads() -> str:
     return exe
 
 
+def build_abi_bwt_mismatch() -> str:
+    """tests/abi/abi_bwt_mismatch: two pthreads on one bwt handle in the search with mismatches (plain gcc, -lpolyhip -lpthread)."""
+    src = os.path.join(ROOT, "tests", "abi", "abi_bwt_mismatch.c")
+    exe = os.path.join(ROOT, "tests", "abi", "abi_bwt_mismatch")
+    lib = build_lib()
+    if _newer(exe, [src, lib, os.path.join(ROOT, "include", "polyhip.h")]):
+        cmd = ["gcc", "-O1", "-Wall", "-I", os.path.join(ROOT, "include"), src, "-o", exe, "-L", HERE, "-lpolyhip", "-lpthread",
+               "-lm", "-Wl,-rpath,$ORIGIN/../../poly_amd"]
+        res = subprocess.run(cmd, capture_output=True, text=True)
+        if res.returncode:
+            sys.stderr.write(" ".join(cmd) + "\n" + res.stdout + res.stderr)
+            raise RuntimeError("build of tests/abi/abi_bwt_mismatch failed")
+    return exe
+
+
 def build_abi_allgather() -> str:
     """tests/abi/abi_allgather: the torch-free multi-rank C host (libpolyhip + the HIP runtime for its device buffers)."""
     src = os.path.join(ROOT, "tests", "abi", "abi_allgather.c")

@@ -2,7 +2,8 @@
 
 Mirrors search/bwt/bwt.go: ``New`` (:455-517) and ``BWT`` with ``Count`` (:235-247), ``Locate`` (:249-273),
 ``Extract`` (:275-299), ``Len`` (:301-304) and ``GetTransform`` (:306-323), plus the batch forms a GPU needs
-(``CountBatch``, ``LocateBatch``, ``ExtractBatch``) and ``*_dev`` entry points on torch tensors.  The suffix array,
+(``CountBatch``, ``LocateBatch``, ``ExtractBatch``), ``*_dev`` entry points on torch tensors, and the search with up to
+four substitutions (``CountMismatch``, ``LocateMismatch`` and their batch forms).  The suffix array,
 the last column and the occurrence structure are built and queried in HIP (polyhip_bwt_*); nothing is computed here.
 
 Sequences and patterns are Go strings, i.e. bytes: a ``str`` is taken one byte per character (latin-1), and a BWT
@@ -133,6 +134,70 @@ class BWT:
         if err.any():
             raise ValueError("Pattern can not be empty")
         return first, out[: int(first[n])]
+
+    # -- with mismatches (polyhip_bwt_*_mismatch: substitutions only, matches inside the sequence) ---------------------------
+    def count_mismatch_packed(self, buf: np.ndarray, offs: np.ndarray, k: int):
+        """(counts uint32[n, k + 1], err uint32[n]): counts[p, d] = positions where pattern p has exactly d mismatches;
+        err = 1 marks an empty pattern"""
+        n = len(offs) - 1
+        k = int(k)
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        counts = np.zeros((n, max(k, 0) + 1), np.uint32)
+        err = np.zeros(n, np.uint32)
+        _lib.check(_lib.lib().polyhip_bwt_count_mismatch(self._handle, buf.ctypes.data, offs.ctypes.data, n, k, counts.ctypes.data,
+                                                         err.ctypes.data))
+        return counts, err
+
+    def CountMismatchBatch(self, patterns, k: int) -> np.ndarray:
+        """int64[n, k + 1]: per pattern, the positions at Hamming distance exactly 0..k; an empty pattern raises"""
+        counts, err = self.count_mismatch_packed(*_pack(patterns), k)
+        if err.any():
+            raise ValueError("Pattern can not be empty")
+        return counts.astype(np.int64)
+
+    def CountMismatch(self, pattern, k: int) -> np.ndarray:
+        if len(pattern) == 0:
+            raise ValueError("Pattern can not be empty")
+        return self.CountMismatchBatch([pattern], k)[0]
+
+    def locate_mismatch_packed(self, buf: np.ndarray, offs: np.ndarray, k: int, capacity: int | None = None):
+        """(first uint64[n + 1], pos uint32[], mm uint8[], err uint32[n])"""
+        n = len(offs) - 1
+        k = int(k)
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        if capacity is None:
+            capacity = int(self.count_mismatch_packed(buf, offs, k)[0].sum(dtype=np.uint64))
+        first = np.zeros(n + 1, np.uint64)
+        pos = np.zeros(max(int(capacity), 1), np.uint32)
+        mm = np.zeros(max(int(capacity), 1), np.uint8)
+        err = np.zeros(n, np.uint32)
+        _lib.check(_lib.lib().polyhip_bwt_locate_mismatch(self._handle, buf.ctypes.data, offs.ctypes.data, n, k, first.ctypes.data,
+                                                          pos.ctypes.data, mm.ctypes.data, int(capacity), err.ctypes.data))
+        total = int(first[n])
+        return first, pos[:total], mm[:total], err
+
+    def LocateMismatchBatch(self, patterns, k: int, capacity: int | None = None):
+        """(first uint64[n + 1], pos uint32[first[n]], mm uint8[first[n]]): pattern p's hits are pos[first[p]:first[p + 1]],
+        ascending, with their mismatches in mm.  ``capacity`` (default: what a count pass says is needed) sizes the buffers."""
+        first, pos, mm, err = self.locate_mismatch_packed(*_pack(patterns), k, capacity)
+        if err.any():
+            raise ValueError("Pattern can not be empty")
+        return first, pos, mm
+
+    def LocateMismatch(self, pattern, k: int):
+        """[(position, mismatches)] ascending by position; None when there is no hit, as Locate"""
+        if len(pattern) == 0:
+            raise ValueError("Pattern can not be empty")
+        first, pos, mm = self.LocateMismatchBatch([pattern], k)
+        return None if first[1] == 0 else [(int(a), int(b)) for a, b in zip(pos, mm)]
+
+    def MismatchInfo(self) -> dict:
+        """polyhip_bwt_mismatch_last_info: the calling thread's last mismatch call"""
+        info = (C.c_uint64 * 5)()
+        _lib.check(_lib.lib().polyhip_bwt_mismatch_last_info(C.addressof(info)))
+        return dict(zip(("patterns", "nodes", "occ_lines", "leaves", "hits"), (int(v) for v in info)))
 
     def extract_raw(self, requests):
         """(bytes per request or None, err uint32[n]) with err = 0 or the reference's failing check (1, 2, 3)"""

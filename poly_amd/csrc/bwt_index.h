@@ -244,6 +244,40 @@ __device__ __forceinline__ uint32_t occ_nuc(const Index &x, uint32_t c, uint32_t
     return r;
 }
 
+// the occurrences of all four codes in rows [0, i) from one pass over the line's words (x: code 0 .. w: code 3); what a
+// search that branches on every symbol needs per range end (bwt_mismatch.hip).  Each component equals occ_nuc's.
+__device__ __forceinline__ uint4 occ_nuc4(const Index &x, uint32_t i)
+{
+    const uint32_t line = i / NUC_SYMS, off = i - line * NUC_SYMS;
+    const uint4 *p = x.lines + (uint64_t)line * 8;
+    uint4 r = p[0];
+    constexpr uint64_t LOW = 0x5555555555555555ull;
+#pragma unroll
+    for (int q = 0; q < 7; ++q) {
+        if (off <= 64u * q)
+            break;
+        const uint4 v = p[1 + q];
+        const uint64_t wd[2] = {(uint64_t)v.x | ((uint64_t)v.y << 32), (uint64_t)v.z | ((uint64_t)v.w << 32)};
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int first = 64 * q + 32 * h;
+            if ((int)off <= first)
+                break;
+            const int take = min((int)off - first, 32);
+            const uint64_t keep = take < 32 ? LOW & ((1ull << (2 * take)) - 1) : LOW;
+            const uint64_t lo = wd[h] & keep, hi = (wd[h] >> 1) & keep;
+            const uint32_t n1 = (uint32_t)__popcll(lo & ~hi), n2 = (uint32_t)__popcll(hi & ~lo), n3 = (uint32_t)__popcll(hi & lo);
+            r.x += (uint32_t)take - n1 - n2 - n3;
+            r.y += n1;
+            r.z += n2;
+            r.w += n3;
+        }
+    }
+    if (x.primary >= line * NUC_SYMS && x.primary < i)
+        r.x -= 1; // the '$' slot holds code 0 and is no base
+    return r;
+}
+
 __device__ __forceinline__ uint32_t occ_gen(const Index &x, uint32_t c, uint8_t b, uint32_t i)
 {
     const uint32_t blk = i / GEN_ROWS, off = i - blk * GEN_ROWS;
