@@ -147,3 +147,37 @@ func SmithWatermanBatch(reads []string, reference string, scoring Scoring) []Ali
 	}
 	return out
 }
+
+// SmithWatermanAffine is SmithWaterman with affine gaps (no counterpart in the reference): the first symbol of a gap
+// costs gapOpen and each further one gapExtend (both negative, gapOpen <= gapExtend <= -1); scoring.GapPenalty is ignored.
+// With gapOpen == gapExtend it returns what SmithWaterman returns with that GapPenalty.  It always runs on the device.
+// Gaps outside the accepted range, and scores that could leave the library's 32-bit cells, come back as the error.
+func SmithWatermanAffine(stringA string, stringB string, scoring Scoring, gapOpen int, gapExtend int) (int, string, string, error) {
+	res, err := SmithWatermanAffineBatch([]string{stringA}, stringB, scoring, gapOpen, gapExtend)
+	if err != nil {
+		return 0, "", "", err
+	}
+	if res[0].Err != nil {
+		return 0, "", "", res[0].Err
+	}
+	return res[0].Score, res[0].AlignA, res[0].AlignB, nil
+}
+
+// SmithWatermanAffineBatch aligns every read against one shared reference with affine gaps in one device call.  The
+// error is the call's (gaps or scores out of range); a read with a symbol outside the alphabet has its own Err.
+func SmithWatermanAffineBatch(reads []string, reference string, scoring Scoring, gapOpen int, gapExtend int) ([]Alignment, error) {
+	A, offA := polyhip.Pack(reads)
+	raw, err := handle(scoring).SWAffineAlignBatch(gapOpen, gapExtend, A, offA, []byte(reference), nil)
+	if err != nil {
+		return nil, err
+	}
+	out := make([]Alignment, len(reads))
+	for i, r := range raw {
+		if r.Err != 0 {
+			out[i].Err = symbolError(r.Err)
+			continue
+		}
+		out[i] = Alignment{Score: int(r.Score), AlignA: r.AlignA, AlignB: r.AlignB}
+	}
+	return out, nil
+}

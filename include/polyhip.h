@@ -472,6 +472,64 @@ int polyhip_sw_align_batch_packed(const polyhip_scoring *sc, const uint8_t *A,
                                   uint32_t *endB, uint32_t *err, uint8_t *alnA,
                                   uint8_t *alnB, uint64_t *alnOff,
                                   uint64_t aln_capacity);
+/* ---- search/align SmithWaterman with affine gaps (Gotoh; no counterpart in the reference) ---- */
+/*
+ * S is the scoring handle's table.  gap_open = go and gap_extend = ge are added values, as GapPenalty is: the first symbol
+ * of a gap costs go and each further one costs ge.  The handle's own gap is ignored.
+ * Rows i run over A and columns j over B.  H[i][0] = H[0][j] = 0.  E[i][0] = F[0][j] = -inf.
+ *   E[i][j] = max(H[i][j-1] + go, E[i][j-1] + ge)      gap in A (alignA gets '-')
+ *   F[i][j] = max(H[i-1][j] + go, F[i-1][j] + ge)      gap in B (alignB gets '-')
+ *   H[i][j] = max(0, H[i-1][j-1] + S(a_i, b_j), F[i][j], E[i][j])
+ * With go == ge this is polyhip_sw_batch's recurrence with gap = go: score, end cell and both strings are the same.
+ * Argmax: the first maximum in row-major order wins (strict '>'), as in polyhip_sw_batch.  endA and endB are 1-based, and
+ * 0, 0 when the score is 0.
+ * Traceback: it starts at (endA, endB) in state H and has three states.
+ *   State H at (i,j): stop if H == 0.  If H == H[i-1][j-1] + S, emit (a_i, b_j) and move to (i-1, j-1).  Otherwise, if
+ *     H == F[i][j], switch to state F.  Otherwise switch to state E.  (Diagonal, then up, then left, as in the reference.)
+ *   State F at (i,j): emit (a_i, '-').  If F[i][j] == H[i-1][j] + go the next state is H (open is preferred over extend),
+ *     otherwise the state stays F.  Then i -= 1.
+ *   State E at (i,j): the same along the row: emit ('-', b_j), test E[i][j] == H[i][j-1] + go, then j -= 1.
+ * The strings are built by prepending.
+ * err: exactly as polyhip_sw_batch -- a[0], then the first invalid b[j], then the first invalid a[i]; never set when a
+ * side is empty.  Such pairs get score 0 and empty strings.
+ * Accepted range: go <= ge <= -1, and absmax * (max_lenA + lenB) < 2^30 where absmax = max(|smin|, |smax|, |go|) over
+ * the handle's table; anything else is POLYHIP_ERR_UNSUPPORTED.  The gap check comes first, before the handle is looked
+ * at.  NULL arguments and offsets that do not ascend are POLYHIP_ERR_INVALID.  npairs == 0 is an empty, successful call.
+ * Cells are int32, exact over the whole accepted range.
+ * Column window of the traceback: a pair with score s >= 1 that ends at (endA, endB) has a path that spans at most
+ *   W_p = endA + floor((smax * endA - s) / -ge)
+ * columns (with x diagonal and l left steps, s <= smax * x + ge * l and x <= endA), so its strings have at most
+ * endA + min(endB, W_p - endA) bytes.  The traceback re-runs the DP on rows 1..endA and columns
+ * (endB - min(endB, W_p), endB] with a zero boundary on the left: windowed values never exceed the true ones, and every
+ * cell the true walk enters has its whole optimal path inside the window, so each equality the walk tests holds in the
+ * window exactly when it holds in the full matrix.
+ * These are host-pointer entry points, like polyhip_sw_batch and polyhip_sw_align_batch_packed: B is shared when
+ * offB == NULL (lenB its length), else a packed batch.  alnOff and aln_capacity behave as in
+ * polyhip_sw_align_batch_packed: alnOff (npairs + 1 entries) is always filled, and if the strings need more room the call
+ * returns POLYHIP_ERR_INVALID with alnOff[npairs] = the bytes needed, after filling score, endA, endB and err.
+ * The calls run on the scoring handle's device, on the calling thread's own streams, never on the null stream; the device
+ * list does not apply.  The direction bits of the traceback (4 per cell of a pair's window) are sized from each pair's own
+ * W_p; when they would exceed 1 GiB the call loops over chunks of pairs (POLYHIP_SWA_CHUNK_PAIRS=<n> in the environment
+ * forces the chunk size: a testing aid).
+ * polyhip_sw_affine_last_info: the calling thread's last affine call: pairs = npairs; cells = cell updates of the score
+ * pass (lenA * lenB over the pairs without err); tb_cells = cell updates of the traceback windows (0 for the score call);
+ * chunks = chunks of pairs the traceback looped over; rows_per_band = rows of A a lane holds in registers per sweep of the
+ * columns; table_in_lds = 1 when the compact score table was staged in LDS, 0 when scores came from global memory.
+ */
+typedef struct polyhip_sw_affine_info {
+    uint64_t pairs, cells, tb_cells, chunks, rows_per_band, table_in_lds;
+} polyhip_sw_affine_info;
+int polyhip_sw_affine_batch(const polyhip_scoring *sc, int64_t gap_open, int64_t gap_extend,
+                            const uint8_t *A, const uint64_t *offA, uint64_t npairs,
+                            const uint8_t *B, const uint64_t *offB, uint64_t lenB,
+                            int64_t *score, uint32_t *endA, uint32_t *endB, uint32_t *err);
+int polyhip_sw_affine_align_batch_packed(const polyhip_scoring *sc, int64_t gap_open, int64_t gap_extend,
+                                         const uint8_t *A, const uint64_t *offA, uint64_t npairs,
+                                         const uint8_t *B, const uint64_t *offB, uint64_t lenB,
+                                         int64_t *score, uint32_t *endA, uint32_t *endB, uint32_t *err,
+                                         uint8_t *alnA, uint8_t *alnB, uint64_t *alnOff,
+                                         uint64_t aln_capacity);
+int polyhip_sw_affine_last_info(polyhip_sw_affine_info *info);
 /* ---- search/align NeedlemanWunsch  (search/align/align.go:100-166) -------------- */
 /*
  * Global alignment of every pair (A_p, B_p) (B shared when d_offB == NULL): score

@@ -86,6 +86,10 @@ SIGNATURES = {
                                              _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
     "polyhip_sw_align_batch": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32]),
     "polyhip_sw_align_batch_packed": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64]),
+    "polyhip_sw_affine_batch": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "polyhip_sw_affine_align_batch_packed": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp,
+                                                       _vp, _vp, _vp, _u64]),
+    "polyhip_sw_affine_last_info": (C.c_int, [_vp]),
     "polyhip_santalucia_scan_dev": (C.c_int, [_vp, _u64, _u64, _u64, _u32, _u32, _dbl, _dbl, _dbl, _vp, _vp, _vp,
                                               _u64, _vp]),
     "polyhip_santalucia_scan": (C.c_int, [_vp, _u64, _u32, _u32, _dbl, _dbl, _dbl, _vp, _vp, _vp]),

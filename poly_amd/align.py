@@ -245,6 +245,97 @@ def SmithWatermanBatch(reads, ref, scoring: Scoring):
     return out
 
 
+# ---- SmithWaterman with affine gaps (polyhip_sw_affine_*: no counterpart in the reference) ---------------
+
+def _affine_args(A, offA, B, offB):
+    A = np.ascontiguousarray(A, dtype=np.uint8)
+    B = np.ascontiguousarray(B, dtype=np.uint8)
+    offA = np.ascontiguousarray(offA, dtype=np.uint64)
+    if offB is not None:
+        offB = np.ascontiguousarray(offB, dtype=np.uint64)
+    return A, offA, B, offB
+
+
+def sw_affine_packed(scoring: Scoring, gap_open: int, gap_extend: int, A: np.ndarray, offA: np.ndarray, B: np.ndarray,
+                     offB: np.ndarray | None = None):
+    """Score pass with affine gaps (the first symbol of a gap costs gap_open, each further one gap_extend; the scoring's own
+    GapPenalty is ignored): (score int64[n], endA uint32[n], endB uint32[n], err uint32[n]).  ``offB is None`` -> one
+    shared B for every pair."""
+    n = len(offA) - 1
+    A, offA, B, offB = _affine_args(A, offA, B, offB)
+    score = np.zeros(n, dtype=np.int64)
+    endA, endB, err = (np.zeros(n, dtype=np.uint32) for _ in range(3))
+    _lib.check(_lib.lib().polyhip_sw_affine_batch(
+        scoring.handle(), int(gap_open), int(gap_extend), A.ctypes.data, offA.ctypes.data, n, B.ctypes.data,
+        offB.ctypes.data if offB is not None else None, len(B) if offB is None else 0,
+        score.ctypes.data, endA.ctypes.data, endB.ctypes.data, err.ctypes.data))
+    return score, endA, endB, err
+
+
+def sw_affine_align_packed(scoring: Scoring, gap_open: int, gap_extend: int, A: np.ndarray, offA: np.ndarray, B: np.ndarray,
+                           offB: np.ndarray | None = None, capacity: int | None = None):
+    """The whole affine SmithWaterman with packed strings: (score, endA, endB, err, alignA list[bytes], alignB
+    list[bytes]).  `capacity` bytes per string buffer (default: 1.25 x the reads' bytes + 64 KB; a batch that needs more is
+    run again with the exact size, as sw_align_strings_packed does)."""
+    n = len(offA) - 1
+    A, offA, B, offB = _affine_args(A, offA, B, offB)
+    score = np.zeros(n, dtype=np.int64)
+    endA, endB, err = (np.zeros(n, dtype=np.uint32) for _ in range(3))
+    off = np.zeros(n + 1, dtype=np.uint64)
+    cap = int(capacity) if capacity is not None else int(int(offA[n] - offA[0]) * 1.25) + (64 << 10)
+    for _ in range(2):
+        alnA, alnB = np.zeros(max(cap, 1), dtype=np.uint8), np.zeros(max(cap, 1), dtype=np.uint8)
+        rc = _lib.lib().polyhip_sw_affine_align_batch_packed(
+            scoring.handle(), int(gap_open), int(gap_extend), A.ctypes.data, offA.ctypes.data, n, B.ctypes.data,
+            offB.ctypes.data if offB is not None else None, len(B) if offB is None else 0,
+            score.ctypes.data, endA.ctypes.data, endB.ctypes.data, err.ctypes.data, alnA.ctypes.data, alnB.ctypes.data,
+            off.ctypes.data, cap)
+        if rc == _lib.ERR_INVALID and int(off[n]) > cap:   # the strings did not fit: off[n] says what they need
+            cap = int(off[n])
+            continue
+        _lib.check(rc)
+        break
+    o = off.astype(np.int64)
+    sa = [alnA[o[p]:o[p + 1]].tobytes() for p in range(n)]
+    sb = [alnB[o[p]:o[p + 1]].tobytes() for p in range(n)]
+    return score, endA, endB, err, sa, sb
+
+
+def SmithWatermanAffine(stringA, stringB, scoring: Scoring, gap_open: int, gap_extend: int):
+    """-> (score, alignA, alignB); raises alphabet.Error as SmithWaterman does."""
+    A, offA = _pack([stringA])
+    B, _ = _pack([stringB])
+    score, _, _, err, sa, sb = sw_affine_align_packed(scoring, gap_open, gap_extend, A, offA, B, None)
+    if err[0]:
+        _raise_symbol(int(err[0]))
+    return int(score[0]), sa[0].decode("latin-1"), sb[0].decode("latin-1")
+
+
+def SmithWatermanAffineBatch(reads, ref, scoring: Scoring, gap_open: int, gap_extend: int):
+    """Every read against one shared reference -> list of (score, alignA, alignB) or alphabet.Error instances."""
+    A, offA = _pack(reads)
+    B, _ = _pack([ref])
+    score, _, _, err, sa, sb = sw_affine_align_packed(scoring, gap_open, gap_extend, A, offA, B, None)
+    out = []
+    for p in range(len(reads)):
+        if err[p]:
+            out.append(alphabet.Error(f"Symbol {chr(int(err[p]) & 0xFF)} not in alphabet"))
+        else:
+            out.append((int(score[p]), sa[p].decode("latin-1"), sb[p].decode("latin-1")))
+    return out
+
+
+def sw_affine_last_info() -> dict:
+    """The calling thread's last affine call: pairs, cells (score pass), tb_cells (traceback windows), chunks (of the
+    traceback), rows_per_band (rows of A a lane holds in registers), table_in_lds (bool)."""
+    info = (C.c_uint64 * 6)()
+    _lib.check(_lib.lib().polyhip_sw_affine_last_info(C.addressof(info)))
+    keys = ("pairs", "cells", "tb_cells", "chunks", "rows_per_band", "table_in_lds")
+    out = {k: int(v) for k, v in zip(keys, info)}
+    out["table_in_lds"] = bool(out["table_in_lds"])
+    return out
+
+
 def sw_traceback_dev(scoring: Scoring, A_t, offA_t, max_lenA: int, B_t, offB_t, lenB: int, endA_t, endB_t, err_t,
                      alnA_t, alnB_t, alnLen_t, work_t, stream=None, score_t=None) -> None:
     """Device-resident traceback on torch CUDA tensors (alnA/alnB: (n, stride) uint8); score_t (the

@@ -156,6 +156,16 @@ int score_pass(const polyhip_scoring *sc, const uint8_t *d_A, const uint64_t *d_
 } // namespace k3
 } // namespace polyhip
 
+// ---- packed strings (sw_traceback.hip): the last alnLen[p] bytes of pair p's two stride-byte slots -> outA / outB at
+// off[p] = base + the lengths before p; off[n] = base + the total.  bsum: pack_bsum_bytes(n) bytes of device scratch.
+namespace polyhip {
+namespace k3t {
+hipError_t pack_slots(hipStream_t st, const uint32_t *alnLen, uint64_t n, uint64_t *bsum, uint64_t base, const uint8_t *slotA,
+                      const uint8_t *slotB, uint32_t stride, uint64_t *off, uint8_t *outA, uint8_t *outB);
+size_t pack_bsum_bytes(uint64_t n);
+} // namespace k3t
+} // namespace polyhip
+
 // ---- one-wave-per-pair exact score pass (sw_wave.hip): the packed pass's tie list and small batches ----
 namespace polyhip {
 namespace k3w {

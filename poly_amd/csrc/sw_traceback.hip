@@ -3405,6 +3405,15 @@ int polyhip_sw_align_batch_packed(const polyhip_scoring *sc, const uint8_t *A, c
 
 } // extern "C"
 
+// the compaction above for the affine entry points (sw_affine.hip), whose strings leave their slots the same way
+hipError_t polyhip::k3t::pack_slots(hipStream_t st, const uint32_t *alnLen, uint64_t n, uint64_t *bsum, uint64_t base,
+                                    const uint8_t *slotA, const uint8_t *slotB, uint32_t stride, uint64_t *off, uint8_t *outA,
+                                    uint8_t *outB)
+{
+    return pack_strings(st, alnLen, n, bsum, base, slotA, slotB, stride, off, outA, outB, nullptr);
+}
+size_t polyhip::k3t::pack_bsum_bytes(uint64_t n) { return ((n + k3t::PACK_BLOCK - 1) / k3t::PACK_BLOCK + 2) * 8; }
+
 
 extern "C" {
 
