@@ -942,6 +942,57 @@ int polyhip_map_reads(const polyhip_bwt *h, const polyhip_scoring *sc,
                       uint32_t *read_end, uint32_t *err, uint8_t *alnA, uint8_t *alnB,
                       uint64_t *alnOff, uint64_t aln_capacity);
 int polyhip_map_last_info(polyhip_map_info *info);
+/* ---- read mapping with affine gaps in the extension (Gotoh) ---- */
+/*
+ * polyhip_map_reads_affine is polyhip_map_reads with steps 5 and 6 changed as follows; steps 1-4 (strands, seeds,
+ * clusters, candidates and their ranks) are unchanged, word for word.
+ *  5. every kept candidate is extended with SmithWatermanAffine(q, T[lo, hi)), as polyhip_sw_affine_align_batch_packed
+ *     defines it: the table is the scoring handle's, gap_open and gap_extend are as defined there, the handle's own gap is
+ *     ignored; the argmax is the first maximum in row-major order; the traceback has three states (diagonal, then F, then
+ *     E) and inside a gap prefers opening over extending.
+ *  6. unchanged in meaning: the alphabet error of the lowest such rank; best = the highest score, ties to the lowest
+ *     rank; mapped iff score >= min_score; second, flags, votes, ref_*, read_* and the strings as before.  Only the
+ *     winner's strings are ever needed, so the traceback runs for each mapped read's winning candidate only: the score
+ *     pass runs on all kept candidates, the winner is picked from scores, errs and ranks, then the winner is traced.
+ *     ref_start / read_start come from the winner's strings, so the traceback also runs when alnA == NULL.
+ * With gap_open == gap_extend == g every output equals polyhip_map_reads with a handle whose gap is g.
+ * work_limit: the most device workspace, in bytes, the call may carve its per-chunk arrays from.  0 = the default, which
+ * is polyhip_map_reads': the whole batch, capped at 8 GiB.  A smaller value makes the call loop over chunks of reads
+ * (each a multiple of 256) with identical outputs; a value below what one chunk of min(nreads, 256) reads needs is
+ * POLYHIP_ERR_INVALID, and the message says how many bytes that chunk needs.  The workspace holds every per-chunk array
+ * of the call: seeds, hits, candidates, the pair batch, the score pass's band scratch, the winners' compact batch, their
+ * string slots, and the direction bits of one traceback sub-chunk.  Direction bits are sized per winner from the largest
+ * window (max_len rows, max_len + 3 * band columns) and at most 1 GiB of them are held at once: the winners of a chunk of
+ * reads are traced in sub-chunks (POLYHIP_SWA_CHUNK_PAIRS=<n> in the environment forces the sub-chunk size, as for
+ * polyhip_sw_affine_align_batch_packed: a testing aid).  A chunk of reads without a winner launches no traceback.
+ * Errors, in this order: everything polyhip_map_reads checks, in its order and with its messages (NULL arguments and
+ * offsets included when nreads > 0); !(gap_open <= gap_extend <= -1) is POLYHIP_ERR_UNSUPPORTED; absmax * (max_len +
+ * (max_len + 3 * band)) >= 2^30 with absmax = max(|smin|, |smax|, |gap_open|) is POLYHIP_ERR_UNSUPPORTED (the int32 cell
+ * range of the affine kernel at the mapper's largest window).  String capacity behaves as in polyhip_map_reads: a short
+ * aln_capacity returns POLYHIP_ERR_INVALID after filling everything else, alnOff[nreads] = the bytes needed.
+ * nreads == 0 is an empty, successful call.  The call runs on the index's device, on the handle's stream; the device list
+ * does not apply.  There is no device-pointer flavour.
+ * polyhip_map_affine_last_info: the calling thread's last polyhip_map_reads_affine.  The first six counters and chunks are
+ * as polyhip_map_info; pairs_traced = candidates whose traceback ran (== reads_mapped in every call); tb_cells = cell
+ * updates of the traceback windows (endA * window columns over the winners); tb_chunks = traceback launches summed over
+ * the chunks of reads.
+ */
+typedef struct polyhip_map_affine_info {
+    uint64_t seeds, seeds_over_max_occ, hits, clusters, pairs_aligned, reads_mapped;
+    uint64_t pairs_traced;
+    uint64_t tb_cells;
+    uint32_t chunks;
+    uint32_t tb_chunks;
+} polyhip_map_affine_info;
+int polyhip_map_reads_affine(const polyhip_bwt *h, const polyhip_scoring *sc,
+                             const polyhip_map_params *params, int64_t gap_open,
+                             int64_t gap_extend, const uint8_t *reads, const uint64_t *off,
+                             uint64_t nreads, uint32_t max_len, uint64_t work_limit,
+                             int64_t *score, int64_t *second, uint32_t *flags, uint32_t *votes,
+                             uint32_t *ref_start, uint32_t *ref_end, uint32_t *read_start,
+                             uint32_t *read_end, uint32_t *err, uint8_t *alnA, uint8_t *alnB,
+                             uint64_t *alnOff, uint64_t aln_capacity);
+int polyhip_map_affine_last_info(polyhip_map_affine_info *info);
 
 /* ---- R1: the path's one collective -- all-gather of per-rank sketches (RCCL over xGMI) ---- */
 /*

@@ -19,7 +19,16 @@
 //   polyhip_sw_align_batch_dev             the existing per-pair-B SmithWaterman, strings in fixed-stride slots
 //   map_reduce_kernel   one wave per read: first error, best and second score, coordinates from the strings' gap counts
 //   map_strings_kernel  the chosen pair's strings packed behind the previous chunk's
+// polyhip_map_reads_affine (Gotoh's affine gaps in the extension) shares everything up to the gather, then:
+//   k3a::score_pass     the affine score pass (sw_affine.h) on all pairs
+//   map_reduce_kernel<true>   the same reduction without the strings' part; a flag per mapped read
+//   scan_excl           read -> winner slots; the winners' count comes back to the host
+//   map_winners_kernel / map_wgather_kernel   the winners' scores, end cells and sequences as a compact batch
+//   k3a::traceback_pass the affine traceback of the winners only, in sub-chunks whose direction words fit the cap
+//   map_finish_kernel   ref_start / read_start from the winner's strings, string lengths, traced cells
+//   map_strings_kernel  as above, from the winners' slots
 #include "bwt_index.h"
+#include "sw_affine.h"
 #include "sw_scoring.h"
 
 namespace polyhip {
@@ -38,7 +47,7 @@ struct MapShape {
     uint64_t n;       // text length
 };
 
-enum { CNT_SEEDS = 0, CNT_OVER = 1, CNT_CLUSTERS = 2, CNT_MAPPED = 3, CNT_N = 4 };
+enum { CNT_SEEDS = 0, CNT_OVER = 1, CNT_CLUSTERS = 2, CNT_MAPPED = 3, CNT_TBCELLS = 4, CNT_N = 5 };
 
 // transform.complementTable (transform.go:78-109): IUPAC letters in both cases, every other byte -> 0x00
 __device__ __forceinline__ uint32_t dna_complement(uint32_t b)
@@ -260,6 +269,9 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
 }
 
 // One wave per read, lane i = its candidate of rank i.  slen / best: the chosen pair's string length (0 unmapped) and index.
+// AFFINE: no strings exist yet: ref_start / read_start and slen are left to map_finish_kernel (0 here, which is what an
+// unmapped read keeps), and wmap[r] = 1 for a mapped read.
+template <bool AFFINE>
 __global__ __launch_bounds__(BT) void map_reduce_kernel(const uint32_t *__restrict__ pfirst, const uint64_t *__restrict__ off, uint64_t nreads,
                                                         MapShape g, int64_t min_score, const int64_t *__restrict__ pscore,
                                                         const uint32_t *__restrict__ pendA, const uint32_t *__restrict__ pendB,
@@ -270,7 +282,8 @@ __global__ __launch_bounds__(BT) void map_reduce_kernel(const uint32_t *__restri
                                                         int64_t *__restrict__ o_second, uint32_t *__restrict__ o_flags,
                                                         uint32_t *__restrict__ o_votes, uint32_t *__restrict__ o_rs, uint32_t *__restrict__ o_re,
                                                         uint32_t *__restrict__ o_qs, uint32_t *__restrict__ o_qe, uint32_t *__restrict__ o_err,
-                                                        uint64_t *__restrict__ slen, uint32_t *__restrict__ best, unsigned long long *__restrict__ cnt)
+                                                        uint64_t *__restrict__ slen, uint32_t *__restrict__ best, uint32_t *__restrict__ wmap,
+                                                        unsigned long long *__restrict__ cnt)
 {
     const int lane = threadIdx.x & 63;
     uint32_t nmapped = 0;
@@ -302,7 +315,7 @@ __global__ __launch_bounds__(BT) void map_reduce_kernel(const uint32_t *__restri
         const bool mapped = nc > 0 && err == 0 && bs >= min_score;
         uint32_t len = 0, ga = 0, gb = 0;
         const uint32_t bp = p0 + (uint32_t)bi;
-        if (mapped) {
+        if (!AFFINE && mapped) {
             len = plen[bp];
             const uint8_t *sa_ = slotA + (uint64_t)bp * stride + (stride - len), *sb_ = slotB + (uint64_t)bp * stride + (stride - len);
             for (uint32_t i = lane; i < len; i += 64) {
@@ -326,6 +339,8 @@ __global__ __launch_bounds__(BT) void map_reduce_kernel(const uint32_t *__restri
             o_err[r] = err;
             slen[r] = len;
             best[r] = bp;
+            if (AFFINE)
+                wmap[r] = mapped;
             nmapped += mapped;
         }
     }
@@ -363,6 +378,94 @@ __global__ void map_advance_kernel(uint64_t *__restrict__ base, const uint64_t *
     }
 }
 
+// ---- the affine path's own kernels ----------------------------------------------------------------------------------------
+// One lane per read: a mapped read's winning pair becomes pair wfirst[r] of the compact batch the traceback runs on
+__global__ __launch_bounds__(BT) void map_winners_kernel(const uint32_t *__restrict__ wfirst, const uint32_t *__restrict__ best,
+                                                         uint64_t nreads, const uint64_t *__restrict__ offA, const uint64_t *__restrict__ offB,
+                                                         const int64_t *__restrict__ pscore, const uint32_t *__restrict__ pendA,
+                                                         const uint32_t *__restrict__ pendB, uint32_t *__restrict__ wsrc,
+                                                         uint64_t *__restrict__ wlenA, uint64_t *__restrict__ wlenB,
+                                                         int64_t *__restrict__ wscore, uint32_t *__restrict__ wendA,
+                                                         uint32_t *__restrict__ wendB, uint32_t *__restrict__ werr)
+{
+    for (uint64_t r = blockIdx.x * (uint64_t)BT + threadIdx.x; r < nreads; r += (uint64_t)gridDim.x * BT) {
+        const uint32_t q = wfirst[r];
+        if (wfirst[r + 1] == q)
+            continue;
+        const uint32_t p = best[r];
+        wsrc[q] = p;
+        wlenA[q] = offA[p + 1] - offA[p];
+        wlenB[q] = offB[p + 1] - offB[p];
+        wscore[q] = pscore[p];
+        wendA[q] = pendA[p];
+        wendB[q] = pendB[p];
+        werr[q] = 0u; // a mapped read has no candidate with an error
+    }
+}
+
+// One wave per winner: its A and B copied out of the pair batch
+__global__ __launch_bounds__(BT) void map_wgather_kernel(const uint32_t *__restrict__ wsrc, uint64_t nwin, const uint64_t *__restrict__ offA,
+                                                         const uint64_t *__restrict__ offB, const uint8_t *__restrict__ A,
+                                                         const uint8_t *__restrict__ B, const uint64_t *__restrict__ woffA,
+                                                         const uint64_t *__restrict__ woffB, uint8_t *__restrict__ wA, uint8_t *__restrict__ wB)
+{
+    const int lane = threadIdx.x & 63;
+    for (uint64_t q = (blockIdx.x * (uint64_t)BT + threadIdx.x) / 64; q < nwin; q += (uint64_t)gridDim.x * (BT / 64)) {
+        const uint32_t p = wsrc[q];
+        const uint64_t la = woffA[q + 1] - woffA[q], lb = woffB[q + 1] - woffB[q];
+        const uint8_t *sa_ = A + offA[p], *sb_ = B + offB[p];
+        uint8_t *da = wA + woffA[q], *db = wB + woffB[q];
+        for (uint64_t i = lane; i < la; i += 64)
+            da[i] = sa_[i];
+        for (uint64_t i = lane; i < lb; i += 64)
+            db[i] = sb_[i];
+    }
+}
+
+// every pair of a traceback sub-chunk owns the direction words of the largest window: no planning from scores
+__global__ __launch_bounds__(BT) void map_diroff_kernel(uint64_t *__restrict__ dirOff, uint64_t n, uint64_t words)
+{
+    for (uint64_t q = blockIdx.x * (uint64_t)BT + threadIdx.x; q < n; q += (uint64_t)gridDim.x * BT)
+        dirOff[q] = q * words;
+}
+
+// One wave per read, after the winners' traceback: coordinates from the strings' gap counts, the string's length, and
+// best[r] = the winner's slot for map_strings_kernel.  An unmapped read keeps what map_reduce_kernel<true> wrote.
+__global__ __launch_bounds__(BT) void map_finish_kernel(const uint32_t *__restrict__ wfirst, uint64_t nreads, const uint32_t *__restrict__ wlen,
+                                                        const uint8_t *__restrict__ slotA, const uint8_t *__restrict__ slotB, uint32_t stride,
+                                                        const int64_t *__restrict__ wscore, const uint32_t *__restrict__ wendA,
+                                                        const uint32_t *__restrict__ wendB, int smax, int ge,
+                                                        const uint32_t *__restrict__ o_re, const uint32_t *__restrict__ o_qe,
+                                                        uint32_t *__restrict__ o_rs, uint32_t *__restrict__ o_qs, uint64_t *__restrict__ slen,
+                                                        uint32_t *__restrict__ best, unsigned long long *__restrict__ cnt)
+{
+    const int lane = threadIdx.x & 63;
+    unsigned long long cells = 0;
+    for (uint64_t r = (blockIdx.x * (uint64_t)BT + threadIdx.x) / 64; r < nreads; r += (uint64_t)gridDim.x * (BT / 64)) {
+        const uint32_t q = wfirst[r];
+        if (wfirst[r + 1] == q)
+            continue;
+        const uint32_t len = wlen[q];
+        const uint8_t *sa_ = slotA + (uint64_t)q * stride + (stride - len), *sb_ = slotB + (uint64_t)q * stride + (stride - len);
+        uint32_t ga = 0, gb = 0;
+        for (uint32_t i = lane; i < len; i += 64) {
+            ga += sa_[i] != '-';
+            gb += sb_[i] != '-';
+        }
+        ga = wave_sum(ga);
+        gb = wave_sum(gb);
+        if (lane == 0) {
+            o_rs[r] = o_re[r] - gb;
+            o_qs[r] = o_qe[r] - ga;
+            slen[r] = len;
+            best[r] = q;
+            cells += (unsigned long long)wendA[q] * k3a::window_cols(wendA[q], wendB[q], wscore[q], smax, ge);
+        }
+    }
+    if (lane == 0 && cells)
+        atomicAdd(cnt + CNT_TBCELLS, cells);
+}
+
 // ---- the workspace of a chunk of nr reads ---------------------------------------------------------------------------------
 struct MapWork {
     unsigned long long *cnt; // CNT_N counters, then the strings' running total
@@ -382,11 +485,25 @@ struct MapWork {
     uint32_t *best;
     uint64_t hcap, pcap;
     uint32_t lenB, stride;
+    // the affine path's (instead of sw_work / tb_work; slotA / slotB hold the winners' strings only)
+    void *band;
+    unsigned blocks; // workgroups the band scratch is sized for
+    uint32_t *wfirst, *wsrc, *wendA, *wendB, *werr, *wlen, *dir;
+    uint64_t *woffA, *woffB, *dirOff;
+    uint8_t *wA, *wB;
+    int64_t *wscore;
+    uint64_t sub, dwords; // pairs per traceback sub-chunk; direction words of each
+};
+
+// polyhip_map_reads_affine's gaps and what k3a::choose() fixed for the call
+struct MapAffine {
+    int go, ge;
+    k3a::Choice c;
 };
 
 // carves the chunk's arrays out of `base` (nullptr: sizes only) and returns the bytes; 0 = the chunk cannot be held at all
 // (2^31 hits or more)
-size_t map_carve(const polyhip_scoring *sc, const MapShape &g, uint64_t nr, uint8_t *base, MapWork *out)
+size_t map_carve(const polyhip_scoring *sc, const MapShape &g, const MapAffine *af, uint64_t nr, uint8_t *base, MapWork *out)
 {
     MapWork w{};
     const uint64_t slots = nr * g.strands * g.ns;
@@ -395,7 +512,7 @@ size_t map_carve(const polyhip_scoring *sc, const MapShape &g, uint64_t nr, uint
     if (w.hcap >= (1ull << 31) || w.pcap >= (1ull << 31))
         return 0;
     w.lenB = g.max_len + 3 * g.W;
-    w.stride = polyhip_sw_traceback_stride(sc, g.max_len, w.lenB);
+    w.stride = af ? k3a::slot_stride(g.max_len, w.lenB) : polyhip_sw_traceback_stride(sc, g.max_len, w.lenB);
     const uint64_t nb = radix_blocks(std::max<uint64_t>(w.hcap, 1));
     Carve c{base};
     w.cnt = c.take<unsigned long long>(CNT_N + 1);
@@ -424,12 +541,37 @@ size_t map_carve(const polyhip_scoring *sc, const MapShape &g, uint64_t nr, uint
     w.endB = c.take<uint32_t>(w.pcap);
     w.err = c.take<uint32_t>(w.pcap);
     w.alnLen = c.take<uint32_t>(w.pcap);
-    w.slotA = c.take<uint8_t>(w.pcap * w.stride);
-    w.slotB = c.take<uint8_t>(w.pcap * w.stride);
-    w.sw_bytes = std::max<size_t>(polyhip_sw_workspace_bytes(sc, w.pcap, g.max_len, w.lenB, 0), 256);
-    w.sw_work = c.take<uint8_t>(w.sw_bytes);
-    w.tb_bytes = polyhip_sw_traceback_workspace_bytes(sc, std::min(w.pcap, MAP_TB_PAIRS), g.max_len, w.lenB);
-    w.tb_work = c.take<uint8_t>(w.tb_bytes);
+    if (af) {
+        // the score pass's band scratch serves the traceback too (fewer pairs, the same columns); the direction words of
+        // a sub-chunk are the worst case per pair, held under the affine call's cap
+        w.blocks = k3a::grid_blocks(af->c, std::max<uint64_t>(w.pcap, 1), w.lenB);
+        w.band = c.take<uint8_t>(k3a::band_bytes(w.blocks, w.lenB));
+        w.dwords = k3a::dir_words(g.max_len, w.lenB);
+        w.sub = std::min(std::min(af->c.chunk_pairs, af->c.dir_cap / std::max<uint64_t>(w.dwords * 4, 1)), nr);
+        w.sub = std::max<uint64_t>(w.sub, 1);
+        w.wfirst = c.take<uint32_t>(nr + 1);
+        w.wsrc = c.take<uint32_t>(nr);
+        w.woffA = c.take<uint64_t>(nr + 1);
+        w.woffB = c.take<uint64_t>(nr + 1);
+        w.wA = c.take<uint8_t>(nr * g.max_len + 64);
+        w.wB = c.take<uint8_t>(nr * w.lenB + 64);
+        w.wscore = c.take<int64_t>(nr);
+        w.wendA = c.take<uint32_t>(nr);
+        w.wendB = c.take<uint32_t>(nr);
+        w.werr = c.take<uint32_t>(nr);
+        w.wlen = c.take<uint32_t>(nr);
+        w.dirOff = c.take<uint64_t>(w.sub);
+        w.dir = c.take<uint32_t>(w.sub * w.dwords + 4);
+        w.slotA = c.take<uint8_t>(nr * w.stride);
+        w.slotB = c.take<uint8_t>(nr * w.stride);
+    } else {
+        w.slotA = c.take<uint8_t>(w.pcap * w.stride);
+        w.slotB = c.take<uint8_t>(w.pcap * w.stride);
+        w.sw_bytes = std::max<size_t>(polyhip_sw_workspace_bytes(sc, w.pcap, g.max_len, w.lenB, 0), 256);
+        w.sw_work = c.take<uint8_t>(w.sw_bytes);
+        w.tb_bytes = polyhip_sw_traceback_workspace_bytes(sc, std::min(w.pcap, MAP_TB_PAIRS), g.max_len, w.lenB);
+        w.tb_work = c.take<uint8_t>(w.tb_bytes);
+    }
     w.soff = c.take<uint64_t>(nr + 1);
     w.best = c.take<uint32_t>(nr);
     if (out)
@@ -438,10 +580,10 @@ size_t map_carve(const polyhip_scoring *sc, const MapShape &g, uint64_t nr, uint
 }
 
 // reads per chunk that `bytes` hold: every read when they all fit, else a multiple of MAP_CHUNK (0: not even one)
-uint64_t map_chunk_reads(const polyhip_scoring *sc, const MapShape &g, uint64_t nreads, size_t bytes)
+uint64_t map_chunk_reads(const polyhip_scoring *sc, const MapShape &g, const MapAffine *af, uint64_t nreads, size_t bytes)
 {
     auto fits = [&](uint64_t nr) {
-        const size_t need = map_carve(sc, g, nr, nullptr, nullptr);
+        const size_t need = map_carve(sc, g, af, nr, nullptr, nullptr);
         return need != 0 && need <= bytes;
     };
     if (fits(nreads))
@@ -488,6 +630,7 @@ MapShape make_shape(const polyhip_map_params *p, uint64_t n, uint32_t max_len)
 }
 
 thread_local polyhip_map_info t_info{};
+thread_local polyhip_map_affine_info t_ainfo{};
 
 int validate(const char *who, const polyhip_bwt *hp, const polyhip_scoring *sc, const polyhip_map_params *p, uint32_t max_len)
 {
@@ -513,32 +656,51 @@ struct MapOut {
     uint64_t capacity;
 };
 
-// The call on device pointers, on the index's device (the caller has entered it).  *needed = the strings' bytes.
-int map_run(const BwtHandle *h, const polyhip_scoring *sc, const polyhip_map_params *p, const uint8_t *d_reads, const uint64_t *d_off,
-            uint64_t nreads, uint32_t max_len, const MapOut &o, void *d_work, size_t work_bytes, hipStream_t st, uint64_t *needed)
+// what a call leaves for polyhip_map_last_info, or (af) for polyhip_map_affine_last_info
+void keep_info(const polyhip_map_info &i, const MapAffine *af, uint64_t traced, uint64_t tb_cells, uint32_t tb_chunks)
 {
-    const char *who = "polyhip_map_reads";
+    if (!af) {
+        t_info = i;
+        return;
+    }
+    t_ainfo = polyhip_map_affine_info{i.seeds, i.seeds_over_max_occ, i.hits, i.clusters, i.pairs_aligned, i.reads_mapped, traced, tb_cells,
+                                      i.chunks, tb_chunks};
+}
+
+// The call on device pointers, on the index's device (the caller has entered it).  *needed = the strings' bytes.
+// af: the extension has affine gaps and only the winners are traced (polyhip_map_reads_affine).
+int map_run(const BwtHandle *h, const polyhip_scoring *sc, const polyhip_map_params *p, const MapAffine *af, const uint8_t *d_reads,
+            const uint64_t *d_off, uint64_t nreads, uint32_t max_len, const MapOut &o, void *d_work, size_t work_bytes, hipStream_t st,
+            uint64_t *needed)
+{
+    const char *who = af ? "polyhip_map_reads_affine" : "polyhip_map_reads";
     polyhip_map_info info{};
+    uint64_t traced = 0;
+    uint32_t tb_chunks = 0;
     *needed = 0;
     const bool strings = o.alnA != nullptr;
     if (nreads == 0) {
         if (o.alnOff)
             PH_HIP(hipMemsetAsync(o.alnOff, 0, sizeof(uint64_t), st));
-        t_info = info;
+        keep_info(info, af, 0, 0, 0);
         return POLYHIP_OK;
     }
     PH_REQUIRE(d_off && o.score && o.second && o.flags && o.votes && o.ref_start && o.ref_end && o.read_start && o.read_end && o.err,
                "%s: null argument", who);
     PH_REQUIRE(!strings || (o.alnB && o.alnOff), "%s: alnA without alnB / alnOff", who);
     const MapShape g = make_shape(p, h->n, max_len);
-    const uint64_t per = map_chunk_reads(sc, g, nreads, d_work ? work_bytes : 0);
+    const uint64_t per = map_chunk_reads(sc, g, af, nreads, d_work ? work_bytes : 0);
     PH_REQUIRE(per > 0, "%s: a workspace of %zu bytes does not hold a chunk of %llu reads (%zu bytes)", who, work_bytes,
                (unsigned long long)std::min<uint64_t>(nreads, MAP_CHUNK),
-               map_carve(sc, g, std::min<uint64_t>(nreads, MAP_CHUNK), nullptr, nullptr));
+               map_carve(sc, g, af, std::min<uint64_t>(nreads, MAP_CHUNK), nullptr, nullptr));
     MapWork w;
-    (void)map_carve(sc, g, per, static_cast<uint8_t *>(d_work), &w);
+    (void)map_carve(sc, g, af, per, static_cast<uint8_t *>(d_work), &w);
     uint64_t *sbase = reinterpret_cast<uint64_t *>(w.cnt + CNT_N);
     PH_HIP(hipMemsetAsync(w.cnt, 0, (CNT_N + 1) * sizeof(unsigned long long), st));
+    if (af) {
+        hipLaunchKernelGGL(map_diroff_kernel, dim3(grid_for(w.sub)), dim3(BT), 0, st, w.dirOff, w.sub, w.dwords);
+        PH_HIP(hipGetLastError());
+    }
     SyncOnExit sync(st); // counts are read back into locals
     for (uint64_t r0 = 0; r0 < nreads; r0 += per, ++info.chunks) {
         const uint64_t nr = std::min(per, nreads - r0), slots = nr * g.strands * g.ns;
@@ -585,15 +747,57 @@ int map_run(const BwtHandle *h, const polyhip_scoring *sc, const polyhip_map_par
             hipLaunchKernelGGL(map_gather_kernel, dim3(grid_for((uint64_t)npairs * 64)), dim3(BT), 0, st, d_reads, off, h->d_text, w.pread,
                                w.pfirst, w.cstrand, w.clo, g.C, (uint64_t)npairs, w.offA, w.offB, w.A, w.B);
             PH_HIP(hipGetLastError());
-            if (int rc = polyhip_sw_align_batch_dev(sc, w.A, w.offA, npairs, g.max_len, w.B, w.offB, w.lenB, w.score, w.endA, w.endB, w.err,
-                                                    w.slotA, w.slotB, w.alnLen, w.stride, w.sw_work, w.sw_bytes, w.tb_work, w.tb_bytes, st))
+            if (af) {
+                if (int rc = k3a::score_pass(sc, af->c, af->go, af->ge, w.A, w.offA, npairs, w.B, w.offB, w.lenB, w.score, w.endA, w.endB,
+                                             w.err, w.band, k3a::grid_blocks(af->c, npairs, w.lenB), st))
+                    return rc;
+            } else if (int rc = polyhip_sw_align_batch_dev(sc, w.A, w.offA, npairs, g.max_len, w.B, w.offB, w.lenB, w.score, w.endA, w.endB,
+                                                           w.err, w.slotA, w.slotB, w.alnLen, w.stride, w.sw_work, w.sw_bytes, w.tb_work,
+                                                           w.tb_bytes, st)) {
                 return rc;
+            }
         }
-        hipLaunchKernelGGL(map_reduce_kernel, dim3(grid_for(nr * 64)), dim3(BT), 0, st, w.pfirst, off, nr, g, p->min_score, w.score, w.endA,
-                           w.endB, w.err, w.alnLen, w.slotA, w.slotB, w.stride, w.cvotes, w.cstrand, w.clo, o.score + r0, o.second + r0,
-                           o.flags + r0, o.votes + r0, o.ref_start + r0, o.ref_end + r0, o.read_start + r0, o.read_end + r0, o.err + r0,
-                           w.soff, w.best, w.cnt);
-        PH_HIP(hipGetLastError());
+        if (af) {
+            // the winner of every read from scores, errs and ranks; then the strings of the winners alone
+            hipLaunchKernelGGL(map_reduce_kernel<true>, dim3(grid_for(nr * 64)), dim3(BT), 0, st, w.pfirst, off, nr, g, p->min_score, w.score,
+                               w.endA, w.endB, w.err, w.alnLen, w.slotA, w.slotB, w.stride, w.cvotes, w.cstrand, w.clo, o.score + r0,
+                               o.second + r0, o.flags + r0, o.votes + r0, o.ref_start + r0, o.ref_end + r0, o.read_start + r0,
+                               o.read_end + r0, o.err + r0, w.soff, w.best, w.wfirst, w.cnt);
+            PH_HIP(hipGetLastError());
+            uint32_t nwin = 0;
+            PH_HIP(scan_excl<uint32_t>(w.wfirst, w.wfirst, nr, w.scratch, st));
+            PH_HIP(hipMemcpyAsync(&nwin, w.wfirst + nr, sizeof nwin, hipMemcpyDeviceToHost, st));
+            PH_HIP(hipStreamSynchronize(st));
+            traced += nwin;
+            if (nwin) { // a chunk without a winner launches no traceback
+                hipLaunchKernelGGL(map_winners_kernel, dim3(grid_for(nr)), dim3(BT), 0, st, w.wfirst, w.best, nr, w.offA, w.offB, w.score,
+                                   w.endA, w.endB, w.wsrc, w.woffA, w.woffB, w.wscore, w.wendA, w.wendB, w.werr);
+                PH_HIP(hipGetLastError());
+                PH_HIP(scan_excl<uint64_t>(w.woffA, w.woffA, nwin, w.scratch, st));
+                PH_HIP(scan_excl<uint64_t>(w.woffB, w.woffB, nwin, w.scratch, st));
+                hipLaunchKernelGGL(map_wgather_kernel, dim3(grid_for((uint64_t)nwin * 64)), dim3(BT), 0, st, w.wsrc, (uint64_t)nwin, w.offA,
+                                   w.offB, w.A, w.B, w.woffA, w.woffB, w.wA, w.wB);
+                PH_HIP(hipGetLastError());
+                for (uint64_t i0 = 0; i0 < nwin; i0 += w.sub, ++tb_chunks) {
+                    const uint64_t m = std::min<uint64_t>(w.sub, nwin - i0);
+                    if (int rc = k3a::traceback_pass(sc, af->c, af->go, af->ge, w.wA, w.woffA + i0, m, w.wB, w.woffB + i0, w.lenB,
+                                                     w.wscore + i0, w.wendA + i0, w.wendB + i0, w.werr + i0, w.dirOff, w.dir, w.band,
+                                                     w.lenB, k3a::grid_blocks(af->c, m, w.lenB), w.slotA + i0 * w.stride,
+                                                     w.slotB + i0 * w.stride, w.wlen + i0, w.stride, st))
+                        return rc;
+                }
+                hipLaunchKernelGGL(map_finish_kernel, dim3(grid_for(nr * 64)), dim3(BT), 0, st, w.wfirst, nr, w.wlen, w.slotA, w.slotB,
+                                   w.stride, w.wscore, w.wendA, w.wendB, (int)sc->smax, af->ge, o.ref_end + r0, o.read_end + r0,
+                                   o.ref_start + r0, o.read_start + r0, w.soff, w.best, w.cnt);
+                PH_HIP(hipGetLastError());
+            }
+        } else {
+            hipLaunchKernelGGL(map_reduce_kernel<false>, dim3(grid_for(nr * 64)), dim3(BT), 0, st, w.pfirst, off, nr, g, p->min_score, w.score,
+                               w.endA, w.endB, w.err, w.alnLen, w.slotA, w.slotB, w.stride, w.cvotes, w.cstrand, w.clo, o.score + r0,
+                               o.second + r0, o.flags + r0, o.votes + r0, o.ref_start + r0, o.ref_end + r0, o.read_start + r0,
+                               o.read_end + r0, o.err + r0, w.soff, w.best, (uint32_t *)nullptr, w.cnt);
+            PH_HIP(hipGetLastError());
+        }
         if (strings) {
             PH_HIP(scan_excl<uint64_t>(w.soff, w.soff, nr, w.scratch, st));
             hipLaunchKernelGGL(map_strings_kernel, dim3(grid_for(nr * 64)), dim3(BT), 0, st, w.soff, w.best, nr, w.slotA, w.slotB, w.stride,
@@ -610,7 +814,7 @@ int map_run(const BwtHandle *h, const polyhip_scoring *sc, const polyhip_map_par
     info.seeds_over_max_occ = cnt[CNT_OVER];
     info.clusters = cnt[CNT_CLUSTERS];
     info.reads_mapped = cnt[CNT_MAPPED];
-    t_info = info;
+    keep_info(info, af, traced, cnt[CNT_TBCELLS], tb_chunks);
     *needed = cnt[CNT_N];
     if (strings && *needed > o.capacity)
         return set_error(POLYHIP_ERR_INVALID, "%s: the aligned strings need %llu bytes, the buffers hold %llu", who,
@@ -619,76 +823,75 @@ int map_run(const BwtHandle *h, const polyhip_scoring *sc, const polyhip_map_par
 }
 
 // the whole-batch workspace, capped: what map_run cuts its chunks from
-size_t map_workspace(const polyhip_scoring *sc, const MapShape &g, uint64_t nreads)
+size_t map_workspace(const polyhip_scoring *sc, const MapShape &g, const MapAffine *af, uint64_t nreads)
 {
     if (nreads == 0)
         return 0;
     const uint64_t padded = nreads <= MAP_CHUNK ? nreads : (nreads + MAP_CHUNK - 1) / MAP_CHUNK * MAP_CHUNK;
-    const size_t all = map_carve(sc, g, padded, nullptr, nullptr);
+    const size_t all = map_carve(sc, g, af, padded, nullptr, nullptr);
     if (all != 0 && all <= MAP_WORK_CAP)
         return all;
-    const uint64_t per = std::max<uint64_t>(map_chunk_reads(sc, g, padded, MAP_WORK_CAP), MAP_CHUNK);
-    return map_carve(sc, g, per, nullptr, nullptr);
+    const uint64_t per = std::max<uint64_t>(map_chunk_reads(sc, g, af, padded, MAP_WORK_CAP), MAP_CHUNK);
+    return map_carve(sc, g, af, per, nullptr, nullptr);
 }
 
-} // namespace
-} // namespace polyhip
-
-using namespace polyhip;
-
-extern "C" {
-
-size_t polyhip_map_workspace_bytes(const polyhip_bwt *hp, const polyhip_scoring *sc, const polyhip_map_params *p, uint64_t nreads,
-                                   uint32_t max_len)
+// The host-pointer calls: polyhip_map_reads (gaps == nullptr) and polyhip_map_reads_affine (gaps = {open, extend}).
+// work_limit: the most workspace the call may use (0: the whole batch, capped).
+int map_host(const char *who, const polyhip_bwt *hp, const polyhip_scoring *sc, const polyhip_map_params *p, const int64_t *gaps,
+             uint64_t work_limit, const uint8_t *reads, const uint64_t *off, uint64_t nreads, uint32_t max_len, int64_t *score,
+             int64_t *second, uint32_t *flags, uint32_t *votes, uint32_t *ref_start, uint32_t *ref_end, uint32_t *read_start,
+             uint32_t *read_end, uint32_t *err, uint8_t *alnA, uint8_t *alnB, uint64_t *alnOff, uint64_t aln_capacity)
 {
-    if (!hp || !sc || check_params(p) || max_len > MAP_MAX_LEN || p->band > MAP_MAX_BAND)
-        return 0;
-    return map_workspace(sc, make_shape(p, as_h(hp)->n, max_len), nreads);
-}
-
-int polyhip_map_reads_dev(const polyhip_bwt *hp, const polyhip_scoring *sc, const polyhip_map_params *p, const uint8_t *d_reads,
-                          const uint64_t *d_off, uint64_t nreads, uint32_t max_len, int64_t *d_score, int64_t *d_second, uint32_t *d_flags,
-                          uint32_t *d_votes, uint32_t *d_ref_start, uint32_t *d_ref_end, uint32_t *d_read_start, uint32_t *d_read_end,
-                          uint32_t *d_err, uint8_t *d_alnA, uint8_t *d_alnB, uint64_t *d_alnOff, uint64_t aln_capacity, void *d_work,
-                          size_t work_bytes, polyhip_stream_t stream)
-{
-    if (int rc = validate("polyhip_map_reads_dev", hp, sc, p, max_len))
-        return rc;
-    const BwtHandle *h = as_h(hp);
-    DeviceScope ds;
-    PH_HIP(ds.enter(h->dev));
-    const MapOut o{d_score, d_second, d_flags, d_votes, d_ref_start, d_ref_end, d_read_start, d_read_end, d_err, d_alnA, d_alnB, d_alnOff,
-                   aln_capacity};
-    uint64_t needed = 0;
-    return map_run(h, sc, p, d_reads, d_off, nreads, max_len, o, d_work, work_bytes, as_stream(stream), &needed);
-}
-
-int polyhip_map_reads(const polyhip_bwt *hp, const polyhip_scoring *sc, const polyhip_map_params *p, const uint8_t *reads,
-                      const uint64_t *off, uint64_t nreads, uint32_t max_len, int64_t *score, int64_t *second, uint32_t *flags,
-                      uint32_t *votes, uint32_t *ref_start, uint32_t *ref_end, uint32_t *read_start, uint32_t *read_end, uint32_t *err,
-                      uint8_t *alnA, uint8_t *alnB, uint64_t *alnOff, uint64_t aln_capacity)
-{
-    const char *who = "polyhip_map_reads";
     if (int rc = validate(who, hp, sc, p, max_len))
         return rc;
     const bool strings = alnA != nullptr;
+    uint64_t nbytes = 0;
+    if (nreads) {
+        PH_REQUIRE(off && score && second && flags && votes && ref_start && ref_end && read_start && read_end && err, "%s: null argument",
+                   who);
+        PH_REQUIRE(!strings || (alnB && alnOff), "%s: alnA without alnB / alnOff", who);
+        for (uint64_t i = 0; i < nreads; ++i)
+            PH_REQUIRE(off[i] <= off[i + 1], "%s: offsets are not ascending at %llu", who, (unsigned long long)i);
+        nbytes = off[nreads] - off[0];
+        PH_REQUIRE(reads || nbytes == 0, "%s: null read buffer", who);
+    }
+    MapAffine aff{};
+    const MapAffine *af = nullptr;
+    if (gaps) {
+        const int64_t go = gaps[0], ge = gaps[1];
+        if (!(go <= ge && ge <= -1))
+            return set_error(POLYHIP_ERR_UNSUPPORTED, "%s: gap_open %lld, gap_extend %lld: need gap_open <= gap_extend <= -1", who,
+                             (long long)go, (long long)ge);
+        // the affine kernel's int32 cells at the mapper's largest window
+        const int64_t absmax = std::max<int64_t>(std::max<int64_t>(std::llabs((long long)sc->smin), std::llabs((long long)sc->smax)), -go);
+        const int64_t span = (int64_t)max_len + ((int64_t)max_len + 3 * (int64_t)p->band), range = 1ll << 30;
+        if (absmax >= range || absmax * span >= range)
+            return set_error(POLYHIP_ERR_UNSUPPORTED,
+                             "%s: scores could leave the int32 cells (|s|max %lld, max_len %u, band %u: |s|max * (2 * max_len + 3 * band) "
+                             "must stay below 2^30)",
+                             who, (long long)absmax, max_len, p->band);
+        aff.go = (int)go;
+        aff.ge = (int)ge;
+        af = &aff;
+    }
     if (nreads == 0) {
         if (alnOff)
             alnOff[0] = 0;
-        t_info = polyhip_map_info{};
+        keep_info(polyhip_map_info{}, af, 0, 0, 0);
         return POLYHIP_OK;
     }
-    PH_REQUIRE(off && score && second && flags && votes && ref_start && ref_end && read_start && read_end && err, "%s: null argument", who);
-    PH_REQUIRE(!strings || (alnB && alnOff), "%s: alnA without alnB / alnOff", who);
-    for (uint64_t i = 0; i < nreads; ++i)
-        PH_REQUIRE(off[i] <= off[i + 1], "%s: offsets are not ascending at %llu", who, (unsigned long long)i);
-    const uint64_t nbytes = off[nreads] - off[0];
-    PH_REQUIRE(reads || nbytes == 0, "%s: null read buffer", who);
     const BwtHandle *h = as_h(hp);
     DeviceScope ds;
     PH_HIP(ds.enter(h->dev));
     hipStream_t st = h->stream;
-    const size_t wb = map_workspace(sc, make_shape(p, h->n, max_len), nreads);
+    if (af) {
+        int cus = 0;
+        PH_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->dev));
+        aff.c = k3a::choose(sc, cus);
+    }
+    size_t wb = map_workspace(sc, make_shape(p, h->n, max_len), af, nreads);
+    if (work_limit && work_limit < wb)
+        wb = work_limit;
     // outputs in one block: two int64 and seven uint32 per read, then the string offsets
     DevBuf dreads, doff, dout, dA, dB, dwork;
     PH_HIP(dreads.alloc(nbytes + 64));
@@ -713,7 +916,7 @@ int polyhip_map_reads(const polyhip_bwt *hp, const polyhip_scoring *sc, const po
                    d32 + 6 * nreads, strings ? dA.as<uint8_t>() : nullptr, strings ? dB.as<uint8_t>() : nullptr, strings ? dao : nullptr,
                    aln_capacity};
     uint64_t needed = 0;
-    const int rc = map_run(h, sc, p, dreads.as<uint8_t>(), doff.as<uint64_t>(), nreads, max_len, o, dwork.p, wb, st, &needed);
+    const int rc = map_run(h, sc, p, af, dreads.as<uint8_t>(), doff.as<uint64_t>(), nreads, max_len, o, dwork.p, wb, st, &needed);
     if (rc != POLYHIP_OK && !(strings && needed > aln_capacity))
         return rc;
     // (a call whose only failure is the strings' capacity still delivers everything else)
@@ -732,6 +935,65 @@ int polyhip_map_reads(const polyhip_bwt *hp, const polyhip_scoring *sc, const po
     }
     PH_HIP(hipStreamSynchronize(st));
     return rc;
+}
+
+} // namespace
+} // namespace polyhip
+
+using namespace polyhip;
+
+extern "C" {
+
+size_t polyhip_map_workspace_bytes(const polyhip_bwt *hp, const polyhip_scoring *sc, const polyhip_map_params *p, uint64_t nreads,
+                                   uint32_t max_len)
+{
+    if (!hp || !sc || check_params(p) || max_len > MAP_MAX_LEN || p->band > MAP_MAX_BAND)
+        return 0;
+    return map_workspace(sc, make_shape(p, as_h(hp)->n, max_len), nullptr, nreads);
+}
+
+int polyhip_map_reads_dev(const polyhip_bwt *hp, const polyhip_scoring *sc, const polyhip_map_params *p, const uint8_t *d_reads,
+                          const uint64_t *d_off, uint64_t nreads, uint32_t max_len, int64_t *d_score, int64_t *d_second, uint32_t *d_flags,
+                          uint32_t *d_votes, uint32_t *d_ref_start, uint32_t *d_ref_end, uint32_t *d_read_start, uint32_t *d_read_end,
+                          uint32_t *d_err, uint8_t *d_alnA, uint8_t *d_alnB, uint64_t *d_alnOff, uint64_t aln_capacity, void *d_work,
+                          size_t work_bytes, polyhip_stream_t stream)
+{
+    if (int rc = validate("polyhip_map_reads_dev", hp, sc, p, max_len))
+        return rc;
+    const BwtHandle *h = as_h(hp);
+    DeviceScope ds;
+    PH_HIP(ds.enter(h->dev));
+    const MapOut o{d_score, d_second, d_flags, d_votes, d_ref_start, d_ref_end, d_read_start, d_read_end, d_err, d_alnA, d_alnB, d_alnOff,
+                   aln_capacity};
+    uint64_t needed = 0;
+    return map_run(h, sc, p, nullptr, d_reads, d_off, nreads, max_len, o, d_work, work_bytes, as_stream(stream), &needed);
+}
+
+int polyhip_map_reads(const polyhip_bwt *hp, const polyhip_scoring *sc, const polyhip_map_params *p, const uint8_t *reads,
+                      const uint64_t *off, uint64_t nreads, uint32_t max_len, int64_t *score, int64_t *second, uint32_t *flags,
+                      uint32_t *votes, uint32_t *ref_start, uint32_t *ref_end, uint32_t *read_start, uint32_t *read_end, uint32_t *err,
+                      uint8_t *alnA, uint8_t *alnB, uint64_t *alnOff, uint64_t aln_capacity)
+{
+    return map_host("polyhip_map_reads", hp, sc, p, nullptr, 0, reads, off, nreads, max_len, score, second, flags, votes, ref_start,
+                    ref_end, read_start, read_end, err, alnA, alnB, alnOff, aln_capacity);
+}
+
+int polyhip_map_reads_affine(const polyhip_bwt *hp, const polyhip_scoring *sc, const polyhip_map_params *p, int64_t gap_open,
+                             int64_t gap_extend, const uint8_t *reads, const uint64_t *off, uint64_t nreads, uint32_t max_len,
+                             uint64_t work_limit, int64_t *score, int64_t *second, uint32_t *flags, uint32_t *votes, uint32_t *ref_start,
+                             uint32_t *ref_end, uint32_t *read_start, uint32_t *read_end, uint32_t *err, uint8_t *alnA, uint8_t *alnB,
+                             uint64_t *alnOff, uint64_t aln_capacity)
+{
+    const int64_t gaps[2] = {gap_open, gap_extend};
+    return map_host("polyhip_map_reads_affine", hp, sc, p, gaps, work_limit, reads, off, nreads, max_len, score, second, flags, votes,
+                    ref_start, ref_end, read_start, read_end, err, alnA, alnB, alnOff, aln_capacity);
+}
+
+int polyhip_map_affine_last_info(polyhip_map_affine_info *info)
+{
+    PH_REQUIRE(info, "polyhip_map_affine_last_info: null argument");
+    *info = t_ainfo;
+    return POLYHIP_OK;
 }
 
 int polyhip_map_last_info(polyhip_map_info *info)

@@ -27,7 +27,8 @@
 //     the pair's own run of the direction workspace.  The lane then walks its three states back from (endA, endB) and
 //     writes the strings right-aligned into the pair's slots; the packing is the linear traceback's (k3t::pack_slots).
 //
-// choose() is the one place that reads the testing aid (POLYHIP_SWA_CHUNK_PAIRS) and fixes the forms that run.
+// choose() is the one place that reads the testing aid (POLYHIP_SWA_CHUNK_PAIRS) and fixes the forms that run.  The read
+// mapper (map_reads.hip) drives score_pass and traceback_pass on its own device arrays through sw_affine.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,6 +38,7 @@
 #include "common.h"
 #include "host_pipeline.h"
 
+#include "sw_affine.h"
 #include "sw_scoring.h"
 
 namespace polyhip {
@@ -47,27 +49,8 @@ constexpr int RB = 32;            // rows per band (what the compiler
 constexpr int NEG = -(1 << 30);   // -inf of E and F
 constexpr int64_t RANGE = 1ll << 30;
 
-// columns of pair's traceback window: min(endB, W_p), W_p = endA + floor((smax * endA - s) / -ge); 0: nothing to trace
-__host__ __device__ inline uint32_t window_cols(uint32_t eA, uint32_t eB, int64_t s, int smax, int ge)
-{
-    if (s < 1 || eA == 0 || eB == 0 || smax < 1)
-        return 0;
-    const uint64_t top = (uint64_t)smax * eA, g = (uint64_t)(-ge);
-    const uint64_t W = eA + (top > (uint64_t)s ? (top - (uint64_t)s) / g : 0);
-    return W < eB ? (uint32_t)W : eB;
-}
-// ... and the most bytes its strings can have: endA + min(endB, W_p - endA)
-__host__ __device__ inline uint32_t string_bound(uint32_t eA, uint32_t eB, int64_t s, int smax, int ge)
-{
-    const uint32_t w = window_cols(eA, eB, s, smax, ge);
-    if (w == 0)
-        return 0;
-    const uint64_t top = (uint64_t)smax * eA, g = (uint64_t)(-ge);
-    const uint64_t left = top > (uint64_t)s ? (top - (uint64_t)s) / g : 0; // W_p - endA
-    return eA + (uint32_t)std::min<uint64_t>(eB, left);
-}
 // words of direction bits of a pair's window, a multiple of 4 (the kernel stores a band's column as one uint4)
-__host__ __device__ inline uint64_t dir_words(uint32_t eA, uint32_t ncol)
+uint64_t dir_words(uint32_t eA, uint32_t ncol)
 {
     return (uint64_t)((eA + RB - 1) / RB) * ncol * (RB / 8);
 }
@@ -359,19 +342,8 @@ __global__ __launch_bounds__(THREADS, 2) void swa_kernel(const KArgs k)
     }
 }
 
-// What runs, and the only place that reads the testing aid
-struct Choice {
-    int rb;               // rows per band of the kernels
-    bool lds;             // the compact table is staged in LDS
-    size_t smem;          // dynamic LDS per workgroup
-    unsigned max_blocks;  // workgroups of the persistent grids
-    uint64_t chunk_pairs; // the traceback's chunks: most pairs per chunk
-    uint64_t dir_cap;     // ... and most bytes of direction words per chunk
-    uint64_t slot_cap;    // ... and most bytes of one side's string slots per chunk
-    uint64_t band_cap;    // most bytes of band scratch (fewer workgroups beyond)
-};
-
-static Choice choose(const polyhip_scoring *sc, int cus)
+// What runs (Choice: sw_affine.h), and the only place that reads the testing aid
+Choice choose(const polyhip_scoring *sc, int cus)
 {
     Choice c{};
     c.rb = RB;
@@ -393,14 +365,14 @@ static Choice choose(const polyhip_scoring *sc, int cus)
 }
 
 // workgroups of a persistent grid over npairs pairs whose band scratch holds `cols` columns per wave
-static unsigned grid_blocks(const Choice &c, uint64_t npairs, uint64_t cols)
+unsigned grid_blocks(const Choice &c, uint64_t npairs, uint64_t cols)
 {
     uint64_t blocks = std::min<uint64_t>((npairs + THREADS - 1) / THREADS, c.max_blocks);
     const uint64_t per_block = std::max<uint64_t>(cols, 1) * 64 * sizeof(int2) * (THREADS / 64);
     blocks = std::min(blocks, std::max<uint64_t>(c.band_cap / per_block, 1));
     return (unsigned)std::max<uint64_t>(blocks, 1);
 }
-static size_t band_bytes(unsigned blocks, uint64_t cols)
+size_t band_bytes(unsigned blocks, uint64_t cols)
 {
     return (size_t)blocks * (THREADS / 64) * std::max<uint64_t>(cols, 1) * 64 * sizeof(int2);
 }
@@ -419,9 +391,9 @@ static void fill_args(KArgs &k, const polyhip_scoring *sc, const Choice &c, int 
 
 // The score pass on device pointers: d_band holds band_bytes(blocks, lenB) bytes.  lenB: the shared B's length, or the
 // longest B of the batch.
-static int score_pass(const polyhip_scoring *sc, const Choice &c, int go, int ge, const uint8_t *d_A, const uint64_t *d_offA,
-                      uint64_t npairs, const uint8_t *d_B, const uint64_t *d_offB, uint32_t lenB, int64_t *d_score,
-                      uint32_t *d_endA, uint32_t *d_endB, uint32_t *d_err, void *d_band, unsigned blocks, hipStream_t st)
+int score_pass(const polyhip_scoring *sc, const Choice &c, int go, int ge, const uint8_t *d_A, const uint64_t *d_offA,
+               uint64_t npairs, const uint8_t *d_B, const uint64_t *d_offB, uint32_t lenB, int64_t *d_score, uint32_t *d_endA,
+               uint32_t *d_endB, uint32_t *d_err, void *d_band, unsigned blocks, hipStream_t st)
 {
     KArgs k{};
     fill_args(k, sc, c, go, ge);
@@ -447,11 +419,11 @@ static int score_pass(const polyhip_scoring *sc, const Choice &c, int go, int ge
 // The traceback of pairs [0, npairs) (a chunk: every pointer is the chunk's own) from the score pass's outputs:
 // d_dirOff[p] = where pair p's dir_words(endA, window_cols) words start in d_dir; d_band holds band_bytes(blocks,
 // max_cols) bytes, max_cols = the chunk's widest window; the strings go right-aligned into stride-byte slots.
-static int traceback_pass(const polyhip_scoring *sc, const Choice &c, int go, int ge, const uint8_t *d_A, const uint64_t *d_offA,
-                          uint64_t npairs, const uint8_t *d_B, const uint64_t *d_offB, uint32_t lenB, const int64_t *d_score,
-                          const uint32_t *d_endA, const uint32_t *d_endB, const uint32_t *d_err, const uint64_t *d_dirOff,
-                          uint32_t *d_dir, void *d_band, uint32_t max_cols, unsigned blocks, uint8_t *d_alnA, uint8_t *d_alnB,
-                          uint32_t *d_alnLen, uint32_t stride, hipStream_t st)
+int traceback_pass(const polyhip_scoring *sc, const Choice &c, int go, int ge, const uint8_t *d_A, const uint64_t *d_offA,
+                   uint64_t npairs, const uint8_t *d_B, const uint64_t *d_offB, uint32_t lenB, const int64_t *d_score,
+                   const uint32_t *d_endA, const uint32_t *d_endB, const uint32_t *d_err, const uint64_t *d_dirOff,
+                   uint32_t *d_dir, void *d_band, uint32_t max_cols, unsigned blocks, uint8_t *d_alnA, uint8_t *d_alnB,
+                   uint32_t *d_alnLen, uint32_t stride, hipStream_t st)
 {
     KArgs k{};
     fill_args(k, sc, c, go, ge);

@@ -29,6 +29,12 @@ class _CInfo(C.Structure):
                 ("pairs_aligned", C.c_uint64), ("reads_mapped", C.c_uint64), ("chunks", C.c_uint32)]
 
 
+class _CAffineInfo(C.Structure):
+    _fields_ = [("seeds", C.c_uint64), ("seeds_over_max_occ", C.c_uint64), ("hits", C.c_uint64), ("clusters", C.c_uint64),
+                ("pairs_aligned", C.c_uint64), ("reads_mapped", C.c_uint64), ("pairs_traced", C.c_uint64), ("tb_cells", C.c_uint64),
+                ("chunks", C.c_uint32), ("tb_chunks", C.c_uint32)]
+
+
 @dataclass
 class MapParams:
     """polyhip_map_params.  The defaults are unmeasured: they are what short-read mappers commonly start from, not the
@@ -97,11 +103,10 @@ def workspace_bytes(index, scoring, params: MapParams, nreads: int, max_len: int
     return int(_lib.lib().polyhip_map_workspace_bytes(index.handle(), scoring.handle(), C.byref(p), int(nreads), int(max_len)))
 
 
-def map_reads_packed(index, scoring, buf: np.ndarray, offs: np.ndarray, params: MapParams | None = None, strings: bool = True,
-                     capacity: int | None = None, max_len: int | None = None) -> MapResult:
-    """Host-pointer entry point on a packed batch.  ``capacity`` bytes per string buffer (default: 1.25 x the reads' bytes
-    + 64 KB; a batch that needs more is run again with the exact size -- unless ``capacity`` was given, in which case the
-    result carries ``status`` = ERR_INVALID, ``aln_off[-1]`` = the bytes needed, and no strings)."""
+def _packed(call, buf: np.ndarray, offs: np.ndarray, params: MapParams | None, strings: bool, capacity: int | None,
+            max_len: int | None) -> MapResult:
+    """what the host-pointer entry points share: the output arrays, the retry with the exact string capacity, the strings as
+    lists.  call(params, reads, offs, n, max_len, *outputs, capacity) -> status"""
     params = params or MapParams()
     n = len(offs) - 1
     buf = np.ascontiguousarray(buf, dtype=np.uint8)
@@ -118,10 +123,9 @@ def map_reads_packed(index, scoring, buf: np.ndarray, offs: np.ndarray, params: 
     for _ in range(2):
         if strings:
             alnA, alnB = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.uint8)
-        rc = _lib.lib().polyhip_map_reads(
-            index.handle(), scoring.handle(), C.byref(p), buf.ctypes.data, offs.ctypes.data, n, int(max_len),
-            score.ctypes.data, second.ctypes.data, *[a.ctypes.data for a in u32],
-            alnA.ctypes.data if strings else None, alnB.ctypes.data if strings else None, off.ctypes.data if strings else None, cap)
+        rc = call(C.byref(p), buf.ctypes.data, offs.ctypes.data, n, int(max_len),
+                  score.ctypes.data, second.ctypes.data, *[a.ctypes.data for a in u32],
+                  alnA.ctypes.data if strings else None, alnB.ctypes.data if strings else None, off.ctypes.data if strings else None, cap)
         if strings and rc == _lib.ERR_INVALID and _strings_short():  # the strings did not fit: off[n] says what they need
             if capacity is not None:
                 break
@@ -137,11 +141,52 @@ def map_reads_packed(index, scoring, buf: np.ndarray, offs: np.ndarray, params: 
     return MapResult(score, second, *u32, sa, sb, off if strings else None, int(rc))
 
 
+def map_reads_packed(index, scoring, buf: np.ndarray, offs: np.ndarray, params: MapParams | None = None, strings: bool = True,
+                     capacity: int | None = None, max_len: int | None = None) -> MapResult:
+    """Host-pointer entry point on a packed batch.  ``capacity`` bytes per string buffer (default: 1.25 x the reads' bytes
+    + 64 KB; a batch that needs more is run again with the exact size -- unless ``capacity`` was given, in which case the
+    result carries ``status`` = ERR_INVALID, ``aln_off[-1]`` = the bytes needed, and no strings)."""
+    def call(p, *rest):
+        return _lib.lib().polyhip_map_reads(index.handle(), scoring.handle(), p, *rest)
+    return _packed(call, buf, offs, params, strings, capacity, max_len)
+
+
 def MapReads(index, scoring, reads, params: MapParams | None = None) -> list:
     """Every read of a list placed on the index's text -> list of MapRecord"""
     as_str = bool(reads) and all(isinstance(r, str) for r in reads)
     buf, offs = _pack(reads)
     r = map_reads_packed(index, scoring, buf, offs, params)
+    conv = (lambda b: b.decode("latin-1")) if as_str else (lambda b: b)
+    return [MapRecord(bool(r.flags[i] & FLAG_MAPPED), bool(r.flags[i] & FLAG_REVERSE), int(r.score[i]), int(r.second[i]),
+                      int(r.votes[i]), int(r.ref_start[i]), int(r.ref_end[i]), int(r.read_start[i]), int(r.read_end[i]),
+                      conv(r.alignA[i]), conv(r.alignB[i]), int(r.err[i])) for i in range(len(reads))]
+
+
+# ---- affine gaps in the extension (polyhip_map_reads_affine; host pointers only) ---------------------------------------------
+def last_affine_info() -> dict:
+    """polyhip_map_affine_last_info: what the calling thread's last affine call did"""
+    info = _CAffineInfo()
+    _lib.check(_lib.lib().polyhip_map_affine_last_info(C.byref(info)))
+    return {name: int(getattr(info, name)) for name, _ in _CAffineInfo._fields_}
+
+
+def map_reads_affine_packed(index, scoring, gap_open: int, gap_extend: int, buf: np.ndarray, offs: np.ndarray,
+                            params: MapParams | None = None, strings: bool = True, capacity: int | None = None,
+                            max_len: int | None = None, work_limit: int = 0) -> MapResult:
+    """map_reads_packed with Gotoh's affine gaps in the extension: the first symbol of a gap costs ``gap_open``, each
+    further one ``gap_extend`` (added values, gap_open <= gap_extend <= -1; the scoring handle's own gap is ignored).
+    ``work_limit``: the most device workspace in bytes (0: the default); ``capacity`` as in map_reads_packed."""
+    def call(p, reads, off, n, max_len_, *rest):
+        return _lib.lib().polyhip_map_reads_affine(index.handle(), scoring.handle(), p, int(gap_open), int(gap_extend), reads, off, n,
+                                                   max_len_, int(work_limit), *rest)
+    return _packed(call, buf, offs, params, strings, capacity, max_len)
+
+
+def MapReadsAffine(index, scoring, reads, gap_open: int, gap_extend: int, params: MapParams | None = None) -> list:
+    """MapReads with affine gaps in the extension -> list of MapRecord"""
+    as_str = bool(reads) and all(isinstance(r, str) for r in reads)
+    buf, offs = _pack(reads)
+    r = map_reads_affine_packed(index, scoring, gap_open, gap_extend, buf, offs, params)
     conv = (lambda b: b.decode("latin-1")) if as_str else (lambda b: b)
     return [MapRecord(bool(r.flags[i] & FLAG_MAPPED), bool(r.flags[i] & FLAG_REVERSE), int(r.score[i]), int(r.second[i]),
                       int(r.votes[i]), int(r.ref_start[i]), int(r.ref_end[i]), int(r.read_start[i]), int(r.read_end[i]),
