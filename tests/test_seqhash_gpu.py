@@ -4,6 +4,7 @@ rotated bytes must be identical.
 
 Mirrors seqhash/seqhash_test.go:68-91 (every rotation of pUC19 rotates to the same string)."""
 import os
+import zlib
 
 import numpy as np
 import pytest
@@ -74,17 +75,21 @@ def test_wave_and_workgroup_kernels_agree(sh, wave_max):
     """The wave-per-sequence kernel takes sequences up to 7 kB, the workgroup kernels what it marks (longer ones; beyond
     LDS from global memory).  POLYHIP_K5_WAVE_MAX moves the boundary: 0 = everything through the workgroup kernels,
     100 / 8192 / 32768 = other splits of the same batch.  Lengths on both sides of every boundary, > 1024 candidates of the
-    least word (the list is full), tandem repeats that do and do not close, the least word wrapping around the origin."""
+    least word (the list is full), tandem repeats that do and do not close, the least word wrapping around the origin
+    (tests/k5_shapes.py has these by family, on both strands)."""
     rng = np.random.default_rng(5)
     seqs = [b"", b"G", b"CA"]
     for L in (7, 8, 9, 75, 76, 77, 99, 100, 101, 7167, 7168, 7169, 7192, 8191, 8192, 8193, 20000, 32767, 32768, 32769):
         seqs.append(bytes(rng.choice(list(b"ACGT"), L).astype(np.uint8)))
-    seqs.append(bytes(rng.choice(list(b"AC"), 8000).astype(np.uint8)) + b"CCCC")          # ~ 500 candidates, then rounds
+    seqs.append(bytes(rng.choice(list(b"AC"), 8000).astype(np.uint8)) + b"CCCC")          # ~ 250 candidates, then rounds
     seqs.append(b"AAAC" * 1500)                                                          # 1500 candidates, closes on itself
-    seqs.append((b"AAAC" * 1500)[:-1])                                                   # the same, not closing: list full
-    seqs.append(b"GATTACA" * 700 + b"GAT")                                               # stalled rounds -> two-pointer search
-    seqs.append(b"CGT" * 2000 + b"A" + b"CGT" * 30 + b"AA")                              # least word wraps: ...AA | CG...
+    seqs.append((b"AAAC" * 1500)[:-1])                                                   # ONE candidate: the seam makes the only run AAAA
+    seqs.append(b"AAAC" * 1500 + b"G")                                                   # 1500 candidates, not closing: list full -> two-pointer search
+    seqs.append(b"GATTACA" * 700 + b"GAT")                                               # 700 candidates, the seam's ...ACAGATGA wins the first round
+    seqs.append(b"AACGT" * 700 + b"T")                                                   # 700 candidates, stalled rounds -> two-pointer search
+    seqs.append(b"CGT" * 2000 + b"A" + b"CGT" * 30 + b"AA")                              # ONE candidate, the run AAA | A..., wraps around the origin
     seqs.append(bytes(rng.choice(list(b"ACGT"), 124_000).astype(np.uint8)))               # beyond the LDS staging limit
+    seqs.append(bytes(rng.choice(list(b"ACG"), 400).astype(np.uint8)) * 10 + b"T")        # a wave of candidates equal beyond 260 bytes -> two-pointer search
     old = os.environ.pop("POLYHIP_K5_WAVE_MAX", None)
     try:
         if wave_max is not None:
@@ -146,7 +151,7 @@ def test_TestHash(sh):
 @pytest.mark.parametrize("stype,circular,ds", [("DNA", c, d) for c in (False, True) for d in (False, True)] +
                          [("RNA", True, True), ("RNA", False, False), ("PROTEIN", False, False), ("PROTEIN", True, False)])
 def test_hash_batch_matches_oracle(sh, stype, circular, ds):
-    rng = np.random.default_rng(hash((stype, circular, ds)) % (1 << 31))
+    rng = np.random.default_rng(zlib.crc32(repr((stype, circular, ds)).encode()))
     if stype == "PROTEIN":
         alpha = b"ACDEFGHIKLMNPQRSTVWYUO*BXZacdxz"
     else:
@@ -175,7 +180,7 @@ def test_hash_batch_normalised_while_staged(sh, monkeypatch, stype, ds):
     stages the bytes (no streaming pass in front).  Lower case, RNA's U, letters outside the alphabet in the first / a
     middle / the last position (the first offending letter is named), lengths 0, 1 and around the 16-byte pieces of the
     staging, the longest length a wave takes: equal to the oracle and to the pass it replaces (POLYHIP_S2_FOLD=0)."""
-    rng = np.random.default_rng(hash((stype, ds)) % (1 << 31))
+    rng = np.random.default_rng(zlib.crc32(repr((stype, ds)).encode()))
     alpha = b"ACDEFGHIKLMNPQRSTVWYUO*BXZacdxz" if stype == "PROTEIN" else b"ACGTacgtUuNRYSWKMBDHVZnryswkmbdhvz"
     seqs = [b"", b"A", b"a", b"u", b"AT", b"ta", b"GAATTC", b"acgu", b"ZZZ", b"AAAA", b"aAaA", b"J", b"j"]
     for L in list(range(2, 50)) + [63, 64, 65, 127, 1023, 1024, 1025, 2049, 4095, 4096, 5000, 7167, 7168]:
