@@ -994,6 +994,79 @@ int polyhip_map_reads_affine(const polyhip_bwt *h, const polyhip_scoring *sc,
                              uint64_t *alnOff, uint64_t aln_capacity);
 int polyhip_map_affine_last_info(polyhip_map_affine_info *info);
 
+/* ---- read mapping of paired-end reads: proper pairs, insert size, mate rescue (no counterpart in the reference) ---- */
+/*
+ * polyhip_map_pairs places npairs pairs of reads: mate 1 of pair i is read i of (reads1, off1), mate 2 is read i of
+ * (reads2, off2), each batch packed as polyhip_map_reads' is.  Entry 2i of every per-mate output is mate 1 of pair i, entry
+ * 2i + 1 is mate 2; tlen has one entry per pair; the strings are packed as in polyhip_map_reads, in that order (2 * npairs
+ * + 1 offsets).  For one pair, with mates r1, r2 of m1, m2 bytes, the text T of n bytes and W = band:
+ *  1. Steps 1-5 of polyhip_map_reads_affine run on each mate on its own: strands, seeds, clusters, ranks, windows [lo, hi)
+ *     and the SmithWatermanAffine(q, T[lo, hi)) score pass are unchanged.  Each kept candidate has strand s, lo, score, endA,
+ *     endB and err.  A mate's err is as in step 6 there: the lowest-ranked candidate's alphabet error, or 0xFFFFFFFF when
+ *     the mate is longer than max_len.  A mate with err != 0 has no usable candidate, is never an anchor and is never
+ *     rescued.  A candidate is usable when its mate's err is 0 and its score is at least min_score.
+ *  2. Projection.  For a usable candidate of a mate of m bytes, left = lo + endB - endA (signed 64-bit: the text position
+ *     q[0] reaches along the end cell's diagonal) and right = left + m.  A candidate f of one mate and a candidate r of the
+ *     other are a proper combination iff f is on strand 0 and r on strand 1, left_f <= left_r, right_f <= right_r, and
+ *     min_insert <= right_r - left_f <= max_insert.  right_r - left_f is the insert.  Forward-reverse orientation only:
+ *     dovetails and same-strand pairs are never proper.
+ *  3. Pairing.  Among all proper combinations (k1, k2), k1 a rank of mate 1 and k2 a rank of mate 2, the best has the
+ *     highest score1 + score2, ties to the smallest k1, then the smallest k2.  If there is one, both mates are mapped at
+ *     those candidates, flags bit 2 (proper) is set on both and tlen[i] is the insert.
+ *  4. Rescue, only when step 3 found nothing and rescue != 0.  For x = 1, 2: if mate x has a usable candidate, its anchor a
+ *     is its best usable candidate as step 6 picks it (highest score, lowest rank).  With y the other mate, an attempt is
+ *     made when err_y == 0 and m_y >= 1.  Anchor on strand 0: the query is q_y = ReverseComplement(r_y), the window
+ *     [left_a + min_insert - m_y - W, left_a + max_insert + W).  Anchor on strand 1: the query is q_y = r_y, the window
+ *     [right_a - max_insert - W, right_a - min_insert + m_y + W).  The window is clipped to [0, n); an empty window means
+ *     no attempt, a non-empty one counts in rescue_attempts.  The attempt is SmithWatermanAffine(q_y, T[wlo, whi)); it
+ *     succeeds iff its err is 0, its score is at least min_score and, with left_y = wlo + endB - endA, the anchor and this
+ *     alignment are a proper combination by step 2.  An alphabet error of an attempt is not reported.  Of the successful
+ *     attempts the one with the higher score_a + score_y wins, a tie goes to the attempt anchored on mate 1.  The anchor
+ *     mate is mapped at a with flags bit 2 set; the other mate is mapped at the rescued alignment with flags = mapped |
+ *     strand << 1 | proper (bit 2) | rescued (bit 3), votes 0 and ref_end = wlo + endB.  tlen[i] is the insert.
+ *  5. Fallback.  Otherwise each mate is placed exactly as step 6 of polyhip_map_reads_affine places a single read; bits 2
+ *     and 3 are clear and tlen[i] = 0.
+ *  6. In every case: second of a mate is the highest score among its kept candidates other than the chosen one (for a
+ *     rescued mate that is all of its kept candidates), 0 if there are none; ref_start, read_start and the strings come
+ *     from the traceback of the chosen alignment only (a candidate or a rescue window); every mapped mate is traced and no
+ *     other; unmapped mates get zeros and empty strings.
+ * Host pointers only: the call runs on the index's device, on the handle's stream, as polyhip_map_reads_affine does.
+ * Errors, in this order: everything polyhip_map_reads_affine checks, in its order and with its messages, the int32 cell
+ * range taken over the wider of the mapping window (max_len + 3 * band columns) and, with rescue != 0, the rescue window
+ * (max_insert - min_insert + max_len + 2 * band columns); a NULL pair_params, both_strands == 0, min_insert > max_insert
+ * or rescue > 1 is POLYHIP_ERR_INVALID naming the field; with rescue != 0 a rescue window of more than
+ * POLYHIP_MAP_MAX_RESCUE_COLS = 7168 columns (the widest window a single read's candidate can have: 4096 + 3 * 1024) is
+ * POLYHIP_ERR_UNSUPPORTED.  npairs == 0 is an empty, successful call.  String capacity behaves as in polyhip_map_reads.
+ * work_limit has the meaning it has in polyhip_map_reads_affine; chunks are whole pairs, a multiple of 128 pairs; the
+ * message of a limit that is too small names the bytes one chunk of min(npairs, 128) pairs needs; outputs are identical
+ * for every chunking.  The workspace also holds the rescue batch, and the winners' slots and direction words are sized for
+ * the wider of the two windows.  A chunk without a rescue request launches no rescue pass, one without a mapped mate no
+ * traceback.
+ * polyhip_map_pairs_last_info: the calling thread's last polyhip_map_pairs.  The first six counters are as
+ * polyhip_map_info, over all 2 * npairs mates; proper_pairs = pairs whose mates carry flags bit 2 (steps 3 and 4);
+ * rescue_attempts = rescue windows scored; rescued = pairs placed by step 4; pairs_traced = alignments traced (==
+ * reads_mapped in every call); chunks = chunks of pairs.
+ */
+#define POLYHIP_MAP_MAX_RESCUE_COLS 7168u
+typedef struct polyhip_map_pair_params {
+    uint32_t min_insert, max_insert, rescue;
+} polyhip_map_pair_params;
+typedef struct polyhip_map_pairs_info {
+    uint64_t seeds, seeds_over_max_occ, hits, clusters, pairs_aligned, reads_mapped;
+    uint64_t proper_pairs, rescue_attempts, rescued, pairs_traced;
+    uint32_t chunks;
+} polyhip_map_pairs_info;
+int polyhip_map_pairs(const polyhip_bwt *h, const polyhip_scoring *sc,
+                      const polyhip_map_params *params,
+                      const polyhip_map_pair_params *pair_params, int64_t gap_open,
+                      int64_t gap_extend, const uint8_t *reads1, const uint64_t *off1,
+                      const uint8_t *reads2, const uint64_t *off2, uint64_t npairs,
+                      uint32_t max_len, uint64_t work_limit, int64_t *score, int64_t *second,
+                      uint32_t *flags, uint32_t *votes, uint32_t *ref_start, uint32_t *ref_end,
+                      uint32_t *read_start, uint32_t *read_end, uint32_t *err, int64_t *tlen,
+                      uint8_t *alnA, uint8_t *alnB, uint64_t *alnOff, uint64_t aln_capacity);
+int polyhip_map_pairs_last_info(polyhip_map_pairs_info *info);
+
 /* ---- R1: the path's one collective -- all-gather of per-rank sketches (RCCL over xGMI) ---- */
 /*
  * For hosts without torch.distributed (the Go/cgo drop-in); one process per GPU.  RCCL is

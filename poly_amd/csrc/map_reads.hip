@@ -27,6 +27,12 @@
 //   k3a::traceback_pass the affine traceback of the winners only, in sub-chunks whose direction words fit the cap
 //   map_finish_kernel   ref_start / read_start from the winner's strings, string lengths, traced cells
 //   map_strings_kernel  as above, from the winners' slots
+// polyhip_map_pairs (paired-end reads: mates interleaved into one batch of 2 * npairs reads) runs the affine candidate pass, then:
+//   pair_reduce_kernel   one wave per pair: the best proper combination of the mates' candidates, or the rescue requests
+//   rescue_plan_kernel / rescue_gather_kernel   the requests as a second pair batch: the mate beside the window its partner implies
+//   k3a::score_pass      on that batch
+//   pair_resolve_kernel  one wave per pair: the rescue's success test and tie rule, the per-mate outputs, tlen, the winners' sources
+//   pair_winners_kernel / pair_wgather_kernel   the winners from either batch; the traceback, finish and strings steps as above
 #include "bwt_index.h"
 #include "sw_affine.h"
 #include "sw_scoring.h"
@@ -47,7 +53,7 @@ struct MapShape {
     uint64_t n;       // text length
 };
 
-enum { CNT_SEEDS = 0, CNT_OVER = 1, CNT_CLUSTERS = 2, CNT_MAPPED = 3, CNT_TBCELLS = 4, CNT_N = 5 };
+enum { CNT_SEEDS = 0, CNT_OVER = 1, CNT_CLUSTERS = 2, CNT_MAPPED = 3, CNT_TBCELLS = 4, CNT_PROPER = 5, CNT_RESCUED = 6, CNT_N = 7 };
 
 // transform.complementTable (transform.go:78-109): IUPAC letters in both cases, every other byte -> 0x00
 __device__ __forceinline__ uint32_t dna_complement(uint32_t b)
@@ -466,6 +472,358 @@ __global__ __launch_bounds__(BT) void map_finish_kernel(const uint32_t *__restri
         atomicAdd(cnt + CNT_TBCELLS, cells);
 }
 
+// ---- polyhip_map_pairs' own kernels ---------------------------------------------------------------------------------------
+// mates in one packed batch: read 2i = mate 1 of pair i, read 2i + 1 = mate 2.  One lane per pair: the lengths (scanned
+// into offsets afterwards) ...
+__global__ __launch_bounds__(BT) void pair_lens_kernel(const uint64_t *__restrict__ off1, const uint64_t *__restrict__ off2, uint64_t npairs,
+                                                       uint64_t *__restrict__ len)
+{
+    for (uint64_t i = blockIdx.x * (uint64_t)BT + threadIdx.x; i < npairs; i += (uint64_t)gridDim.x * BT) {
+        len[2 * i] = off1[i + 1] - off1[i];
+        len[2 * i + 1] = off2[i + 1] - off2[i];
+    }
+}
+
+// ... and one wave per mate: its bytes
+__global__ __launch_bounds__(BT) void pair_interleave_kernel(const uint8_t *__restrict__ reads1, const uint64_t *__restrict__ off1,
+                                                             const uint8_t *__restrict__ reads2, const uint64_t *__restrict__ off2,
+                                                             uint64_t nreads, const uint64_t *__restrict__ off, uint8_t *__restrict__ out)
+{
+    const int lane = threadIdx.x & 63;
+    for (uint64_t r = (blockIdx.x * (uint64_t)BT + threadIdx.x) / 64; r < nreads; r += (uint64_t)gridDim.x * (BT / 64)) {
+        const uint8_t *src = r & 1 ? reads2 + off2[r >> 1] : reads1 + off1[r >> 1];
+        const uint64_t o = off[r], m = off[r + 1] - o;
+        for (uint64_t i = lane; i < m; i += 64)
+            out[o + i] = src[i];
+    }
+}
+
+struct PairShape {
+    int64_t min_insert, max_insert;
+    uint32_t rescue;
+};
+
+// a (strand, left, length) and b: the insert when they are a proper combination (forward-reverse, neither end of the
+// forward mate beyond the reverse mate's, insert within the bounds), else -1
+__device__ __forceinline__ int64_t proper_insert(uint32_t sa, int64_t la, int64_t ma, uint32_t sb, int64_t lb, int64_t mb, const PairShape &q)
+{
+    if (sa == sb)
+        return -1;
+    const int64_t lf = sa ? lb : la, rf = sa ? lb + mb : la + ma; // the mate on strand 0
+    const int64_t lr = sa ? la : lb, rr = sa ? la + ma : lb + mb; // the mate on strand 1
+    const int64_t ins = rr - lf;
+    return lf <= lr && rf <= rr && ins >= q.min_insert && ins <= q.max_insert ? ins : -1;
+}
+
+// What one wave knows of a mate, lane i = its candidate of rank i
+struct MateCands {
+    uint32_t nc, err, strand;
+    int64_t m, score, left; // left = lo + endB - endA: where q[0] lands along the end cell's diagonal
+    int bi;                 // the single-read winner's rank ...
+    bool mapped, usable;    // ... which exists; this lane's candidate is usable
+};
+
+__device__ __forceinline__ MateCands load_mate(uint64_t r, int lane, const uint32_t *__restrict__ pfirst, const uint64_t *__restrict__ off,
+                                               const MapShape &g, int64_t min_score, const int64_t *__restrict__ pscore,
+                                               const uint32_t *__restrict__ pendA, const uint32_t *__restrict__ pendB,
+                                               const uint32_t *__restrict__ perr, const uint32_t *__restrict__ cstrand,
+                                               const uint32_t *__restrict__ clo)
+{
+    MateCands c;
+    const uint32_t p0 = pfirst[r];
+    c.nc = pfirst[r + 1] - p0;
+    c.m = (int64_t)(off[r + 1] - off[r]);
+    const bool have = (uint32_t)lane < c.nc;
+    c.score = have ? pscore[p0 + lane] : INT64_MIN;
+    const uint32_t er = have ? perr[p0 + lane] : 0u;
+    const uint64_t bad = __ballot(er != 0);
+    c.err = (uint64_t)c.m > g.max_len ? 0xFFFFFFFFu : 0u;
+    if (bad)
+        c.err = __shfl(er, __ffsll((unsigned long long)bad) - 1, 64);
+    c.strand = have ? cstrand[r * g.C + lane] : 0u;
+    c.left = have ? (int64_t)clo[r * g.C + lane] + (int64_t)pendB[p0 + lane] - (int64_t)pendA[p0 + lane] : 0;
+    int64_t bs = c.score;
+    int bi = lane;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const int64_t os = __shfl_xor(bs, d, 64);
+        const int oi = __shfl_xor(bi, d, 64);
+        if (os > bs || (os == bs && oi < bi))
+            bs = os, bi = oi;
+    }
+    c.bi = bi;
+    c.mapped = c.nc > 0 && c.err == 0 && bs >= min_score;
+    c.usable = have && c.err == 0 && c.score >= min_score;
+    return c;
+}
+
+// One wave per pair, after the candidates' score pass.  The proper combinations (k1, k2) are spread over the lanes, 64 at
+// a time, each lane fetching its two candidates from the lanes that hold them; the best has the highest sum, then the
+// smallest k1, then the smallest k2, which is the smallest k1 * nc2 + k2.  Out: err of both mates; choice = the rank
+// pairing chose, or without a proper combination the single-read winner's (-1: none); proper / insert of the pair; and
+// then the rescue requests, kept under the mate to rescue: rvalid = 1, the query's strand, the clipped window.
+__global__ __launch_bounds__(BT) void pair_reduce_kernel(const uint32_t *__restrict__ pfirst, const uint64_t *__restrict__ off, uint64_t npairs,
+                                                         MapShape g, PairShape q, int64_t min_score, const int64_t *__restrict__ pscore,
+                                                         const uint32_t *__restrict__ pendA, const uint32_t *__restrict__ pendB,
+                                                         const uint32_t *__restrict__ perr, const uint32_t *__restrict__ cstrand,
+                                                         const uint32_t *__restrict__ clo, uint32_t *__restrict__ o_err,
+                                                         int32_t *__restrict__ choice, uint32_t *__restrict__ proper,
+                                                         int64_t *__restrict__ ptlen, uint32_t *__restrict__ rvalid,
+                                                         uint32_t *__restrict__ rstrand, uint32_t *__restrict__ rlo, uint32_t *__restrict__ rhi)
+{
+    const int lane = threadIdx.x & 63;
+    for (uint64_t i = (blockIdx.x * (uint64_t)BT + threadIdx.x) / 64; i < npairs; i += (uint64_t)gridDim.x * (BT / 64)) {
+        const MateCands a = load_mate(2 * i, lane, pfirst, off, g, min_score, pscore, pendA, pendB, perr, cstrand, clo);
+        const MateCands b = load_mate(2 * i + 1, lane, pfirst, off, g, min_score, pscore, pendA, pendB, perr, cstrand, clo);
+        int64_t bsum = INT64_MIN, bins = 0;
+        uint32_t bt = 0xFFFFFFFFu;
+        const uint32_t ncomb = a.err == 0 && b.err == 0 ? a.nc * b.nc : 0u;
+        for (uint32_t t0 = 0; t0 < ncomb; t0 += 64) {
+            const uint32_t t = t0 + lane;
+            const bool in = t < ncomb;
+            const int k1 = in ? (int)(t / b.nc) : 0, k2 = in ? (int)(t % b.nc) : 0;
+            const int64_t s1 = __shfl(a.score, k1, 64), s2 = __shfl(b.score, k2, 64);
+            const int64_t l1 = __shfl(a.left, k1, 64), l2 = __shfl(b.left, k2, 64);
+            const uint32_t d1 = __shfl(a.strand, k1, 64), d2 = __shfl(b.strand, k2, 64);
+            const int u1 = __shfl((int)a.usable, k1, 64), u2 = __shfl((int)b.usable, k2, 64);
+            const int64_t ins = in && u1 && u2 ? proper_insert(d1, l1, a.m, d2, l2, b.m, q) : -1;
+            if (ins >= 0 && s1 + s2 > bsum) // t ascends within a lane: the first of equal sums stays
+                bsum = s1 + s2, bins = ins, bt = t;
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            const int64_t os = __shfl_xor(bsum, d, 64), oi = __shfl_xor(bins, d, 64);
+            const uint32_t ot = __shfl_xor(bt, d, 64);
+            if (ot != 0xFFFFFFFFu && (bt == 0xFFFFFFFFu || os > bsum || (os == bsum && ot < bt)))
+                bsum = os, bins = oi, bt = ot;
+        }
+        const bool found = bt != 0xFFFFFFFFu;
+        // the anchors of a rescue: each mate's single-read winner, fetched from the lane that holds it
+        const int64_t la = __shfl(a.left, a.bi, 64), lb = __shfl(b.left, b.bi, 64);
+        const uint32_t sa = __shfl(a.strand, a.bi, 64), sb = __shfl(b.strand, b.bi, 64);
+        if (lane == 0) {
+            o_err[2 * i] = a.err;
+            o_err[2 * i + 1] = b.err;
+            choice[2 * i] = found ? (int32_t)(bt / b.nc) : a.mapped ? a.bi : -1;
+            choice[2 * i + 1] = found ? (int32_t)(bt % b.nc) : b.mapped ? b.bi : -1;
+            proper[i] = found;
+            ptlen[i] = found ? bins : 0;
+        }
+        if (lane < 2) { // lane 0: mate 1 anchors the rescue of mate 2; lane 1: the other way round
+            const bool anchored = lane == 0 ? a.mapped : b.mapped;
+            const uint32_t s = lane == 0 ? sa : sb, ey = lane == 0 ? b.err : a.err;
+            const int64_t left = lane == 0 ? la : lb, mx = lane == 0 ? a.m : b.m, my = lane == 0 ? b.m : a.m;
+            const int64_t W = g.W;
+            int64_t wlo = s == 0 ? left + q.min_insert - my - W : left + mx - q.max_insert - W;
+            int64_t whi = s == 0 ? left + q.max_insert + W : left + mx - q.min_insert + my + W;
+            wlo = wlo > 0 ? wlo : 0;
+            whi = whi < (int64_t)g.n ? whi : (int64_t)g.n;
+            const bool ask = !found && q.rescue && anchored && ey == 0 && my >= 1 && wlo < whi;
+            const uint64_t y = 2 * i + 1 - lane;
+            rvalid[y] = ask;
+            rstrand[y] = s ^ 1u;
+            rlo[y] = ask ? (uint32_t)wlo : 0u;
+            rhi[y] = ask ? (uint32_t)whi : 0u;
+        }
+    }
+}
+
+// One lane per mate with a request: request rfirst[y] of the rescue batch, its lengths (scanned into offsets afterwards)
+__global__ __launch_bounds__(BT) void rescue_plan_kernel(const uint32_t *__restrict__ rfirst, const uint64_t *__restrict__ off, uint64_t nreads,
+                                                         const uint32_t *__restrict__ rlo, const uint32_t *__restrict__ rhi,
+                                                         uint32_t *__restrict__ rread, uint64_t *__restrict__ lenA, uint64_t *__restrict__ lenB)
+{
+    for (uint64_t y = blockIdx.x * (uint64_t)BT + threadIdx.x; y < nreads; y += (uint64_t)gridDim.x * BT) {
+        const uint32_t j = rfirst[y];
+        if (rfirst[y + 1] == j)
+            continue;
+        rread[j] = (uint32_t)y;
+        lenA[j] = off[y + 1] - off[y];
+        lenB[j] = rhi[y] - rlo[y];
+    }
+}
+
+// One wave per request: A = the mate on the strand its anchor implies, B = the window of the text
+__global__ __launch_bounds__(BT) void rescue_gather_kernel(const uint8_t *__restrict__ reads, const uint64_t *__restrict__ off,
+                                                           const uint8_t *__restrict__ text, const uint32_t *__restrict__ rread,
+                                                           const uint32_t *__restrict__ rstrand, const uint32_t *__restrict__ rlo, uint64_t nreq,
+                                                           const uint64_t *__restrict__ offA, const uint64_t *__restrict__ offB,
+                                                           uint8_t *__restrict__ A, uint8_t *__restrict__ B)
+{
+    __shared__ uint8_t cmp[256];
+    cmp[threadIdx.x] = (uint8_t)dna_complement(threadIdx.x);
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    for (uint64_t j = (blockIdx.x * (uint64_t)BT + threadIdx.x) / 64; j < nreq; j += (uint64_t)gridDim.x * (BT / 64)) {
+        const uint32_t y = rread[j];
+        const uint8_t *src = reads + off[y];
+        const uint64_t m = offA[j + 1] - offA[j], lb = offB[j + 1] - offB[j];
+        uint8_t *da = A + offA[j], *db = B + offB[j];
+        if (rstrand[y]) {
+            for (uint64_t i = lane; i < m; i += 64)
+                da[i] = cmp[src[m - 1 - i]];
+        } else {
+            for (uint64_t i = lane; i < m; i += 64)
+                da[i] = src[i];
+        }
+        const uint8_t *t = text + rlo[y];
+        for (uint64_t i = lane; i < lb; i += 64)
+            db[i] = t[i];
+    }
+}
+
+constexpr uint32_t SRC_RESCUE = 0x80000000u; // a winner's source: a pair of the candidate batch, or (this bit) of the rescue batch
+
+// One wave per pair, after the rescue score pass (rfirst is all zero when there was none).  Applies the success test and
+// the tie rule of the rescue, then writes every per-mate output but ref_start / read_start (map_finish_kernel's, from the
+// strings), tlen, wmap = 1 for a mapped mate and src = where its alignment is.
+__global__ __launch_bounds__(BT) void pair_resolve_kernel(const uint32_t *__restrict__ pfirst, const uint64_t *__restrict__ off, uint64_t npairs,
+                                                          MapShape g, PairShape q, int64_t min_score, const int64_t *__restrict__ pscore,
+                                                          const uint32_t *__restrict__ pendA, const uint32_t *__restrict__ pendB,
+                                                          const uint32_t *__restrict__ cvotes, const uint32_t *__restrict__ cstrand,
+                                                          const uint32_t *__restrict__ clo, const int32_t *__restrict__ choice,
+                                                          const uint32_t *__restrict__ proper, const int64_t *__restrict__ ptlen,
+                                                          const uint32_t *__restrict__ rfirst, const uint32_t *__restrict__ rstrand,
+                                                          const uint32_t *__restrict__ rlo, const int64_t *__restrict__ rscore,
+                                                          const uint32_t *__restrict__ rendA, const uint32_t *__restrict__ rendB,
+                                                          const uint32_t *__restrict__ rerr, int64_t *__restrict__ o_score,
+                                                          int64_t *__restrict__ o_second, uint32_t *__restrict__ o_flags,
+                                                          uint32_t *__restrict__ o_votes, uint32_t *__restrict__ o_rs, uint32_t *__restrict__ o_re,
+                                                          uint32_t *__restrict__ o_qs, uint32_t *__restrict__ o_qe, int64_t *__restrict__ o_tlen,
+                                                          uint64_t *__restrict__ slen, uint32_t *__restrict__ src, uint32_t *__restrict__ wmap,
+                                                          unsigned long long *__restrict__ cnt)
+{
+    const int lane = threadIdx.x & 63;
+    uint32_t nmapped = 0, nproper = 0, nrescued = 0;
+    for (uint64_t i = (blockIdx.x * (uint64_t)BT + threadIdx.x) / 64; i < npairs; i += (uint64_t)gridDim.x * (BT / 64)) {
+        const bool paired = proper[i] != 0;
+        int64_t tlen = ptlen[i];
+        int resc = -1; // the mate that is placed by a rescue (0 or 1)
+        if (!paired && q.rescue) {
+            int64_t best = INT64_MIN;
+            for (int yy = 1; yy >= 0; --yy) { // the attempt anchored on mate 1 first: it keeps a tie
+                const uint64_t y = 2 * i + yy, x = 2 * i + 1 - yy;
+                const uint32_t j = rfirst[y];
+                if (rfirst[y + 1] == j || rerr[j] != 0 || rscore[j] < min_score)
+                    continue;
+                const uint32_t px = pfirst[x] + (uint32_t)choice[x];
+                const uint64_t cx = x * g.C + (uint32_t)choice[x];
+                const int64_t la = (int64_t)clo[cx] + (int64_t)pendB[px] - (int64_t)pendA[px];
+                const int64_t ly = (int64_t)rlo[y] + (int64_t)rendB[j] - (int64_t)rendA[j];
+                const int64_t ins = proper_insert(cstrand[cx], la, (int64_t)(off[x + 1] - off[x]), rstrand[y], ly,
+                                                  (int64_t)(off[y + 1] - off[y]), q);
+                if (ins >= 0 && pscore[px] + rscore[j] > best)
+                    best = pscore[px] + rscore[j], resc = yy, tlen = ins;
+            }
+        }
+        for (int x = 0; x < 2; ++x) {
+            const uint64_t r = 2 * i + x;
+            const uint32_t p0 = pfirst[r], nc = pfirst[r + 1] - p0;
+            const int ch = choice[r];
+            const bool rescued = resc == x, mapped = rescued || ch >= 0;
+            // second: the best of the kept candidates but the chosen one (a rescued mate chose none of them)
+            int64_t second = (uint32_t)lane < nc && (rescued || lane != ch) ? pscore[p0 + lane] : INT64_MIN;
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) {
+                const int64_t other = __shfl_xor(second, d, 64);
+                second = other > second ? other : second;
+            }
+            if (second == INT64_MIN)
+                second = 0;
+            if (lane == 0) {
+                const uint32_t pair_bits = paired || resc >= 0 ? 4u : 0u;
+                if (rescued) {
+                    const uint32_t j = rfirst[r];
+                    o_score[r] = rscore[j];
+                    o_flags[r] = 1u | (rstrand[r] << 1) | pair_bits | 8u;
+                    o_votes[r] = 0;
+                    o_re[r] = rlo[r] + rendB[j];
+                    o_qe[r] = rendA[j];
+                    src[r] = SRC_RESCUE | j;
+                } else if (mapped) {
+                    const uint32_t bp = p0 + (uint32_t)ch;
+                    const uint64_t c = r * g.C + (uint32_t)ch;
+                    o_score[r] = pscore[bp];
+                    o_flags[r] = 1u | (cstrand[c] << 1) | pair_bits;
+                    o_votes[r] = cvotes[c];
+                    o_re[r] = clo[c] + pendB[bp];
+                    o_qe[r] = pendA[bp];
+                    src[r] = bp;
+                } else {
+                    o_score[r] = 0;
+                    o_flags[r] = 0;
+                    o_votes[r] = 0;
+                    o_re[r] = 0;
+                    o_qe[r] = 0;
+                    src[r] = 0;
+                }
+                o_second[r] = mapped ? second : 0;
+                o_rs[r] = 0;
+                o_qs[r] = 0;
+                slen[r] = 0;
+                wmap[r] = mapped;
+                nmapped += mapped;
+            }
+        }
+        if (lane == 0) {
+            o_tlen[i] = paired || resc >= 0 ? tlen : 0;
+            nproper += paired || resc >= 0;
+            nrescued += resc >= 0;
+        }
+    }
+    count_add(cnt + CNT_MAPPED, nmapped);
+    count_add(cnt + CNT_PROPER, nproper);
+    count_add(cnt + CNT_RESCUED, nrescued);
+}
+
+// map_winners_kernel / map_wgather_kernel for winners that lie in either batch
+__global__ __launch_bounds__(BT) void pair_winners_kernel(const uint32_t *__restrict__ wfirst, const uint32_t *__restrict__ src, uint64_t nreads,
+                                                          const uint64_t *__restrict__ offA, const uint64_t *__restrict__ offB,
+                                                          const int64_t *__restrict__ pscore, const uint32_t *__restrict__ pendA,
+                                                          const uint32_t *__restrict__ pendB, const uint64_t *__restrict__ roffA,
+                                                          const uint64_t *__restrict__ roffB, const int64_t *__restrict__ rscore,
+                                                          const uint32_t *__restrict__ rendA, const uint32_t *__restrict__ rendB,
+                                                          uint32_t *__restrict__ wsrc, uint64_t *__restrict__ wlenA, uint64_t *__restrict__ wlenB,
+                                                          int64_t *__restrict__ wscore, uint32_t *__restrict__ wendA,
+                                                          uint32_t *__restrict__ wendB, uint32_t *__restrict__ werr)
+{
+    for (uint64_t r = blockIdx.x * (uint64_t)BT + threadIdx.x; r < nreads; r += (uint64_t)gridDim.x * BT) {
+        const uint32_t w = wfirst[r];
+        if (wfirst[r + 1] == w)
+            continue;
+        const uint32_t s = src[r], p = s & ~SRC_RESCUE;
+        const bool resc = (s & SRC_RESCUE) != 0;
+        wsrc[w] = s;
+        wlenA[w] = resc ? roffA[p + 1] - roffA[p] : offA[p + 1] - offA[p];
+        wlenB[w] = resc ? roffB[p + 1] - roffB[p] : offB[p + 1] - offB[p];
+        wscore[w] = resc ? rscore[p] : pscore[p];
+        wendA[w] = resc ? rendA[p] : pendA[p];
+        wendB[w] = resc ? rendB[p] : pendB[p];
+        werr[w] = 0u;
+    }
+}
+
+__global__ __launch_bounds__(BT) void pair_wgather_kernel(const uint32_t *__restrict__ wsrc, uint64_t nwin, const uint64_t *__restrict__ offA,
+                                                          const uint64_t *__restrict__ offB, const uint8_t *__restrict__ A,
+                                                          const uint8_t *__restrict__ B, const uint64_t *__restrict__ roffA,
+                                                          const uint64_t *__restrict__ roffB, const uint8_t *__restrict__ rA,
+                                                          const uint8_t *__restrict__ rB, const uint64_t *__restrict__ woffA,
+                                                          const uint64_t *__restrict__ woffB, uint8_t *__restrict__ wA, uint8_t *__restrict__ wB)
+{
+    const int lane = threadIdx.x & 63;
+    for (uint64_t w = (blockIdx.x * (uint64_t)BT + threadIdx.x) / 64; w < nwin; w += (uint64_t)gridDim.x * (BT / 64)) {
+        const uint32_t s = wsrc[w], p = s & ~SRC_RESCUE;
+        const bool resc = (s & SRC_RESCUE) != 0;
+        const uint64_t la = woffA[w + 1] - woffA[w], lb = woffB[w + 1] - woffB[w];
+        const uint8_t *sa_ = resc ? rA + roffA[p] : A + offA[p], *sb_ = resc ? rB + roffB[p] : B + offB[p];
+        uint8_t *da = wA + woffA[w], *db = wB + woffB[w];
+        for (uint64_t i = lane; i < la; i += 64)
+            da[i] = sa_[i];
+        for (uint64_t i = lane; i < lb; i += 64)
+            db[i] = sb_[i];
+    }
+}
+
 // ---- the workspace of a chunk of nr reads ---------------------------------------------------------------------------------
 struct MapWork {
     unsigned long long *cnt; // CNT_N counters, then the strings' running total
@@ -493,12 +851,24 @@ struct MapWork {
     uint8_t *wA, *wB;
     int64_t *wscore;
     uint64_t sub, dwords; // pairs per traceback sub-chunk; direction words of each
+    uint32_t lenW;        // the widest window a winner can have: lenB, or a rescue window
+    // polyhip_map_pairs': per mate the candidate pairing chose (-1 none), per pair proper / insert, the rescue requests by
+    // rescued mate, and the rescue batch with its scores
+    int32_t *choice;
+    uint32_t *proper, *rfirst, *rstrand, *rlo, *rhi, *rread, *rendA, *rendB, *rerr;
+    int64_t *ptlen, *rscore;
+    uint64_t *roffA, *roffB;
+    uint8_t *rA, *rB;
 };
 
 // polyhip_map_reads_affine's gaps and what k3a::choose() fixed for the call
 struct MapAffine {
     int go, ge;
     k3a::Choice c;
+    // polyhip_map_pairs: the reads are mates (2i, 2i + 1), and the winners' windows are up to `wide` columns (a rescue
+    // window; 0: none is wider than a candidate's)
+    bool pairs = false;
+    uint32_t wide = 0;
 };
 
 // carves the chunk's arrays out of `base` (nullptr: sizes only) and returns the bytes; 0 = the chunk cannot be held at all
@@ -512,7 +882,8 @@ size_t map_carve(const polyhip_scoring *sc, const MapShape &g, const MapAffine *
     if (w.hcap >= (1ull << 31) || w.pcap >= (1ull << 31))
         return 0;
     w.lenB = g.max_len + 3 * g.W;
-    w.stride = af ? k3a::slot_stride(g.max_len, w.lenB) : polyhip_sw_traceback_stride(sc, g.max_len, w.lenB);
+    w.lenW = af ? std::max(w.lenB, af->wide) : w.lenB;
+    w.stride = af ? k3a::slot_stride(g.max_len, w.lenW) : polyhip_sw_traceback_stride(sc, g.max_len, w.lenB);
     const uint64_t nb = radix_blocks(std::max<uint64_t>(w.hcap, 1));
     Carve c{base};
     w.cnt = c.take<unsigned long long>(CNT_N + 1);
@@ -545,8 +916,11 @@ size_t map_carve(const polyhip_scoring *sc, const MapShape &g, const MapAffine *
         // the score pass's band scratch serves the traceback too (fewer pairs, the same columns); the direction words of
         // a sub-chunk are the worst case per pair, held under the affine call's cap
         w.blocks = k3a::grid_blocks(af->c, std::max<uint64_t>(w.pcap, 1), w.lenB);
-        w.band = c.take<uint8_t>(k3a::band_bytes(w.blocks, w.lenB));
-        w.dwords = k3a::dir_words(g.max_len, w.lenB);
+        size_t band = k3a::band_bytes(w.blocks, w.lenB);
+        if (w.lenW > w.lenB) // at most nr pairs (rescue requests, winners) run at the wider window
+            band = std::max(band, k3a::band_bytes(k3a::grid_blocks(af->c, std::max<uint64_t>(nr, 1), w.lenW), w.lenW));
+        w.band = c.take<uint8_t>(band);
+        w.dwords = k3a::dir_words(g.max_len, w.lenW);
         w.sub = std::min(std::min(af->c.chunk_pairs, af->c.dir_cap / std::max<uint64_t>(w.dwords * 4, 1)), nr);
         w.sub = std::max<uint64_t>(w.sub, 1);
         w.wfirst = c.take<uint32_t>(nr + 1);
@@ -554,7 +928,7 @@ size_t map_carve(const polyhip_scoring *sc, const MapShape &g, const MapAffine *
         w.woffA = c.take<uint64_t>(nr + 1);
         w.woffB = c.take<uint64_t>(nr + 1);
         w.wA = c.take<uint8_t>(nr * g.max_len + 64);
-        w.wB = c.take<uint8_t>(nr * w.lenB + 64);
+        w.wB = c.take<uint8_t>(nr * w.lenW + 64);
         w.wscore = c.take<int64_t>(nr);
         w.wendA = c.take<uint32_t>(nr);
         w.wendB = c.take<uint32_t>(nr);
@@ -564,6 +938,24 @@ size_t map_carve(const polyhip_scoring *sc, const MapShape &g, const MapAffine *
         w.dir = c.take<uint32_t>(w.sub * w.dwords + 4);
         w.slotA = c.take<uint8_t>(nr * w.stride);
         w.slotB = c.take<uint8_t>(nr * w.stride);
+        if (af->pairs) {
+            w.choice = c.take<int32_t>(nr);
+            w.proper = c.take<uint32_t>(nr / 2 + 1);
+            w.ptlen = c.take<int64_t>(nr / 2 + 1);
+            w.rfirst = c.take<uint32_t>(nr + 1);
+            w.rstrand = c.take<uint32_t>(nr);
+            w.rlo = c.take<uint32_t>(nr);
+            w.rhi = c.take<uint32_t>(nr);
+            w.rread = c.take<uint32_t>(nr);
+            w.roffA = c.take<uint64_t>(nr + 1);
+            w.roffB = c.take<uint64_t>(nr + 1);
+            w.rA = c.take<uint8_t>(nr * g.max_len + 64);
+            w.rB = c.take<uint8_t>(nr * w.lenW + 64);
+            w.rscore = c.take<int64_t>(nr);
+            w.rendA = c.take<uint32_t>(nr);
+            w.rendB = c.take<uint32_t>(nr);
+            w.rerr = c.take<uint32_t>(nr);
+        }
     } else {
         w.slotA = c.take<uint8_t>(w.pcap * w.stride);
         w.slotB = c.take<uint8_t>(w.pcap * w.stride);
@@ -667,6 +1059,68 @@ void keep_info(const polyhip_map_info &i, const MapAffine *af, uint64_t traced, 
                                       i.chunks, tb_chunks};
 }
 
+// Steps 1-5 for a chunk of nr reads: seeds -> hits -> clusters -> the kept candidates as a pair batch -> its scores (the
+// affine score pass, or the linear aligner with every pair's strings).  *pairs_out = the candidates.
+int map_candidates(const BwtHandle *h, const polyhip_scoring *sc, const MapShape &g, const MapAffine *af, const MapWork &w,
+                   const uint8_t *d_reads, const uint64_t *off, uint64_t nr, hipStream_t st, polyhip_map_info &info, uint32_t *pairs_out)
+{
+    const uint64_t slots = nr * g.strands * g.ns;
+    // seeds -> hits
+    uint32_t nhits = 0;
+    if (slots) {
+        if (h->x.layout == 0)
+            hipLaunchKernelGGL(map_seed_kernel<0>, dim3(grid_for(slots)), dim3(BT), 0, st, h->x, d_reads, off, slots, g, w.start, w.first,
+                               w.cnt);
+        else
+            hipLaunchKernelGGL(map_seed_kernel<1>, dim3(grid_for(slots)), dim3(BT), 0, st, h->x, d_reads, off, slots, g, w.start, w.first,
+                               w.cnt);
+        PH_HIP(hipGetLastError());
+        PH_HIP(scan_excl<uint32_t>(w.first, w.first, slots, w.scratch, st));
+        PH_HIP(hipMemcpyAsync(&nhits, w.first + slots, sizeof nhits, hipMemcpyDeviceToHost, st));
+        PH_HIP(hipStreamSynchronize(st));
+    }
+    info.hits += nhits;
+    uint32_t npairs = 0;
+    uint64_t *ka = w.ka, *kb = w.kb;
+    uint32_t *va = w.va, *vb = w.vb;
+    if (nhits) {
+        hipLaunchKernelGGL(map_expand_kernel, dim3(grid_for(slots)), dim3(BT), 0, st, h->d_sa, w.start, w.first, slots, g, ka, va);
+        PH_HIP(hipGetLastError());
+        if (int rc = radix_sort(ka, va, kb, vb, nhits, (int)g.dbits + bits_for(2 * nr - 1), w.hist, w.scratch, st))
+            return rc;
+        hipLaunchKernelGGL(map_cluster_kernel, dim3(grid_for(nr * 64)), dim3(BT), 0, st, ka, w.first, off, nr, g, w.pfirst, w.cvotes,
+                           w.cstrand, w.clo, w.chi, w.cnt);
+        PH_HIP(hipGetLastError());
+        PH_HIP(scan_excl<uint32_t>(w.pfirst, w.pfirst, nr, w.scratch, st));
+        PH_HIP(hipMemcpyAsync(&npairs, w.pfirst + nr, sizeof npairs, hipMemcpyDeviceToHost, st));
+        PH_HIP(hipStreamSynchronize(st));
+    } else {
+        PH_HIP(hipMemsetAsync(w.pfirst, 0, (nr + 1) * sizeof(uint32_t), st)); // no read has a candidate
+    }
+    info.pairs_aligned += npairs;
+    if (npairs) {
+        hipLaunchKernelGGL(map_pairs_kernel, dim3(grid_for(nr * g.C)), dim3(BT), 0, st, w.pfirst, off, w.clo, w.chi, nr, g.C, w.pread,
+                           w.offA, w.offB);
+        PH_HIP(hipGetLastError());
+        PH_HIP(scan_excl<uint64_t>(w.offA, w.offA, npairs, w.scratch, st));
+        PH_HIP(scan_excl<uint64_t>(w.offB, w.offB, npairs, w.scratch, st));
+        hipLaunchKernelGGL(map_gather_kernel, dim3(grid_for((uint64_t)npairs * 64)), dim3(BT), 0, st, d_reads, off, h->d_text, w.pread,
+                           w.pfirst, w.cstrand, w.clo, g.C, (uint64_t)npairs, w.offA, w.offB, w.A, w.B);
+        PH_HIP(hipGetLastError());
+        if (af) {
+            if (int rc = k3a::score_pass(sc, af->c, af->go, af->ge, w.A, w.offA, npairs, w.B, w.offB, w.lenB, w.score, w.endA, w.endB,
+                                         w.err, w.band, k3a::grid_blocks(af->c, npairs, w.lenB), st))
+                return rc;
+        } else if (int rc = polyhip_sw_align_batch_dev(sc, w.A, w.offA, npairs, g.max_len, w.B, w.offB, w.lenB, w.score, w.endA, w.endB,
+                                                       w.err, w.slotA, w.slotB, w.alnLen, w.stride, w.sw_work, w.sw_bytes, w.tb_work,
+                                                       w.tb_bytes, st)) {
+            return rc;
+        }
+    }
+    *pairs_out = npairs;
+    return POLYHIP_OK;
+}
+
 // The call on device pointers, on the index's device (the caller has entered it).  *needed = the strings' bytes.
 // af: the extension has affine gaps and only the winners are traced (polyhip_map_reads_affine).
 int map_run(const BwtHandle *h, const polyhip_scoring *sc, const polyhip_map_params *p, const MapAffine *af, const uint8_t *d_reads,
@@ -703,60 +1157,11 @@ int map_run(const BwtHandle *h, const polyhip_scoring *sc, const polyhip_map_par
     }
     SyncOnExit sync(st); // counts are read back into locals
     for (uint64_t r0 = 0; r0 < nreads; r0 += per, ++info.chunks) {
-        const uint64_t nr = std::min(per, nreads - r0), slots = nr * g.strands * g.ns;
+        const uint64_t nr = std::min(per, nreads - r0);
         const uint64_t *off = d_off + r0;
-        // seeds -> hits
-        uint32_t nhits = 0;
-        if (slots) {
-            if (h->x.layout == 0)
-                hipLaunchKernelGGL(map_seed_kernel<0>, dim3(grid_for(slots)), dim3(BT), 0, st, h->x, d_reads, off, slots, g, w.start, w.first,
-                                   w.cnt);
-            else
-                hipLaunchKernelGGL(map_seed_kernel<1>, dim3(grid_for(slots)), dim3(BT), 0, st, h->x, d_reads, off, slots, g, w.start, w.first,
-                                   w.cnt);
-            PH_HIP(hipGetLastError());
-            PH_HIP(scan_excl<uint32_t>(w.first, w.first, slots, w.scratch, st));
-            PH_HIP(hipMemcpyAsync(&nhits, w.first + slots, sizeof nhits, hipMemcpyDeviceToHost, st));
-            PH_HIP(hipStreamSynchronize(st));
-        }
-        info.hits += nhits;
         uint32_t npairs = 0;
-        uint64_t *ka = w.ka, *kb = w.kb;
-        uint32_t *va = w.va, *vb = w.vb;
-        if (nhits) {
-            hipLaunchKernelGGL(map_expand_kernel, dim3(grid_for(slots)), dim3(BT), 0, st, h->d_sa, w.start, w.first, slots, g, ka, va);
-            PH_HIP(hipGetLastError());
-            if (int rc = radix_sort(ka, va, kb, vb, nhits, (int)g.dbits + bits_for(2 * nr - 1), w.hist, w.scratch, st))
-                return rc;
-            hipLaunchKernelGGL(map_cluster_kernel, dim3(grid_for(nr * 64)), dim3(BT), 0, st, ka, w.first, off, nr, g, w.pfirst, w.cvotes,
-                               w.cstrand, w.clo, w.chi, w.cnt);
-            PH_HIP(hipGetLastError());
-            PH_HIP(scan_excl<uint32_t>(w.pfirst, w.pfirst, nr, w.scratch, st));
-            PH_HIP(hipMemcpyAsync(&npairs, w.pfirst + nr, sizeof npairs, hipMemcpyDeviceToHost, st));
-            PH_HIP(hipStreamSynchronize(st));
-        } else {
-            PH_HIP(hipMemsetAsync(w.pfirst, 0, (nr + 1) * sizeof(uint32_t), st)); // no read has a candidate
-        }
-        info.pairs_aligned += npairs;
-        if (npairs) {
-            hipLaunchKernelGGL(map_pairs_kernel, dim3(grid_for(nr * g.C)), dim3(BT), 0, st, w.pfirst, off, w.clo, w.chi, nr, g.C, w.pread,
-                               w.offA, w.offB);
-            PH_HIP(hipGetLastError());
-            PH_HIP(scan_excl<uint64_t>(w.offA, w.offA, npairs, w.scratch, st));
-            PH_HIP(scan_excl<uint64_t>(w.offB, w.offB, npairs, w.scratch, st));
-            hipLaunchKernelGGL(map_gather_kernel, dim3(grid_for((uint64_t)npairs * 64)), dim3(BT), 0, st, d_reads, off, h->d_text, w.pread,
-                               w.pfirst, w.cstrand, w.clo, g.C, (uint64_t)npairs, w.offA, w.offB, w.A, w.B);
-            PH_HIP(hipGetLastError());
-            if (af) {
-                if (int rc = k3a::score_pass(sc, af->c, af->go, af->ge, w.A, w.offA, npairs, w.B, w.offB, w.lenB, w.score, w.endA, w.endB,
-                                             w.err, w.band, k3a::grid_blocks(af->c, npairs, w.lenB), st))
-                    return rc;
-            } else if (int rc = polyhip_sw_align_batch_dev(sc, w.A, w.offA, npairs, g.max_len, w.B, w.offB, w.lenB, w.score, w.endA, w.endB,
-                                                           w.err, w.slotA, w.slotB, w.alnLen, w.stride, w.sw_work, w.sw_bytes, w.tb_work,
-                                                           w.tb_bytes, st)) {
-                return rc;
-            }
-        }
+        if (int rc = map_candidates(h, sc, g, af, w, d_reads, off, nr, st, info, &npairs))
+            return rc;
         if (af) {
             // the winner of every read from scores, errs and ranks; then the strings of the winners alone
             hipLaunchKernelGGL(map_reduce_kernel<true>, dim3(grid_for(nr * 64)), dim3(BT), 0, st, w.pfirst, off, nr, g, p->min_score, w.score,
@@ -937,6 +1342,258 @@ int map_host(const char *who, const polyhip_bwt *hp, const polyhip_scoring *sc, 
     return rc;
 }
 
+// ---- polyhip_map_pairs -----------------------------------------------------------------------------------------------------
+constexpr uint32_t MAP_MAX_RESCUE = POLYHIP_MAP_MAX_RESCUE_COLS; // = MAP_MAX_LEN + 3 * MAP_MAX_BAND, the widest candidate window
+
+thread_local polyhip_map_pairs_info t_pinfo{};
+
+// columns of the widest rescue window of a call: max_insert - min_insert + max_len + 2 * band (0 without rescue)
+uint64_t rescue_cols(const polyhip_map_params *p, const polyhip_map_pair_params *pp, uint32_t max_len)
+{
+    if (!pp || !pp->rescue || pp->min_insert > pp->max_insert)
+        return 0;
+    return (uint64_t)(pp->max_insert - pp->min_insert) + max_len + 2ull * p->band;
+}
+
+// The paired call on device pointers: d_reads / d_off hold the mates interleaved (2 * npairs reads).  A sibling of map_run's
+// affine branch: the same candidate pass and the same winners' traceback, with the pair rule and the rescue pass between.
+int pairs_run(const BwtHandle *h, const polyhip_scoring *sc, const polyhip_map_params *p, const PairShape &q, const MapAffine *af,
+              const uint8_t *d_reads, const uint64_t *d_off, uint64_t npairs, uint32_t max_len, const MapOut &o, int64_t *o_tlen,
+              void *d_work, size_t work_bytes, hipStream_t st, uint64_t *needed)
+{
+    const char *who = "polyhip_map_pairs";
+    polyhip_map_info info{};
+    uint64_t traced = 0, attempts = 0;
+    *needed = 0;
+    const bool strings = o.alnA != nullptr;
+    const uint64_t nreads = 2 * npairs;
+    const MapShape g = make_shape(p, h->n, max_len);
+    const uint64_t per = map_chunk_reads(sc, g, af, nreads, d_work ? work_bytes : 0); // MAP_CHUNK reads are 128 pairs
+    PH_REQUIRE(per > 0, "%s: a workspace of %zu bytes does not hold a chunk of %llu pairs (%zu bytes)", who, work_bytes,
+               (unsigned long long)(std::min<uint64_t>(nreads, MAP_CHUNK) / 2),
+               map_carve(sc, g, af, std::min<uint64_t>(nreads, MAP_CHUNK), nullptr, nullptr));
+    MapWork w;
+    (void)map_carve(sc, g, af, per, static_cast<uint8_t *>(d_work), &w);
+    uint64_t *sbase = reinterpret_cast<uint64_t *>(w.cnt + CNT_N);
+    PH_HIP(hipMemsetAsync(w.cnt, 0, (CNT_N + 1) * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(map_diroff_kernel, dim3(grid_for(w.sub)), dim3(BT), 0, st, w.dirOff, w.sub, w.dwords);
+    PH_HIP(hipGetLastError());
+    SyncOnExit sync(st); // counts are read back into locals
+    for (uint64_t r0 = 0; r0 < nreads; r0 += per, ++info.chunks) {
+        const uint64_t nr = std::min(per, nreads - r0), np = nr / 2;
+        const uint64_t *off = d_off + r0;
+        uint32_t ncand = 0;
+        if (int rc = map_candidates(h, sc, g, af, w, d_reads, off, nr, st, info, &ncand))
+            return rc;
+        // the pair rule on scores, errs, ranks and projections; then the rescue windows it asks for, scored
+        hipLaunchKernelGGL(pair_reduce_kernel, dim3(grid_for(np * 64)), dim3(BT), 0, st, w.pfirst, off, np, g, q, p->min_score, w.score,
+                           w.endA, w.endB, w.err, w.cstrand, w.clo, o.err + r0, w.choice, w.proper, w.ptlen, w.rfirst, w.rstrand, w.rlo,
+                           w.rhi);
+        PH_HIP(hipGetLastError());
+        uint32_t nreq = 0;
+        PH_HIP(scan_excl<uint32_t>(w.rfirst, w.rfirst, nr, w.scratch, st));
+        if (q.rescue) {
+            PH_HIP(hipMemcpyAsync(&nreq, w.rfirst + nr, sizeof nreq, hipMemcpyDeviceToHost, st));
+            PH_HIP(hipStreamSynchronize(st));
+        }
+        attempts += nreq;
+        if (nreq) { // a chunk without a request launches no rescue pass
+            hipLaunchKernelGGL(rescue_plan_kernel, dim3(grid_for(nr)), dim3(BT), 0, st, w.rfirst, off, nr, w.rlo, w.rhi, w.rread, w.roffA,
+                               w.roffB);
+            PH_HIP(hipGetLastError());
+            PH_HIP(scan_excl<uint64_t>(w.roffA, w.roffA, nreq, w.scratch, st));
+            PH_HIP(scan_excl<uint64_t>(w.roffB, w.roffB, nreq, w.scratch, st));
+            hipLaunchKernelGGL(rescue_gather_kernel, dim3(grid_for((uint64_t)nreq * 64)), dim3(BT), 0, st, d_reads, off, h->d_text, w.rread,
+                               w.rstrand, w.rlo, (uint64_t)nreq, w.roffA, w.roffB, w.rA, w.rB);
+            PH_HIP(hipGetLastError());
+            if (int rc = k3a::score_pass(sc, af->c, af->go, af->ge, w.rA, w.roffA, nreq, w.rB, w.roffB, w.lenW, w.rscore, w.rendA, w.rendB,
+                                         w.rerr, w.band, k3a::grid_blocks(af->c, nreq, w.lenW), st))
+                return rc;
+        }
+        hipLaunchKernelGGL(pair_resolve_kernel, dim3(grid_for(np * 64)), dim3(BT), 0, st, w.pfirst, off, np, g, q, p->min_score, w.score,
+                           w.endA, w.endB, w.cvotes, w.cstrand, w.clo, w.choice, w.proper, w.ptlen, w.rfirst, w.rstrand, w.rlo, w.rscore,
+                           w.rendA, w.rendB, w.rerr, o.score + r0, o.second + r0, o.flags + r0, o.votes + r0, o.ref_start + r0,
+                           o.ref_end + r0, o.read_start + r0, o.read_end + r0, o_tlen + r0 / 2, w.soff, w.best, w.wfirst, w.cnt);
+        PH_HIP(hipGetLastError());
+        uint32_t nwin = 0;
+        PH_HIP(scan_excl<uint32_t>(w.wfirst, w.wfirst, nr, w.scratch, st));
+        PH_HIP(hipMemcpyAsync(&nwin, w.wfirst + nr, sizeof nwin, hipMemcpyDeviceToHost, st));
+        PH_HIP(hipStreamSynchronize(st));
+        traced += nwin;
+        if (nwin) { // a chunk without a mapped mate launches no traceback
+            hipLaunchKernelGGL(pair_winners_kernel, dim3(grid_for(nr)), dim3(BT), 0, st, w.wfirst, w.best, nr, w.offA, w.offB, w.score,
+                               w.endA, w.endB, w.roffA, w.roffB, w.rscore, w.rendA, w.rendB, w.wsrc, w.woffA, w.woffB, w.wscore, w.wendA,
+                               w.wendB, w.werr);
+            PH_HIP(hipGetLastError());
+            PH_HIP(scan_excl<uint64_t>(w.woffA, w.woffA, nwin, w.scratch, st));
+            PH_HIP(scan_excl<uint64_t>(w.woffB, w.woffB, nwin, w.scratch, st));
+            hipLaunchKernelGGL(pair_wgather_kernel, dim3(grid_for((uint64_t)nwin * 64)), dim3(BT), 0, st, w.wsrc, (uint64_t)nwin, w.offA,
+                               w.offB, w.A, w.B, w.roffA, w.roffB, w.rA, w.rB, w.woffA, w.woffB, w.wA, w.wB);
+            PH_HIP(hipGetLastError());
+            for (uint64_t i0 = 0; i0 < nwin; i0 += w.sub) {
+                const uint64_t m = std::min<uint64_t>(w.sub, nwin - i0);
+                if (int rc = k3a::traceback_pass(sc, af->c, af->go, af->ge, w.wA, w.woffA + i0, m, w.wB, w.woffB + i0, w.lenW,
+                                                 w.wscore + i0, w.wendA + i0, w.wendB + i0, w.werr + i0, w.dirOff, w.dir, w.band,
+                                                 w.lenW, k3a::grid_blocks(af->c, m, w.lenW), w.slotA + i0 * w.stride,
+                                                 w.slotB + i0 * w.stride, w.wlen + i0, w.stride, st))
+                    return rc;
+            }
+            hipLaunchKernelGGL(map_finish_kernel, dim3(grid_for(nr * 64)), dim3(BT), 0, st, w.wfirst, nr, w.wlen, w.slotA, w.slotB, w.stride,
+                               w.wscore, w.wendA, w.wendB, (int)sc->smax, af->ge, o.ref_end + r0, o.read_end + r0, o.ref_start + r0,
+                               o.read_start + r0, w.soff, w.best, w.cnt);
+            PH_HIP(hipGetLastError());
+        }
+        if (strings) {
+            PH_HIP(scan_excl<uint64_t>(w.soff, w.soff, nr, w.scratch, st));
+            hipLaunchKernelGGL(map_strings_kernel, dim3(grid_for(nr * 64)), dim3(BT), 0, st, w.soff, w.best, nr, w.slotA, w.slotB, w.stride,
+                               sbase, o.alnOff + r0, o.alnA, o.alnB, o.capacity);
+            PH_HIP(hipGetLastError());
+            hipLaunchKernelGGL(map_advance_kernel, dim3(1), dim3(64), 0, st, sbase, w.soff + nr, o.alnOff + nreads);
+            PH_HIP(hipGetLastError());
+        }
+    }
+    unsigned long long cnt[CNT_N + 1];
+    PH_HIP(hipMemcpyAsync(cnt, w.cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
+    PH_HIP(hipStreamSynchronize(st));
+    t_pinfo = polyhip_map_pairs_info{cnt[CNT_SEEDS], cnt[CNT_OVER], info.hits, cnt[CNT_CLUSTERS], info.pairs_aligned, cnt[CNT_MAPPED],
+                                     cnt[CNT_PROPER], attempts, cnt[CNT_RESCUED], traced, info.chunks};
+    *needed = cnt[CNT_N];
+    if (strings && *needed > o.capacity)
+        return set_error(POLYHIP_ERR_INVALID, "%s: the aligned strings need %llu bytes, the buffers hold %llu", who,
+                         (unsigned long long)*needed, (unsigned long long)o.capacity);
+    return POLYHIP_OK;
+}
+
+int pairs_host(const polyhip_bwt *hp, const polyhip_scoring *sc, const polyhip_map_params *p, const polyhip_map_pair_params *pp,
+               int64_t go, int64_t ge, const uint8_t *reads1, const uint64_t *off1, const uint8_t *reads2, const uint64_t *off2,
+               uint64_t npairs, uint32_t max_len, uint64_t work_limit, int64_t *score, int64_t *second, uint32_t *flags, uint32_t *votes,
+               uint32_t *ref_start, uint32_t *ref_end, uint32_t *read_start, uint32_t *read_end, uint32_t *err, int64_t *tlen,
+               uint8_t *alnA, uint8_t *alnB, uint64_t *alnOff, uint64_t aln_capacity)
+{
+    const char *who = "polyhip_map_pairs";
+    if (int rc = validate(who, hp, sc, p, max_len))
+        return rc;
+    const bool strings = alnA != nullptr;
+    uint64_t nb1 = 0, nb2 = 0;
+    if (npairs) {
+        PH_REQUIRE(off1 && off2 && score && second && flags && votes && ref_start && ref_end && read_start && read_end && err && tlen,
+                   "%s: null argument", who);
+        PH_REQUIRE(!strings || (alnB && alnOff), "%s: alnA without alnB / alnOff", who);
+        for (uint64_t i = 0; i < npairs; ++i)
+            PH_REQUIRE(off1[i] <= off1[i + 1] && off2[i] <= off2[i + 1], "%s: offsets are not ascending at %llu", who,
+                       (unsigned long long)i);
+        nb1 = off1[npairs] - off1[0];
+        nb2 = off2[npairs] - off2[0];
+        PH_REQUIRE((reads1 || nb1 == 0) && (reads2 || nb2 == 0), "%s: null read buffer", who);
+    }
+    if (!(go <= ge && ge <= -1))
+        return set_error(POLYHIP_ERR_UNSUPPORTED, "%s: gap_open %lld, gap_extend %lld: need gap_open <= gap_extend <= -1", who,
+                         (long long)go, (long long)ge);
+    // the affine kernel's int32 cells at the wider of the mapping window and the rescue window
+    const uint64_t wide = rescue_cols(p, pp, max_len);
+    const int64_t absmax = std::max<int64_t>(std::max<int64_t>(std::llabs((long long)sc->smin), std::llabs((long long)sc->smax)), -go);
+    const int64_t cols = std::max<int64_t>((int64_t)max_len + 3 * (int64_t)p->band, (int64_t)wide);
+    const int64_t span = (int64_t)max_len + cols, range = 1ll << 30;
+    if (absmax >= range || absmax * span >= range)
+        return set_error(POLYHIP_ERR_UNSUPPORTED,
+                         "%s: scores could leave the int32 cells (|s|max %lld, max_len %u, widest window %lld columns: |s|max * (max_len "
+                         "+ columns) must stay below 2^30)",
+                         who, (long long)absmax, max_len, (long long)cols);
+    PH_REQUIRE(pp, "%s: null pair parameters", who);
+    PH_REQUIRE(p->both_strands, "%s: both_strands must be set (a proper pair has one mate on each strand)", who);
+    PH_REQUIRE(pp->min_insert <= pp->max_insert, "%s: min_insert %u exceeds max_insert %u", who, pp->min_insert, pp->max_insert);
+    PH_REQUIRE(pp->rescue <= 1, "%s: rescue must be 0 or 1", who);
+    if (wide > MAP_MAX_RESCUE)
+        return set_error(POLYHIP_ERR_UNSUPPORTED,
+                         "%s: a rescue window of max_insert - min_insert + max_len + 2 * band = %llu columns exceeds %u", who,
+                         (unsigned long long)wide, MAP_MAX_RESCUE);
+    if (npairs == 0) {
+        if (alnOff)
+            alnOff[0] = 0;
+        t_pinfo = polyhip_map_pairs_info{};
+        return POLYHIP_OK;
+    }
+    PH_REQUIRE(npairs < (1ull << 31), "%s: %llu pairs exceed 2^31 - 1", who, (unsigned long long)npairs);
+    const BwtHandle *h = as_h(hp);
+    DeviceScope ds;
+    PH_HIP(ds.enter(h->dev));
+    hipStream_t st = h->stream;
+    MapAffine aff{};
+    aff.go = (int)go;
+    aff.ge = (int)ge;
+    aff.pairs = true;
+    aff.wide = (uint32_t)wide;
+    int cus = 0;
+    PH_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->dev));
+    aff.c = k3a::choose(sc, cus);
+    const PairShape q{(int64_t)pp->min_insert, (int64_t)pp->max_insert, pp->rescue};
+    const uint64_t nreads = 2 * npairs, nbytes = nb1 + nb2;
+    size_t wb = map_workspace(sc, make_shape(p, h->n, max_len), &aff, nreads);
+    if (work_limit && work_limit < wb)
+        wb = work_limit;
+    // the mates as they came, the interleaved batch, and the outputs in one block: two int64 and seven uint32 per mate, the
+    // string offsets, an int64 per pair
+    DevBuf din, dinoff, dreads, doff, dscan, dout, dA, dB, dwork;
+    PH_HIP(din.alloc(nbytes + 64));
+    PH_HIP(dinoff.alloc(2 * (npairs + 1) * sizeof(uint64_t)));
+    PH_HIP(dreads.alloc(nbytes + 64));
+    PH_HIP(doff.alloc((nreads + 1) * sizeof(uint64_t)));
+    PH_HIP(dscan.alloc(scan_scratch_bytes<uint64_t>(nreads)));
+    PH_HIP(dout.alloc(nreads * (2 * 8 + 7 * 4) + (nreads + 1) * 8 + npairs * 8));
+    if (strings) {
+        PH_HIP(dA.alloc(aln_capacity));
+        PH_HIP(dB.alloc(aln_capacity));
+    }
+    PH_HIP(dwork.alloc(wb));
+    std::vector<uint64_t> rebased(2 * (npairs + 1));
+    for (uint64_t i = 0; i <= npairs; ++i) {
+        rebased[i] = off1[i] - off1[0];
+        rebased[npairs + 1 + i] = off2[i] - off2[0];
+    }
+    SyncOnExit sync(st);
+    uint8_t *d1 = din.as<uint8_t>(), *d2 = d1 + nb1;
+    if (nb1)
+        PH_HIP(hipMemcpyAsync(d1, reads1 + off1[0], nb1, hipMemcpyHostToDevice, st));
+    if (nb2)
+        PH_HIP(hipMemcpyAsync(d2, reads2 + off2[0], nb2, hipMemcpyHostToDevice, st));
+    uint64_t *do1 = dinoff.as<uint64_t>(), *do2 = do1 + npairs + 1;
+    PH_HIP(hipMemcpyAsync(do1, rebased.data(), rebased.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(pair_lens_kernel, dim3(grid_for(npairs)), dim3(BT), 0, st, do1, do2, npairs, doff.as<uint64_t>());
+    PH_HIP(hipGetLastError());
+    PH_HIP(scan_excl<uint64_t>(doff.as<uint64_t>(), doff.as<uint64_t>(), nreads, dscan.as<uint8_t>(), st));
+    hipLaunchKernelGGL(pair_interleave_kernel, dim3(grid_for(nreads * 64)), dim3(BT), 0, st, d1, do1, d2, do2, nreads, doff.as<uint64_t>(),
+                       dreads.as<uint8_t>());
+    PH_HIP(hipGetLastError());
+    int64_t *d64 = dout.as<int64_t>();
+    int64_t *dtl = d64 + 2 * nreads;
+    uint64_t *dao = reinterpret_cast<uint64_t *>(dtl + npairs);
+    uint32_t *d32 = reinterpret_cast<uint32_t *>(dao + nreads + 1);
+    const MapOut o{d64, d64 + nreads, d32, d32 + nreads, d32 + 2 * nreads, d32 + 3 * nreads, d32 + 4 * nreads, d32 + 5 * nreads,
+                   d32 + 6 * nreads, strings ? dA.as<uint8_t>() : nullptr, strings ? dB.as<uint8_t>() : nullptr, strings ? dao : nullptr,
+                   aln_capacity};
+    uint64_t needed = 0;
+    const int rc = pairs_run(h, sc, p, q, &aff, dreads.as<uint8_t>(), doff.as<uint64_t>(), npairs, max_len, o, dtl, dwork.p, wb, st, &needed);
+    if (rc != POLYHIP_OK && !(strings && needed > aln_capacity))
+        return rc;
+    // (a call whose only failure is the strings' capacity still delivers everything else)
+    uint32_t *const h32[7] = {flags, votes, ref_start, ref_end, read_start, read_end, err};
+    PH_HIP(hipMemcpyAsync(score, o.score, nreads * 8, hipMemcpyDeviceToHost, st));
+    PH_HIP(hipMemcpyAsync(second, o.second, nreads * 8, hipMemcpyDeviceToHost, st));
+    PH_HIP(hipMemcpyAsync(tlen, dtl, npairs * 8, hipMemcpyDeviceToHost, st));
+    for (int k = 0; k < 7; ++k)
+        PH_HIP(hipMemcpyAsync(h32[k], d32 + k * nreads, nreads * 4, hipMemcpyDeviceToHost, st));
+    if (strings) {
+        PH_HIP(hipMemcpyAsync(alnOff, dao, (nreads + 1) * 8, hipMemcpyDeviceToHost, st));
+        const uint64_t fit = std::min(needed, aln_capacity);
+        if (fit) {
+            PH_HIP(hipMemcpyAsync(alnA, dA.p, fit, hipMemcpyDeviceToHost, st));
+            PH_HIP(hipMemcpyAsync(alnB, dB.p, fit, hipMemcpyDeviceToHost, st));
+        }
+    }
+    PH_HIP(hipStreamSynchronize(st));
+    return rc;
+}
+
 } // namespace
 } // namespace polyhip
 
@@ -987,6 +1644,23 @@ int polyhip_map_reads_affine(const polyhip_bwt *hp, const polyhip_scoring *sc, c
     const int64_t gaps[2] = {gap_open, gap_extend};
     return map_host("polyhip_map_reads_affine", hp, sc, p, gaps, work_limit, reads, off, nreads, max_len, score, second, flags, votes,
                     ref_start, ref_end, read_start, read_end, err, alnA, alnB, alnOff, aln_capacity);
+}
+
+int polyhip_map_pairs(const polyhip_bwt *hp, const polyhip_scoring *sc, const polyhip_map_params *p, const polyhip_map_pair_params *pp,
+                      int64_t gap_open, int64_t gap_extend, const uint8_t *reads1, const uint64_t *off1, const uint8_t *reads2,
+                      const uint64_t *off2, uint64_t npairs, uint32_t max_len, uint64_t work_limit, int64_t *score, int64_t *second,
+                      uint32_t *flags, uint32_t *votes, uint32_t *ref_start, uint32_t *ref_end, uint32_t *read_start, uint32_t *read_end,
+                      uint32_t *err, int64_t *tlen, uint8_t *alnA, uint8_t *alnB, uint64_t *alnOff, uint64_t aln_capacity)
+{
+    return pairs_host(hp, sc, p, pp, gap_open, gap_extend, reads1, off1, reads2, off2, npairs, max_len, work_limit, score, second, flags,
+                      votes, ref_start, ref_end, read_start, read_end, err, tlen, alnA, alnB, alnOff, aln_capacity);
+}
+
+int polyhip_map_pairs_last_info(polyhip_map_pairs_info *info)
+{
+    PH_REQUIRE(info, "polyhip_map_pairs_last_info: null argument");
+    *info = t_pinfo;
+    return POLYHIP_OK;
 }
 
 int polyhip_map_affine_last_info(polyhip_map_affine_info *info)

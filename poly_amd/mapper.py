@@ -68,6 +68,7 @@ class MapResult:
     alignB: list | None
     aln_off: np.ndarray | None = None
     status: int = 0
+    tlen: np.ndarray | None = None      # map_pairs_packed only: one entry per pair
 
 
 @dataclass
@@ -104,11 +105,13 @@ def workspace_bytes(index, scoring, params: MapParams, nreads: int, max_len: int
 
 
 def _packed(call, buf: np.ndarray, offs: np.ndarray, params: MapParams | None, strings: bool, capacity: int | None,
-            max_len: int | None) -> MapResult:
+            max_len: int | None, per_read: int = 1) -> MapResult:
     """what the host-pointer entry points share: the output arrays, the retry with the exact string capacity, the strings as
-    lists.  call(params, reads, offs, n, max_len, *outputs, capacity) -> status"""
+    lists.  call(params, reads, offs, n, max_len, *outputs, capacity) -> status.  per_read: output entries per read of
+    ``offs`` (2 for pairs, whose second batch the caller holds)"""
     params = params or MapParams()
-    n = len(offs) - 1
+    nin = len(offs) - 1
+    n = nin * per_read
     buf = np.ascontiguousarray(buf, dtype=np.uint8)
     offs = np.ascontiguousarray(offs, dtype=np.uint64)
     if max_len is None:
@@ -117,13 +120,13 @@ def _packed(call, buf: np.ndarray, offs: np.ndarray, params: MapParams | None, s
     score, second = np.zeros(n, np.int64), np.zeros(n, np.int64)
     u32 = [np.zeros(n, np.uint32) for _ in range(7)]
     off = np.zeros(n + 1, np.uint64)
-    cap = int(capacity) if capacity is not None else int(int(offs[n] - offs[0]) * 1.25) + (64 << 10)
+    cap = int(capacity) if capacity is not None else int(int(offs[nin] - offs[0]) * 1.25 * per_read) + (64 << 10)
     alnA = alnB = None
     rc = _lib.OK
     for _ in range(2):
         if strings:
             alnA, alnB = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.uint8)
-        rc = call(C.byref(p), buf.ctypes.data, offs.ctypes.data, n, int(max_len),
+        rc = call(C.byref(p), buf.ctypes.data, offs.ctypes.data, nin, int(max_len),
                   score.ctypes.data, second.ctypes.data, *[a.ctypes.data for a in u32],
                   alnA.ctypes.data if strings else None, alnB.ctypes.data if strings else None, off.ctypes.data if strings else None, cap)
         if strings and rc == _lib.ERR_INVALID and _strings_short():  # the strings did not fit: off[n] says what they need
@@ -191,6 +194,86 @@ def MapReadsAffine(index, scoring, reads, gap_open: int, gap_extend: int, params
     return [MapRecord(bool(r.flags[i] & FLAG_MAPPED), bool(r.flags[i] & FLAG_REVERSE), int(r.score[i]), int(r.second[i]),
                       int(r.votes[i]), int(r.ref_start[i]), int(r.ref_end[i]), int(r.read_start[i]), int(r.read_end[i]),
                       conv(r.alignA[i]), conv(r.alignB[i]), int(r.err[i])) for i in range(len(reads))]
+
+
+# ---- paired-end reads (polyhip_map_pairs; host pointers only) ---------------------------------------------------------------
+FLAG_PROPER, FLAG_RESCUED = 4, 8
+
+
+class _CPairParams(C.Structure):
+    _fields_ = [("min_insert", C.c_uint32), ("max_insert", C.c_uint32), ("rescue", C.c_uint32)]
+
+
+class _CPairsInfo(C.Structure):
+    _fields_ = [("seeds", C.c_uint64), ("seeds_over_max_occ", C.c_uint64), ("hits", C.c_uint64), ("clusters", C.c_uint64),
+                ("pairs_aligned", C.c_uint64), ("reads_mapped", C.c_uint64), ("proper_pairs", C.c_uint64),
+                ("rescue_attempts", C.c_uint64), ("rescued", C.c_uint64), ("pairs_traced", C.c_uint64), ("chunks", C.c_uint32)]
+
+
+@dataclass
+class PairParams:
+    """polyhip_map_pair_params: the inserts (outer distance of a forward-reverse pair) that make a pair proper, and whether a
+    mate without a placement of its own is searched for in the window its partner implies"""
+    min_insert: int
+    max_insert: int
+    rescue: bool = True
+
+    def _c(self) -> _CPairParams:
+        return _CPairParams(int(self.min_insert), int(self.max_insert), int(self.rescue))
+
+
+def last_pairs_info() -> dict:
+    """polyhip_map_pairs_last_info: what the calling thread's last paired call did"""
+    info = _CPairsInfo()
+    _lib.check(_lib.lib().polyhip_map_pairs_last_info(C.byref(info)))
+    return {name: int(getattr(info, name)) for name, _ in _CPairsInfo._fields_}
+
+
+def map_pairs_packed(index, scoring, gap_open: int, gap_extend: int, buf1: np.ndarray, offs1: np.ndarray, buf2: np.ndarray,
+                     offs2: np.ndarray, params: MapParams | None = None, pair_params: PairParams | None = None, strings: bool = True,
+                     capacity: int | None = None, max_len: int | None = None, work_limit: int = 0) -> MapResult:
+    """Mate i of (buf1, offs1) with mate i of (buf2, offs2) -> a MapResult of 2n entries (2i: mate 1 of pair i, 2i + 1: mate
+    2) whose ``tlen`` has one entry per pair: the insert of a proper pair, else 0.  ``pair_params`` is required; the other
+    arguments are map_reads_affine_packed's."""
+    if pair_params is None:
+        raise ValueError("map_pairs_packed: pair_params is required")
+    n = len(offs1) - 1
+    if len(offs2) - 1 != n:
+        raise ValueError("map_pairs_packed: the two batches hold different numbers of reads")
+    buf2 = np.ascontiguousarray(buf2, dtype=np.uint8)
+    offs2 = np.ascontiguousarray(offs2, dtype=np.uint64)
+    if max_len is None:
+        max_len = max((int(np.diff(o.astype(np.int64)).max()) for o in (np.asarray(offs1), offs2)), default=0) if n else 0
+    pp = pair_params._c()
+    tlen = np.zeros(n, np.int64)
+
+    def call(p, reads, off, n_, max_len_, *rest):
+        per_mate, tail = rest[:9], rest[9:]
+        return _lib.lib().polyhip_map_pairs(index.handle(), scoring.handle(), p, C.byref(pp), int(gap_open), int(gap_extend), reads, off,
+                                            buf2.ctypes.data, offs2.ctypes.data, n_, max_len_, int(work_limit), *per_mate,
+                                            tlen.ctypes.data, *tail)
+    r = _packed(call, buf1, offs1, params, strings, capacity, max_len, per_read=2)
+    r.tlen = tlen
+    return r
+
+
+def MapPairs(index, scoring, reads1, reads2, gap_open: int, gap_extend: int, pair_params: PairParams,
+             params: MapParams | None = None) -> list:
+    """Every pair (reads1[i], reads2[i]) placed on the index's text -> list of (MapRecord, MapRecord, proper, tlen)"""
+    if len(reads1) != len(reads2):
+        raise ValueError("MapPairs: reads1 and reads2 differ in length")
+    both = list(reads1) + list(reads2)
+    as_str = bool(both) and all(isinstance(r, str) for r in both)
+    buf1, offs1 = _pack(reads1)
+    buf2, offs2 = _pack(reads2)
+    r = map_pairs_packed(index, scoring, gap_open, gap_extend, buf1, offs1, buf2, offs2, params, pair_params)
+    conv = (lambda b: b.decode("latin-1")) if as_str else (lambda b: b)
+
+    def rec(i):
+        return MapRecord(bool(r.flags[i] & FLAG_MAPPED), bool(r.flags[i] & FLAG_REVERSE), int(r.score[i]), int(r.second[i]),
+                         int(r.votes[i]), int(r.ref_start[i]), int(r.ref_end[i]), int(r.read_start[i]), int(r.read_end[i]),
+                         conv(r.alignA[i]), conv(r.alignB[i]), int(r.err[i]))
+    return [(rec(2 * i), rec(2 * i + 1), bool(r.flags[2 * i] & FLAG_PROPER), int(r.tlen[i])) for i in range(len(reads1))]
 
 
 # ---- device-resident entry point (torch CUDA tensors) ---------------------------------------------------------------------

@@ -31,6 +31,24 @@ COMP = np.zeros(256, np.uint8)
 COMP[list(b"ACGT")] = list(b"TGCA")
 
 
+def mutate_windows(rng, src, m, sub=0.05, indel=0.01):
+    """(k, span) uint8 windows -> (k, m): substitutions, deleted bases and inserted ones, then the first m bytes of each"""
+    k, span = src.shape
+    hit = rng.random(src.shape) < sub
+    src[hit] = ACGT[(np.searchsorted(ACGT, src[hit]) + rng.integers(1, 4, int(hit.sum()))) & 3]
+    u = rng.random(src.shape)
+    copies = np.where(u < indel / 2, 0, np.where(u < indel, 2, 1))          # deleted / an inserted base in front / kept
+    flat = np.repeat(src.reshape(-1), copies.reshape(-1))
+    row = np.repeat(np.repeat(np.arange(k), span), copies.reshape(-1))
+    first = np.concatenate([[0], np.cumsum(copies.sum(1))[:-1]])
+    rank = np.arange(len(flat)) - first[row]
+    ins = np.zeros(len(flat), bool)
+    ins[np.nonzero(np.repeat(copies.reshape(-1), copies.reshape(-1)) == 2)[0][::2]] = True
+    flat[ins] = ACGT[rng.integers(0, 4, int(ins.sum()))]
+    keep = rank < m
+    return flat[keep].reshape(k, m)
+
+
 def make_reads(rng, g, nreads, m=150, sub=0.05, indel=0.01, block=100_000):
     """(nreads, m) uint8: windows of g with errors, odd rows reverse-complemented"""
     out = np.empty((nreads, m), np.uint8)
@@ -38,19 +56,7 @@ def make_reads(rng, g, nreads, m=150, sub=0.05, indel=0.01, block=100_000):
     for r0 in range(0, nreads, block):
         k = min(block, nreads - r0)
         src = g[rng.integers(0, len(g) - span, k)[:, None] + np.arange(span)]
-        hit = rng.random(src.shape) < sub
-        src[hit] = ACGT[(np.searchsorted(ACGT, src[hit]) + rng.integers(1, 4, int(hit.sum()))) & 3]
-        u = rng.random(src.shape)
-        copies = np.where(u < indel / 2, 0, np.where(u < indel, 2, 1))          # deleted / an inserted base in front / kept
-        flat = np.repeat(src.reshape(-1), copies.reshape(-1))
-        row = np.repeat(np.repeat(np.arange(k), span), copies.reshape(-1))
-        first = np.concatenate([[0], np.cumsum(copies.sum(1))[:-1]])
-        rank = np.arange(len(flat)) - first[row]
-        ins = np.zeros(len(flat), bool)
-        ins[np.nonzero(np.repeat(copies.reshape(-1), copies.reshape(-1)) == 2)[0][::2]] = True
-        flat[ins] = ACGT[rng.integers(0, 4, int(ins.sum()))]
-        keep = rank < m
-        out[r0:r0 + k] = flat[keep].reshape(k, m)
+        out[r0:r0 + k] = mutate_windows(rng, src, m, sub, indel)
     out[1::2] = COMP[out[1::2, ::-1]]
     return out
 
