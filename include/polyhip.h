@@ -1067,6 +1067,68 @@ int polyhip_map_pairs(const polyhip_bwt *h, const polyhip_scoring *sc,
                       uint8_t *alnA, uint8_t *alnB, uint64_t *alnOff, uint64_t aln_capacity);
 int polyhip_map_pairs_last_info(polyhip_map_pairs_info *info);
 
+/* ---- the mapper's output as alignment records: CIGAR, NM, MD, MAPQ, SAM FLAG (no counterpart in the reference) ---- */
+/*
+ * polyhip_aln_records turns what polyhip_map_reads, polyhip_map_reads_affine or polyhip_map_pairs returned for n entries
+ * (reads, or mates in the order 2i, 2i + 1) into the fields of a SAM record.  It is a pass over those arrays: it places
+ * nothing and needs no index.  read_len[i] is the length of read i, which the mapper's caller holds.  For entry i the
+ * columns are c in [alnOff[i], alnOff[i + 1]) with a = alnA[c] (the oriented read q) and b = alnB[c] (the text window).
+ *  Column class: a == '-' and b == '-' is invalid; a == '-' only is D (deletion from the text); b == '-' only is I
+ *   (insertion); a == b is '='; anything else is X.  Bytes are compared raw, no case is folded.
+ *  err[i], the first that applies, for entries with flags bit 0 (mapped) only; an unmapped entry gets 0 and its strings are
+ *   never read:  4 = more than POLYHIP_ALN_MAX_COLUMNS = 2^28 - 1 columns (a BAM CIGAR length has 28 bits); this one is
+ *   decided from the offsets alone, before any column is read, so such an entry is 4 whatever its columns hold;  1 = an
+ *   invalid column;  2 = read_start > read_end, or read_end > read_len, or the number of columns with a != '-' differs from
+ *   read_end - read_start;  3 = no columns.
+ *  Live: flags bit 0 is set and err[i] == 0.  An entry that is not live gets no CIGAR entries, no MD bytes (zero bytes, not
+ *   "0"), nm = 0 and mapq = 0.
+ *  CIGAR, as BAM stores it: uint32 len << 4 | op with M = 0, I = 1, D = 2, S = 4, '=' = 7, X = 8.  First (read_start, S) if
+ *   read_start > 0; then one entry per maximal run of columns of one class, where with eqx == 0 the classes '=' and X are
+ *   one class M; last (read_len - read_end, S) if that is positive.  Coordinates are those of q, as the mapper reports them:
+ *   SAM's convention for a record on the reverse strand.  A clip keeps the low 28 bits of its length.
+ *  nm = the number of X, I and D columns.
+ *  MD, in samtools' form: with a counter k = 0 over the columns in order, an I column is skipped; '=' adds one to k; X
+ *   writes k in decimal and the byte b, then k = 0; the first column of a maximal run of D columns (maximal among all
+ *   columns, so an I column between two D columns separates two runs) writes k, '^' and b, then k = 0, and every further
+ *   column of the run writes its b; the end writes k.  Adjacent mismatches give ..A0C.., a deletion followed at once by a
+ *   mismatch ^AC0T, the columns D I D ^A0^C.  The MD of a live entry is never empty.
+ *  mapq: with s = score and t = max(second, 0): 0 if t >= s, else min(60, floor(60 * (s - t) / s)) in signed 64-bit integers
+ *   (s below 2^57).  This is a stated convention, not a calibrated quality: nobody has measured how its values relate to
+ *   the probability that a placement is wrong.
+ *  sam_flag: 0x4 if the entry is not live; 0x10 if it is live and flags bit 1 (reverse) is set.  With paired != 0 the mate
+ *   of entry i is entry i ^ 1 and further: 0x1 always; 0x2 if flags bit 2 (proper) is set and both mates are live; 0x8 if
+ *   the mate is not live; 0x20 if the mate is live and its flags bit 1 is set; 0x40 for even i, 0x80 for odd i.
+ * Packing and capacity are polyhip_bwt_locate's: cigar_off[0..n] and md_off[0..n] are the exclusive scans of the entries'
+ * CIGAR entries and MD bytes and are always filled, as are nm, mapq, sam_flag and err; entry i's CIGAR is cigar[cigar_off[i]
+ * .. cigar_off[i + 1]), its MD md[md_off[i] .. md_off[i + 1]) (no terminator).  If cigar_off[n] > cigar_capacity or md_off[n]
+ * > md_capacity nothing is written to cigar or md and the call fails with POLYHIP_ERR_INVALID naming both sizes needed;
+ * cigar == NULL or md == NULL with a capacity of 0 asks for the sizes only.  No device buffer for either is allocated
+ * before that check.
+ * Errors, in this order, all POLYHIP_ERR_INVALID: a NULL params; eqx > 1 or paired > 1, naming the field; paired != 0 with
+ * an odd n; with n > 0 a NULL array (alnA and alnB may be NULL when alnOff[n] == alnOff[0]; cigar, md as above); alnOff
+ * not ascending.  n == 0 is an empty, successful call: cigar_off[0] = md_off[0] = 0 where those are not NULL.
+ * Host pointers only, no stream: the call copies the arrays in, runs on the calling thread's current device and copies
+ * the records out; nothing that depends on n is allocated before the checks above; the device list does not apply.
+ * polyhip_aln_records_last_info: the calling thread's last call: entries = n; mapped = live entries; columns = the columns
+ * of the live entries; cigar_ops = cigar_off[n]; md_bytes = md_off[n]; bad = entries with err != 0.
+ */
+#define POLYHIP_ALN_MAX_COLUMNS 0x0FFFFFFFu
+typedef struct polyhip_aln_records_params {
+    uint32_t eqx, paired;
+} polyhip_aln_records_params;
+typedef struct polyhip_aln_records_info {
+    uint64_t entries, mapped, columns, cigar_ops, md_bytes, bad;
+} polyhip_aln_records_info;
+int polyhip_aln_records(const polyhip_aln_records_params *params, uint64_t n,
+                        const uint32_t *flags, const int64_t *score, const int64_t *second,
+                        const uint32_t *read_start, const uint32_t *read_end,
+                        const uint32_t *read_len, const uint8_t *alnA, const uint8_t *alnB,
+                        const uint64_t *alnOff, uint64_t *cigar_off, uint32_t *cigar,
+                        uint64_t cigar_capacity, uint64_t *md_off, uint8_t *md,
+                        uint64_t md_capacity, uint32_t *nm, uint8_t *mapq, uint32_t *sam_flag,
+                        uint32_t *err);
+int polyhip_aln_records_last_info(polyhip_aln_records_info *info);
+
 /* ---- R1: the path's one collective -- all-gather of per-rank sketches (RCCL over xGMI) ---- */
 /*
  * For hosts without torch.distributed (the Go/cgo drop-in); one process per GPU.  RCCL is

@@ -143,6 +143,9 @@ SIGNATURES = {
     "polyhip_map_pairs": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64]),
     "polyhip_map_pairs_last_info": (C.c_int, [_vp]),
+    "polyhip_aln_records": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp,
+                                      _vp, _vp]),
+    "polyhip_aln_records_last_info": (C.c_int, [_vp]),
     "polyhip_comm_unique_id": (C.c_int, [_vp]),
     "polyhip_comm_init_rank": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "polyhip_comm_destroy": (C.c_int, [_vp]),

@@ -5,6 +5,10 @@ tests/map_oracle.py restates it on the CPU.  Everything is computed in HIP (poly
 
 Reads are Go strings, i.e. bytes: a ``str`` is taken one byte per character (latin-1), and ``MapReads`` returns aligned
 strings as ``str`` when the reads were ``str`` (``bytes`` otherwise), as poly_amd.bwt does.
+
+What tools downstream of a mapper read -- CIGAR, NM, MD, a mapping quality, the SAM FLAG word, SAM text -- is made from a
+``MapResult`` by poly_amd.sam (``sam.records``, ``sam.write``; polyhip_aln_records), a pass over the arrays and strings
+returned here.
 """
 from __future__ import annotations
 
