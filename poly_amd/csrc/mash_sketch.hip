@@ -1636,11 +1636,18 @@ static Launch plan(uint32_t k, uint32_t s)
     return L;
 }
 
-static unsigned persistent_grid(size_t smem, uint64_t n)
+// The slab pass's grid is this many rounds deep.  A workgroup's reads are its own from the start (read r goes to workgroup
+// r mod grid), so the hardware balances the chip only by when it starts the next workgroup, and behind the last round the
+// CUs drain at a fraction of their rate: over 1M x 10 kb reads the pass takes T (1 + 0.33 / rounds) -- 12.7 ms at 1 round,
+// 11.4 at 2, 10.6 at 4, 10.15 at 8, 10.0 at 16, 9.9 at 32 and no less at 64, 128 or 512, where a workgroup's start (the
+// table, the kernel arguments) begins to show (profiles/k1_grid_depth.log).  100k reads take the same time at 4..64 rounds.
+constexpr uint64_t SLAB_ROUNDS = 32;
+
+static unsigned persistent_grid(size_t smem, uint64_t n, uint64_t rounds = 4)
 {
-    // as many workgroups as fit the chip at once (LDS-limited, <= 8 per CU), a few rounds deep
+    // as many workgroups as fit the chip at once (LDS-limited, <= 8 per CU), `rounds` rounds deep
     const uint64_t per_cu = std::max<uint64_t>(1, std::min<uint64_t>(8, (160 * 1024) / std::max<size_t>(smem, 1)));
-    return (unsigned)std::min<uint64_t>(n, 256 * per_cu * 4);
+    return (unsigned)std::min<uint64_t>(n, 256 * per_cu * rounds);
 }
 
 template <int KS>
@@ -1664,7 +1671,7 @@ static int launch(const uint8_t *d_seqs, const uint64_t *d_offs, uint64_t n, uin
             auto slab = sketch_slab_kernel<KS>;
             PH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(slab), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)L.smem_slab));
-            hipLaunchKernelGGL(slab, dim3(persistent_grid(L.smem_slab, n)), dim3(THREADS), L.smem_slab, st, d_seqs, d_offs, n, s,
+            hipLaunchKernelGGL(slab, dim3(persistent_grid(L.smem_slab, n, SLAB_ROUNDS)), dim3(THREADS), L.smem_slab, st, d_seqs, d_offs, n, s,
                                d_out, L.n_seq_dw, L.n_P_w, L.n_span, L.capw, L.capf_slab, L.nbf_log2_slab);
         }
     }
