@@ -1,0 +1,112 @@
+// cgo binding of the pileup of libpolyhip.so (include/polyhip.h, "pileup of the mapper's output").
+// UNCOMPILED in the authoring image (no Go toolchain).
+package polyhip
+
+/*
+#include "polyhip.h"
+*/
+import "C"
+
+import (
+	"fmt"
+	"unsafe"
+)
+
+// PileupChannels is POLYHIP_PILEUP_CHANNELS: Counts holds that many planes of one uint32 per position of the region.
+const PileupChannels = 16
+
+// PileupParams is polyhip_pileup_params: the region [RegionLo, RegionHi) of the text and the thresholds.
+type PileupParams struct {
+	RegionLo, RegionHi                              uint64
+	MinMapq, MinDepth, MinAltCount, MinAltPermille uint32
+}
+
+// PileupSite is polyhip_pileup_site.  Kind: 1 SNV (Alt is the base), 2 insertion event, 3 deletion event anchored at Pos.
+type PileupSite struct {
+	Pos, Depth, Count, CountFwd uint32
+	Kind, Ref, Alt, Pad         uint8
+}
+
+// PileupInfo is polyhip_pileup_info: what the calling OS thread's last Pileup did.
+type PileupInfo struct {
+	Entries, Used, SkippedMapq, Bad, Columns, EdgeEvents, Sites uint64
+}
+
+// PileupResult: Counts[ch*L+(p-RegionLo)] with ch = 8*strand + k (k = 0..3 A C G T, 4 other, 5 deleted base, 6 insertion
+// events, 7 deletion events); Consensus one byte per position; Sites in ascending position; Errs one value per entry.
+type PileupResult struct {
+	Counts    []uint32
+	Consensus []byte
+	Sites     []PileupSite
+	Errs      []uint32
+}
+
+// Pileup counts what the entries of a MapResult (of MapReads, MapReadsAffine or MapPairs) say about each position of the
+// text ref they were mapped to.  mapq: the Mapq of AlnRecords on the same result, or nil when p.MinMapq is 0.  siteCap:
+// entries of the site buffer; a call that outgrows it runs once more with the size the library reports.
+func Pileup(r *MapResult, mapq []uint8, ref []byte, p PileupParams, siteCap int) (*PileupResult, error) {
+	n := len(r.Flags)
+	if len(r.AlnOff) != n+1 || len(r.RefStart) != n || len(r.RefEnd) != n || (mapq != nil && len(mapq) != n) {
+		return nil, fmt.Errorf("polyhip.Pileup: the arrays hold different numbers of entries")
+	}
+	if p.RegionLo > p.RegionHi || p.RegionHi > uint64(len(ref)) {
+		return nil, fmt.Errorf("polyhip.Pileup: the region [%d, %d) is not inside the text of %d bytes", p.RegionLo, p.RegionHi, len(ref))
+	}
+	var cp C.polyhip_pileup_params
+	cp.region_lo, cp.region_hi = C.uint64_t(p.RegionLo), C.uint64_t(p.RegionHi)
+	cp.min_mapq, cp.min_depth = C.uint32_t(p.MinMapq), C.uint32_t(p.MinDepth)
+	cp.min_alt_count, cp.min_alt_permille = C.uint32_t(p.MinAltCount), C.uint32_t(p.MinAltPermille)
+	pad32 := func(s []uint32) []uint32 { // an empty batch still needs &s[0]
+		if len(s) == 0 {
+			return []uint32{0}
+		}
+		return s
+	}
+	padB := func(s []byte) []byte {
+		if len(s) == 0 {
+			return []byte{0}
+		}
+		return s
+	}
+	flags, refStart, refEnd := pad32(r.Flags), pad32(r.RefStart), pad32(r.RefEnd)
+	alnA, alnB, text := padB(r.AlignA), padB(r.AlignB), padB(ref)
+	var mq *C.uint8_t // nil: no mapq, MinMapq must be 0
+	if len(mapq) > 0 {
+		mq = (*C.uint8_t)(unsafe.Pointer(&mapq[0]))
+	}
+	L := int(p.RegionHi - p.RegionLo)
+	out := &PileupResult{Counts: make([]uint32, PileupChannels*L+1), Consensus: make([]byte, L+1), Errs: make([]uint32, n+1)}
+	var nsites C.uint64_t
+	var err error
+	for attempt := 0; attempt < 2; attempt++ {
+		out.Sites = make([]PileupSite, siteCap+1)
+		err = call(func() C.int {
+			return C.polyhip_pileup((*C.polyhip_pileup_params)(unsafe.Pointer(&cp)), C.uint64_t(n),
+				(*C.uint32_t)(unsafe.Pointer(&flags[0])), (*C.uint8_t)(unsafe.Pointer(mq)),
+				(*C.uint32_t)(unsafe.Pointer(&refStart[0])), (*C.uint32_t)(unsafe.Pointer(&refEnd[0])),
+				(*C.uint8_t)(unsafe.Pointer(&alnA[0])), (*C.uint8_t)(unsafe.Pointer(&alnB[0])),
+				(*C.uint64_t)(unsafe.Pointer(&r.AlnOff[0])), (*C.uint8_t)(unsafe.Pointer(&text[0])), C.uint64_t(len(ref)),
+				(*C.uint32_t)(unsafe.Pointer(&out.Counts[0])), (*C.uint8_t)(unsafe.Pointer(&out.Consensus[0])),
+				(*C.uint64_t)(unsafe.Pointer(&nsites)), (*C.polyhip_pileup_site)(unsafe.Pointer(&out.Sites[0])),
+				C.uint64_t(siteCap), (*C.uint32_t)(unsafe.Pointer(&out.Errs[0])))
+		})
+		if err == nil || uint64(nsites) <= uint64(siteCap) {
+			break
+		}
+		siteCap = int(nsites)
+	}
+	if err != nil {
+		return nil, err
+	}
+	out.Counts, out.Consensus, out.Errs = out.Counts[:PileupChannels*L], out.Consensus[:L], out.Errs[:n]
+	out.Sites = out.Sites[:nsites]
+	return out, nil
+}
+
+// LastPileupInfo must run on the OS thread that made the call (runtime.LockOSThread around both).
+func LastPileupInfo() (PileupInfo, error) {
+	var ci C.polyhip_pileup_info
+	err := call(func() C.int { return C.polyhip_pileup_last_info((*C.polyhip_pileup_info)(unsafe.Pointer(&ci))) })
+	return PileupInfo{Entries: uint64(ci.entries), Used: uint64(ci.used), SkippedMapq: uint64(ci.skipped_mapq), Bad: uint64(ci.bad),
+		Columns: uint64(ci.columns), EdgeEvents: uint64(ci.edge_events), Sites: uint64(ci.sites)}, err
+}

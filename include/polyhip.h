@@ -1129,6 +1129,78 @@ int polyhip_aln_records(const polyhip_aln_records_params *params, uint64_t n,
                         uint32_t *err);
 int polyhip_aln_records_last_info(polyhip_aln_records_info *info);
 
+/* ---- pileup of the mapper's output: per-position counts, consensus, variant sites (integer counts only; no text rows) ---- */
+/*
+ * polyhip_pileup asks what the n entries that polyhip_map_reads, polyhip_map_reads_affine or polyhip_map_pairs returned say
+ * about each position of the text region [region_lo, region_hi), L = region_hi - region_lo.  It is a pass over those
+ * arrays, the mapq of polyhip_aln_records (optional) and the text ref[0, ref_len) itself: it places nothing and needs no
+ * index.  For entry i the columns are c in [alnOff[i], alnOff[i + 1]) with a = alnA[c] (the oriented read, so already in the
+ * text's orientation) and b = alnB[c] (the text byte).  Column classes are those of polyhip_aln_records: a == '-' and
+ * b == '-' is invalid, a == '-' only is D, b == '-' only is I, everything else is a base column; bytes are compared raw.
+ * The text position of a column with b != '-' is ref_start[i] plus the number of earlier columns of the entry with
+ * b != '-'.  The strand is s = flags bit 1.
+ *  Skipped: an entry with flags bit 0 (mapped) and mapq[i] < min_mapq; min_mapq == 0 skips nothing and never reads mapq.
+ *  err[i], the first that applies, for mapped entries that are not skipped; every other entry gets 0 and its strings are
+ *   never read:  4 = more than POLYHIP_ALN_MAX_COLUMNS columns, decided from the offsets alone;  1 = an invalid column;
+ *   2 = ref_start plus the number of columns with b != '-' differs from ref_end, or ref_end > ref_len;  3 = no columns;
+ *   5 = some column has b != '-' and b != ref[its position].
+ *  Used: mapped, not skipped, err[i] == 0.  Only used entries add to the counts: the whole entry is judged before any of
+ *   its adds.
+ *  counts, channel-major, 16 planes of L uint32: counts[ch * L + (p - region_lo)] with ch = 8 * s + k.  k = 0..3: a is A/a,
+ *   C/c, G/g, T/t at a base column at p;  k = 4: any other a at a base column;  k = 5: a D column at p;  k = 6: an insertion
+ *   event anchored at p, one per maximal run of I columns (maximal among all columns of the entry), anchored at the position
+ *   of the last column with b != '-' before the run, ref_start - 1 if there is none;  k = 7: a deletion event anchored at
+ *   p, one per maximal run of D columns, anchored the same way, so the deleted bases are p + 1 onward.  An event anchored
+ *   at -1 is dropped and counted in info.edge_events (whatever the region); a position or anchor outside the region is
+ *   dropped silently.  counts is zeroed by the call.  All sums are integers, so the result does not depend on the order
+ *   of the adds.
+ *  consensus[p - region_lo]: with depth = the sum of k = 0..5 over both strands, 'N' if depth < max(min_depth, 1), else
+ *   "ACGTN*"[k] for the k in 0..5 with the highest two-strand count, ties to the lowest k.
+ *  sites, ascending p and within a position SNV to A, C, G, T, then INS, then DEL; only positions with depth >=
+ *   max(min_depth, 1) have any.  A count passes when count >= max(min_alt_count, 1) and count * 1000 >= min_alt_permille *
+ *   depth (in uint64).  SNV (kind 1): k in 0..3 that differs from the class of ref[p] (same table, "other" is class 4) and
+ *   whose two-strand count passes; alt is the upper-case base.  INS (kind 2): the count of channel 6 passes; alt = 0.  DEL
+ *   (kind 3): the count of channel 7 passes; alt = 0.  pos = p, depth as above, count the two-strand count, count_fwd its
+ *   strand-0 share, ref the raw ref[p], pad = 0.
+ * Capacity is polyhip_bwt_locate's: *nsites is always filled; if it exceeds site_capacity nothing is written to sites and the
+ * call fails with POLYHIP_ERR_INVALID naming the size needed, after counts, consensus and err have been filled; sites ==
+ * NULL with a capacity of 0 asks for the size only.  No device buffer for the sites is allocated before that check.
+ * Errors, in this order: a NULL params (POLYHIP_ERR_INVALID); region_lo > region_hi, region_hi > ref_len or
+ * min_alt_permille > 1000 (_INVALID, naming the field); n >= 2^32 (POLYHIP_ERR_UNSUPPORTED: the counts are uint32 and an
+ * entry adds at most one to a cell); min_mapq > 0 with mapq == NULL (_INVALID); a NULL array that is needed (_INVALID: ref
+ * and nsites always; with n > 0 flags, ref_start, ref_end, alnOff and err; alnA and alnB may be NULL when alnOff[n] ==
+ * alnOff[0]; counts and consensus may be NULL only when L == 0; sites as above); alnOff not ascending (_INVALID).  n == 0
+ * and L == 0 are successful calls; with L == 0 the only outputs are err and *nsites = 0.
+ * Host pointers only, no stream: the call copies the arrays in, runs on the calling thread's current device and copies the
+ * results out; nothing that depends on n or on the region is allocated before the checks above; the device list does not
+ * apply.  One text only; base qualities and the inserted bytes themselves are not looked at.
+ * polyhip_pileup_last_info: the calling thread's last call: entries = n; used = used entries; skipped_mapq = entries
+ * skipped by min_mapq; bad = entries with err != 0; columns = the columns of the used entries; edge_events = events dropped
+ * for anchor -1; sites = *nsites.
+ */
+#define POLYHIP_PILEUP_CHANNELS 16u
+typedef struct polyhip_pileup_params {
+    uint64_t region_lo, region_hi; /* text positions [lo, hi); L = hi - lo */
+    uint32_t min_mapq;             /* entries with mapq[i] < min_mapq are skipped; > 0 needs mapq != NULL */
+    uint32_t min_depth;            /* consensus and sites need depth >= max(min_depth, 1) */
+    uint32_t min_alt_count;        /* a site needs count >= max(min_alt_count, 1) ... */
+    uint32_t min_alt_permille;     /* ... and count * 1000 >= min_alt_permille * depth (uint64); 0..1000 */
+} polyhip_pileup_params;
+typedef struct polyhip_pileup_site {
+    uint32_t pos, depth, count, count_fwd;
+    uint8_t kind, ref, alt, pad;
+} polyhip_pileup_site;
+typedef struct polyhip_pileup_info {
+    uint64_t entries, used, skipped_mapq, bad, columns, edge_events, sites;
+} polyhip_pileup_info;
+int polyhip_pileup(const polyhip_pileup_params *params, uint64_t n, const uint32_t *flags,
+                   const uint8_t *mapq, const uint32_t *ref_start, const uint32_t *ref_end,
+                   const uint8_t *alnA, const uint8_t *alnB, const uint64_t *alnOff,
+                   const uint8_t *ref, uint64_t ref_len, uint32_t *counts, uint8_t *consensus,
+                   uint64_t *nsites, polyhip_pileup_site *sites, uint64_t site_capacity,
+                   uint32_t *err);
+int polyhip_pileup_last_info(polyhip_pileup_info *info);
+
 /* ---- R1: the path's one collective -- all-gather of per-rank sketches (RCCL over xGMI) ---- */
 /*
  * For hosts without torch.distributed (the Go/cgo drop-in); one process per GPU.  RCCL is

@@ -146,6 +146,8 @@ SIGNATURES = {
     "polyhip_aln_records": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp,
                                       _vp, _vp]),
     "polyhip_aln_records_last_info": (C.c_int, [_vp]),
+    "polyhip_pileup": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "polyhip_pileup_last_info": (C.c_int, [_vp]),
     "polyhip_comm_unique_id": (C.c_int, [_vp]),
     "polyhip_comm_init_rank": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "polyhip_comm_destroy": (C.c_int, [_vp]),
