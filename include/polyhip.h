@@ -1067,6 +1067,84 @@ int polyhip_map_pairs(const polyhip_bwt *h, const polyhip_scoring *sc,
                       uint8_t *alnA, uint8_t *alnB, uint64_t *alnOff, uint64_t aln_capacity);
 int polyhip_map_pairs_last_info(polyhip_map_pairs_info *info);
 
+/* ---- a reference of several contigs, and read mapping onto it (no counterpart in the reference) ---- */
+/*
+ * A polyhip_refs is a set of k contigs T_0 .. T_{k-1} of n_c >= 1 bytes each, given as a packed batch (seqs, off[0..k]).
+ * C is their concatenation without a separator (an ACGT set keeps the index's 2-bit nucleotide layout), start_c the
+ * exclusive scan of the lengths (start_k = |C|).  The set owns one FM-index over C, built by polyhip_bwt_create's path,
+ * and keeps start[0..k] on the index's device.
+ * refs_create errors, all decided before any device work: POLYHIP_ERR_INVALID for a NULL argument, ncontigs == 0, offsets
+ *   that do not ascend or an empty contig; POLYHIP_ERR_UNSUPPORTED for ncontigs > 2^24; POLYHIP_ERR_INVALID for a '$' in a
+ *   contig ("Provided sequence contains the nullChar $. BWT cannot be constructed") and for |C| >= 2^32 - 1, both as
+ *   polyhip_bwt_create.
+ * refs_count: k (negative status for a NULL handle).  refs_starts: out[0..k] = start (k + 1 entries).
+ * refs_index: the index of C.  It is BORROWED: the set owns it, it lives until polyhip_refs_destroy, and passing it to
+ *   polyhip_bwt_destroy is the caller's error.  polyhip_bwt_count / locate / extract work on it as on any index; its
+ *   positions are positions in C.  NULL for a NULL handle.
+ * refs_resolve: entry i is the span [pos[i], pos[i] + len[i]) of C (len == NULL: 1 each), e.g. what Locate returned with
+ *   the pattern's length.  One lane per entry finds by binary search over start[] the contig c with start_c <= pos <
+ *   start_{c+1}: rid[i] = c, local[i] = pos - start_c, err[i] = 0; err[i] = 2 when the span runs past the contig's end
+ *   (pos + len > start_{c+1}; rid and local are still those of pos); err[i] = 1 with rid = local = 0 when pos >= |C|.
+ *   n == 0 is an empty, successful call.  Host pointers; runs on the index's device and stream, as polyhip_bwt_count; the
+ *   device list does not apply.
+ *
+ * polyhip_map_reads_refs is polyhip_map_reads_affine, and polyhip_map_pairs_refs is polyhip_map_pairs, on a set instead of
+ * one text: the first argument is the set, and there is one more per-entry output, rid, before ref_start.  (With gap_open
+ * == gap_extend the single-read call is polyhip_map_reads with that linear gap.)  The definition is the single-text one
+ * with the changes below; everything not named here is unchanged, word for word.
+ *  2. seeds.  A seed's occurrences are the p with C[p, p + L) = q[o, o + L).  max_occ is judged on that count (occurrences
+ *     that straddle a boundary count towards it: it is a cost guard, and the count is known before anything is located);
+ *     a max_occ above |C| means no limit.  Of a seed that passes, an occurrence is a hit only if it lies wholly inside one
+ *     contig: start_c <= p and p + L <= start_c + n_c.  The hit is in contig c on the local diagonal d = p - start_c - o.
+ *     Straddling occurrences are dropped and counted (polyhip_map_refs_info.straddling).
+ *  3. clusters are formed per (strand, contig) on local diagonals: hits of different contigs never share a cluster.
+ *  4. candidates are ordered by (votes descending, s ascending, contig ascending, d0 ascending).
+ *  5. windows: lo = max(0, d0 - W), hi = min(n_c, dmax + m + W); the extension sees T_c[lo, hi) only.
+ *  6. rid = the chosen candidate's contig; ref_start and ref_end are positions in T_rid; an unmapped entry has rid = 0 with
+ *     its other zeros.
+ *  pairs, step 2: a proper combination also needs both candidates on the same contig; left and right are local.
+ *  pairs, step 4: a rescue window is clipped to [0, n_c) of the anchor's contig, and the rescued mate takes the anchor's rid.
+ * Parameter checks, their order and messages, POLYHIP_MAP_MAX_RESCUE_COLS, work_limit, chunking (multiples of 256 reads or
+ * 128 pairs, identical outputs for every chunking) and the string-capacity protocol are those of the single-text calls,
+ * with "null index handle" said of a NULL set.  A sort key holds (read of the chunk, strand, contig, local diagonal): a
+ * chunk is also limited to the reads whose keys fit 64 bits, and a set for which that is fewer than 256 reads (about
+ * log2(k) + log2(longest contig + max_len + band) > 54) is POLYHIP_ERR_UNSUPPORTED.
+ * The calls fill the calling thread's polyhip_map_affine_last_info / polyhip_map_pairs_last_info as their single-text
+ * siblings do (hits = the hits kept), and polyhip_map_refs_last_info: contigs = k, straddling = occurrences dropped in
+ * step 2, over both strands and all chunks.
+ */
+typedef struct polyhip_refs polyhip_refs;
+typedef struct polyhip_map_refs_info {
+    uint64_t contigs, straddling;
+} polyhip_map_refs_info;
+int polyhip_refs_create(const uint8_t *seqs, const uint64_t *off, uint64_t ncontigs,
+                        polyhip_refs **out);
+int polyhip_refs_destroy(polyhip_refs *h);
+int64_t polyhip_refs_count(const polyhip_refs *h);
+int polyhip_refs_starts(const polyhip_refs *h, uint64_t *out);
+const polyhip_bwt *polyhip_refs_index(const polyhip_refs *h);
+int polyhip_refs_resolve(const polyhip_refs *h, const uint32_t *pos, const uint32_t *len,
+                         uint64_t n, uint32_t *rid, uint32_t *local, uint32_t *err);
+int polyhip_map_reads_refs(const polyhip_refs *h, const polyhip_scoring *sc,
+                           const polyhip_map_params *params, int64_t gap_open,
+                           int64_t gap_extend, const uint8_t *reads, const uint64_t *off,
+                           uint64_t nreads, uint32_t max_len, uint64_t work_limit,
+                           int64_t *score, int64_t *second, uint32_t *flags, uint32_t *votes,
+                           uint32_t *rid, uint32_t *ref_start, uint32_t *ref_end,
+                           uint32_t *read_start, uint32_t *read_end, uint32_t *err,
+                           uint8_t *alnA, uint8_t *alnB, uint64_t *alnOff, uint64_t aln_capacity);
+int polyhip_map_pairs_refs(const polyhip_refs *h, const polyhip_scoring *sc,
+                           const polyhip_map_params *params,
+                           const polyhip_map_pair_params *pair_params, int64_t gap_open,
+                           int64_t gap_extend, const uint8_t *reads1, const uint64_t *off1,
+                           const uint8_t *reads2, const uint64_t *off2, uint64_t npairs,
+                           uint32_t max_len, uint64_t work_limit, int64_t *score, int64_t *second,
+                           uint32_t *flags, uint32_t *votes, uint32_t *rid, uint32_t *ref_start,
+                           uint32_t *ref_end, uint32_t *read_start, uint32_t *read_end,
+                           uint32_t *err, int64_t *tlen, uint8_t *alnA, uint8_t *alnB,
+                           uint64_t *alnOff, uint64_t aln_capacity);
+int polyhip_map_refs_last_info(polyhip_map_refs_info *info);
+
 /* ---- the mapper's output as alignment records: CIGAR, NM, MD, MAPQ, SAM FLAG (no counterpart in the reference) ---- */
 /*
  * polyhip_aln_records turns what polyhip_map_reads, polyhip_map_reads_affine or polyhip_map_pairs returned for n entries

@@ -143,6 +143,17 @@ SIGNATURES = {
     "polyhip_map_pairs": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64]),
     "polyhip_map_pairs_last_info": (C.c_int, [_vp]),
+    "polyhip_refs_create": (C.c_int, [_vp, _vp, _u64, C.POINTER(C.c_void_p)]),
+    "polyhip_refs_destroy": (C.c_int, [_vp]),
+    "polyhip_refs_count": (C.c_int64, [_vp]),
+    "polyhip_refs_starts": (C.c_int, [_vp, _vp]),
+    "polyhip_refs_index": (C.c_void_p, [_vp]),
+    "polyhip_refs_resolve": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "polyhip_map_reads_refs": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64]),
+    "polyhip_map_pairs_refs": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64]),
+    "polyhip_map_refs_last_info": (C.c_int, [_vp]),
     "polyhip_aln_records": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp,
                                       _vp, _vp]),
     "polyhip_aln_records_last_info": (C.c_int, [_vp]),

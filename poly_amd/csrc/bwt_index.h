@@ -363,7 +363,19 @@ struct BwtHandle {
     }
 };
 
+// A reference set (refs.hip; the mapper's refs calls read it): k contigs concatenated into the text of `index`, which the
+// set owns.  start[c] = where contig c begins in that text, start[k] = its length.
+struct RefsHandle {
+    polyhip_bwt *index = nullptr;
+    uint32_t k = 0;
+    uint32_t nmax = 0;           // the longest contig
+    uint32_t *d_start = nullptr; // k + 1, on the index's device
+    uint64_t *starts = nullptr;  // the same on the host, as polyhip_refs_starts returns them
+};
+
 namespace {
+
+const RefsHandle *as_refs(const polyhip_refs *h) { return reinterpret_cast<const RefsHandle *>(h); }
 
 // the calling thread runs a bwt call on the handle's device and gets its own device back afterwards
 struct DeviceScope {

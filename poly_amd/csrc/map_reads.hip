@@ -33,6 +33,16 @@
 //   k3a::score_pass      on that batch
 //   pair_resolve_kernel  one wave per pair: the rescue's success test and tie rule, the per-mate outputs, tlen, the winners' sources
 //   pair_winners_kernel / pair_wgather_kernel   the winners from either batch; the traceback, finish and strings steps as above
+// polyhip_map_reads_refs / polyhip_map_pairs_refs (a reference of several contigs, refs.hip: one index over their concatenation
+// C and start[0..k]) are the affine and the paired call with the REFS instantiations of four kernels and two kernels of their own:
+//   map_count_refs_kernel / map_expand_refs_kernel   hits in two passes: an occurrence that straddles a boundary is no hit and
+//                       the runs per seed must stay dense, so the first pass counts what each seed keeps (binary search of
+//                       every located p over start[]) and the second writes keys with the contig above the local diagonal
+//   map_cluster_kernel<true>   the diagonal field is wide enough for k0 + W, so clusters split at contigs by themselves;
+//                       windows are clipped to the contig and kept as positions in C with the contig beside them (crid)
+//   everything between (gathers, score pass, winners, traceback, finish) works on positions in C and is shared unchanged
+//   map_reduce_kernel<true, true> / pair_resolve_kernel<true>   rid out, ref_end made local (ref_start follows from it)
+//   pair_reduce_kernel<true>   proper only within one contig; the rescue window clipped to the anchor's contig
 #include "bwt_index.h"
 #include "sw_affine.h"
 #include "sw_scoring.h"
@@ -51,9 +61,24 @@ struct MapShape {
     uint32_t max_len; // also the diagonal bias: d + max_len >= 0
     uint32_t dbits;   // bits of a biased diagonal
     uint64_t n;       // text length
+    // a reference set (polyhip_map_*_refs; k = 0: one text): contigs, bits of a contig number, bits of a key below the
+    // (read, strand) field, and the most reads whose keys fit 64 bits (0: no such limit)
+    uint32_t k, cbits, kbits;
+    uint64_t rcap;
 };
 
-enum { CNT_SEEDS = 0, CNT_OVER = 1, CNT_CLUSTERS = 2, CNT_MAPPED = 3, CNT_TBCELLS = 4, CNT_PROPER = 5, CNT_RESCUED = 6, CNT_N = 7 };
+// what the kernels of the refs calls see of the set besides the shape: start[0..k], the kept candidates' contigs, and
+// where the per-entry contig goes.  All null in the single-text calls, whose instantiations never read them.
+struct RefView {
+    const uint32_t *start;
+    uint32_t *crid;
+    uint32_t *o_rid;
+};
+
+enum {
+    CNT_SEEDS = 0, CNT_OVER = 1, CNT_CLUSTERS = 2, CNT_MAPPED = 3, CNT_TBCELLS = 4, CNT_PROPER = 5, CNT_RESCUED = 6, CNT_STRADDLE = 7,
+    CNT_N = 8
+};
 
 // transform.complementTable (transform.go:78-109): IUPAC letters in both cases, every other byte -> 0x00
 __device__ __forceinline__ uint32_t dna_complement(uint32_t b)
@@ -156,19 +181,96 @@ __global__ __launch_bounds__(BT) void map_expand_kernel(const uint32_t *__restri
     }
 }
 
+// ---- hits on a reference set -----------------------------------------------------------------------------------------------
+// the contig of position p < start[k]: start[c] <= p < start[c + 1]
+__device__ __forceinline__ uint32_t find_contig(const uint32_t *__restrict__ start, uint32_t k, uint32_t p)
+{
+    uint32_t lo = 0, hi = k;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (start[mid] <= p)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+// Occurrences that straddle a boundary are no hits, and the sort, first[] and the cluster kernel want dense per-seed runs:
+// two passes.  The counting pass, one lane per seed slot: width[slot] keeps the seed's rows, first[slot] (the rows on
+// entry) becomes the occurrences that lie inside one contig; the dropped ones are counted.
+__global__ __launch_bounds__(BT) void map_count_refs_kernel(const uint32_t *__restrict__ sa, const uint32_t *__restrict__ start,
+                                                            uint64_t nslots, MapShape g, const uint32_t *__restrict__ cstart,
+                                                            uint32_t *__restrict__ first, uint32_t *__restrict__ width,
+                                                            unsigned long long *__restrict__ cnt)
+{
+    uint32_t dropped = 0;
+    const uint64_t span = (uint64_t)gridDim.x * BT;
+    for (uint64_t base = blockIdx.x * (uint64_t)BT; base < nslots; base += span) {
+        const uint64_t slot = base + threadIdx.x;
+        if (slot < nslots) {
+            const uint32_t w = first[slot], s = start[slot];
+            uint32_t kept = 0;
+            for (uint32_t t = 0; t < w; ++t) {
+                const uint32_t p = sa[s + t];
+                const uint32_t c = find_contig(cstart, g.k, p);
+                kept += p + g.L <= cstart[c + 1];
+            }
+            width[slot] = w;
+            first[slot] = kept;
+            dropped += w - kept;
+        }
+    }
+    count_add(cnt + CNT_STRADDLE, dropped);
+}
+
+// The write pass: a slot's kept hits as keys ((read * 2 + strand) << cbits | c) << dbits | (p - start_c - o + max_len)
+__global__ __launch_bounds__(BT) void map_expand_refs_kernel(const uint32_t *__restrict__ sa, const uint32_t *__restrict__ start,
+                                                             const uint32_t *__restrict__ width, const uint32_t *__restrict__ first,
+                                                             uint64_t nslots, MapShape g, const uint32_t *__restrict__ cstart,
+                                                             uint64_t *__restrict__ keys, uint32_t *__restrict__ vals)
+{
+    for (uint64_t slot = blockIdx.x * (uint64_t)BT + threadIdx.x; slot < nslots; slot += (uint64_t)gridDim.x * BT) {
+        uint32_t f = first[slot];
+        const uint32_t end = first[slot + 1], w = width[slot];
+        if (f == end)
+            continue;
+        const uint32_t k = (uint32_t)(slot % g.ns);
+        const uint64_t rs = slot / g.ns;
+        const uint64_t r = rs / g.strands, strand = rs % g.strands;
+        const uint64_t hi = (r * 2 + strand) << g.cbits;
+        const uint64_t bias = (uint64_t)g.max_len - (uint64_t)k * g.S; // >= 0: a seed starts inside the read
+        const uint32_t s = start[slot];
+        for (uint32_t t = 0; t < w && f < end; ++t) {
+            const uint32_t p = sa[s + t];
+            const uint32_t c = find_contig(cstart, g.k, p), b = cstart[c];
+            if (p + g.L > cstart[c + 1])
+                continue;
+            keys[f] = ((hi | c) << g.dbits) | ((uint64_t)(p - b) + bias);
+            vals[f] = p;
+            ++f;
+        }
+    }
+}
+
 // One wave per read over its sorted hits.  Lane i holds the candidate of rank i: a new cluster goes behind every kept one
 // with at least its votes (clusters arrive in (strand, d0) order, which is the order among equal votes).
+// REFS: the keys hold the contig above the local diagonal, in a field wide enough that k0 + W never carries into it, so
+// clusters split at contigs without a test and arrive in (strand, contig, d0) order; a window is clipped to its contig and
+// kept in C's coordinates (clo = start_c + lo), with the contig beside it.
+template <bool REFS>
 __global__ __launch_bounds__(BT) void map_cluster_kernel(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ first,
                                                          const uint64_t *__restrict__ off, uint64_t nreads, MapShape g,
                                                          uint32_t *__restrict__ ncand, uint32_t *__restrict__ cvotes,
                                                          uint32_t *__restrict__ cstrand, uint32_t *__restrict__ clo,
-                                                         uint32_t *__restrict__ chi, unsigned long long *__restrict__ cnt)
+                                                         uint32_t *__restrict__ chi, RefView rv, unsigned long long *__restrict__ cnt)
 {
     const int lane = threadIdx.x & 63;
     const uint64_t dmask = (1ull << g.dbits) - 1;
+    const uint32_t cmask = REFS ? (1u << g.cbits) - 1 : 0u;
     for (uint64_t r = (blockIdx.x * (uint64_t)BT + threadIdx.x) / 64; r < nreads; r += (uint64_t)gridDim.x * (BT / 64)) {
         const int64_t m = (int64_t)(off[r + 1] - off[r]);
-        uint32_t votes = 0, cs = 0, ncl = 0;
+        uint32_t votes = 0, cs = 0, ncl = 0, cc = 0;
         uint64_t d0k = 0, dmaxk = 0; // biased diagonals
         for (uint32_t strand = 0; strand < g.strands; ++strand) {
             const uint64_t s0 = (r * g.strands + strand) * g.ns;
@@ -189,10 +291,15 @@ __global__ __launch_bounds__(BT) void map_cluster_kernel(const uint64_t *__restr
                 const int at = __popcll(__ballot(votes >= n)); // free lanes hold 0 votes, n >= 1
                 const uint32_t uv = __shfl_up(votes, 1, 64), us = __shfl_up(cs, 1, 64);
                 const uint64_t ud0 = __shfl_up(d0k, 1, 64), ud1 = __shfl_up(dmaxk, 1, 64);
+                const uint32_t uc = REFS ? __shfl_up(cc, 1, 64) : 0u;
                 if (lane > at) {
                     votes = uv, cs = us, d0k = ud0, dmaxk = ud1;
+                    if (REFS)
+                        cc = uc;
                 } else if (lane == at) {
                     votes = n, cs = strand, d0k = k0 & dmask, dmaxk = k1 & dmask;
+                    if (REFS)
+                        cc = (uint32_t)(k0 >> g.dbits) & cmask;
                 }
                 ++ncl;
                 pos += n;
@@ -202,12 +309,16 @@ __global__ __launch_bounds__(BT) void map_cluster_kernel(const uint64_t *__restr
         if ((uint32_t)lane < nc) {
             const int64_t d0 = (int64_t)d0k - g.max_len, d1 = (int64_t)dmaxk - g.max_len;
             const int64_t lo_ = d0 - (int64_t)g.W, hi_ = d1 + m + (int64_t)g.W;
-            const int64_t lo = lo_ > 0 ? lo_ : 0, hi = hi_ < (int64_t)g.n ? hi_ : (int64_t)g.n;
+            const int64_t base = REFS ? (int64_t)rv.start[cc] : 0;
+            const int64_t len = REFS ? (int64_t)rv.start[cc + 1] - base : (int64_t)g.n;
+            const int64_t lo = lo_ > 0 ? lo_ : 0, hi = hi_ < len ? hi_ : len;
             const uint64_t o = r * g.C + lane;
             cvotes[o] = votes;
             cstrand[o] = cs;
-            clo[o] = (uint32_t)lo;
-            chi[o] = (uint32_t)hi;
+            clo[o] = (uint32_t)(base + lo);
+            chi[o] = (uint32_t)(base + hi);
+            if (REFS)
+                rv.crid[o] = cc;
         }
         if (lane == 0) {
             ncand[r] = nc;
@@ -277,7 +388,8 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
 // One wave per read, lane i = its candidate of rank i.  slen / best: the chosen pair's string length (0 unmapped) and index.
 // AFFINE: no strings exist yet: ref_start / read_start and slen are left to map_finish_kernel (0 here, which is what an
 // unmapped read keeps), and wmap[r] = 1 for a mapped read.
-template <bool AFFINE>
+// REFS: clo is a position in C; the entry gets its candidate's contig and a ref_end inside it.
+template <bool AFFINE, bool REFS = false>
 __global__ __launch_bounds__(BT) void map_reduce_kernel(const uint32_t *__restrict__ pfirst, const uint64_t *__restrict__ off, uint64_t nreads,
                                                         MapShape g, int64_t min_score, const int64_t *__restrict__ pscore,
                                                         const uint32_t *__restrict__ pendA, const uint32_t *__restrict__ pendB,
@@ -289,7 +401,7 @@ __global__ __launch_bounds__(BT) void map_reduce_kernel(const uint32_t *__restri
                                                         uint32_t *__restrict__ o_votes, uint32_t *__restrict__ o_rs, uint32_t *__restrict__ o_re,
                                                         uint32_t *__restrict__ o_qs, uint32_t *__restrict__ o_qe, uint32_t *__restrict__ o_err,
                                                         uint64_t *__restrict__ slen, uint32_t *__restrict__ best, uint32_t *__restrict__ wmap,
-                                                        unsigned long long *__restrict__ cnt)
+                                                        RefView rv, unsigned long long *__restrict__ cnt)
 {
     const int lane = threadIdx.x & 63;
     uint32_t nmapped = 0;
@@ -333,7 +445,12 @@ __global__ __launch_bounds__(BT) void map_reduce_kernel(const uint32_t *__restri
         }
         if (lane == 0) {
             const uint64_t c = r * g.C + (uint32_t)bi;
-            const uint32_t eA = mapped ? pendA[bp] : 0u, eB = mapped ? clo[c] + pendB[bp] : 0u;
+            uint32_t eA = mapped ? pendA[bp] : 0u, eB = mapped ? clo[c] + pendB[bp] : 0u;
+            if (REFS) {
+                const uint32_t id = mapped ? rv.crid[c] : 0u;
+                eB -= mapped ? rv.start[id] : 0u;
+                rv.o_rid[r] = id;
+            }
             o_score[r] = mapped ? bs : 0;
             o_second[r] = mapped ? second : 0;
             o_flags[r] = mapped ? 1u | (cstrand[c] << 1) : 0u;
@@ -521,13 +638,15 @@ struct MateCands {
     int64_t m, score, left; // left = lo + endB - endA: where q[0] lands along the end cell's diagonal
     int bi;                 // the single-read winner's rank ...
     bool mapped, usable;    // ... which exists; this lane's candidate is usable
+    uint32_t rid;           // REFS: the candidate's contig (left is a position in C)
 };
 
+template <bool REFS>
 __device__ __forceinline__ MateCands load_mate(uint64_t r, int lane, const uint32_t *__restrict__ pfirst, const uint64_t *__restrict__ off,
                                                const MapShape &g, int64_t min_score, const int64_t *__restrict__ pscore,
                                                const uint32_t *__restrict__ pendA, const uint32_t *__restrict__ pendB,
                                                const uint32_t *__restrict__ perr, const uint32_t *__restrict__ cstrand,
-                                               const uint32_t *__restrict__ clo)
+                                               const uint32_t *__restrict__ clo, const RefView &rv)
 {
     MateCands c;
     const uint32_t p0 = pfirst[r];
@@ -542,6 +661,7 @@ __device__ __forceinline__ MateCands load_mate(uint64_t r, int lane, const uint3
         c.err = __shfl(er, __ffsll((unsigned long long)bad) - 1, 64);
     c.strand = have ? cstrand[r * g.C + lane] : 0u;
     c.left = have ? (int64_t)clo[r * g.C + lane] + (int64_t)pendB[p0 + lane] - (int64_t)pendA[p0 + lane] : 0;
+    c.rid = REFS && have ? rv.crid[r * g.C + lane] : 0u;
     int64_t bs = c.score;
     int bi = lane;
 #pragma unroll
@@ -562,6 +682,9 @@ __device__ __forceinline__ MateCands load_mate(uint64_t r, int lane, const uint3
 // smallest k1, then the smallest k2, which is the smallest k1 * nc2 + k2.  Out: err of both mates; choice = the rank
 // pairing chose, or without a proper combination the single-read winner's (-1: none); proper / insert of the pair; and
 // then the rescue requests, kept under the mate to rescue: rvalid = 1, the query's strand, the clipped window.
+// REFS: a combination is proper only within one contig (projections are positions in C, so their differences are the local
+// ones), and a rescue window is clipped to the anchor's contig.
+template <bool REFS>
 __global__ __launch_bounds__(BT) void pair_reduce_kernel(const uint32_t *__restrict__ pfirst, const uint64_t *__restrict__ off, uint64_t npairs,
                                                          MapShape g, PairShape q, int64_t min_score, const int64_t *__restrict__ pscore,
                                                          const uint32_t *__restrict__ pendA, const uint32_t *__restrict__ pendB,
@@ -569,12 +692,13 @@ __global__ __launch_bounds__(BT) void pair_reduce_kernel(const uint32_t *__restr
                                                          const uint32_t *__restrict__ clo, uint32_t *__restrict__ o_err,
                                                          int32_t *__restrict__ choice, uint32_t *__restrict__ proper,
                                                          int64_t *__restrict__ ptlen, uint32_t *__restrict__ rvalid,
-                                                         uint32_t *__restrict__ rstrand, uint32_t *__restrict__ rlo, uint32_t *__restrict__ rhi)
+                                                         uint32_t *__restrict__ rstrand, uint32_t *__restrict__ rlo, uint32_t *__restrict__ rhi,
+                                                         RefView rv)
 {
     const int lane = threadIdx.x & 63;
     for (uint64_t i = (blockIdx.x * (uint64_t)BT + threadIdx.x) / 64; i < npairs; i += (uint64_t)gridDim.x * (BT / 64)) {
-        const MateCands a = load_mate(2 * i, lane, pfirst, off, g, min_score, pscore, pendA, pendB, perr, cstrand, clo);
-        const MateCands b = load_mate(2 * i + 1, lane, pfirst, off, g, min_score, pscore, pendA, pendB, perr, cstrand, clo);
+        const MateCands a = load_mate<REFS>(2 * i, lane, pfirst, off, g, min_score, pscore, pendA, pendB, perr, cstrand, clo, rv);
+        const MateCands b = load_mate<REFS>(2 * i + 1, lane, pfirst, off, g, min_score, pscore, pendA, pendB, perr, cstrand, clo, rv);
         int64_t bsum = INT64_MIN, bins = 0;
         uint32_t bt = 0xFFFFFFFFu;
         const uint32_t ncomb = a.err == 0 && b.err == 0 ? a.nc * b.nc : 0u;
@@ -586,7 +710,8 @@ __global__ __launch_bounds__(BT) void pair_reduce_kernel(const uint32_t *__restr
             const int64_t l1 = __shfl(a.left, k1, 64), l2 = __shfl(b.left, k2, 64);
             const uint32_t d1 = __shfl(a.strand, k1, 64), d2 = __shfl(b.strand, k2, 64);
             const int u1 = __shfl((int)a.usable, k1, 64), u2 = __shfl((int)b.usable, k2, 64);
-            const int64_t ins = in && u1 && u2 ? proper_insert(d1, l1, a.m, d2, l2, b.m, q) : -1;
+            const bool same = !REFS || __shfl(a.rid, k1, 64) == __shfl(b.rid, k2, 64);
+            const int64_t ins = in && u1 && u2 && same ? proper_insert(d1, l1, a.m, d2, l2, b.m, q) : -1;
             if (ins >= 0 && s1 + s2 > bsum) // t ascends within a lane: the first of equal sums stays
                 bsum = s1 + s2, bins = ins, bt = t;
         }
@@ -601,6 +726,7 @@ __global__ __launch_bounds__(BT) void pair_reduce_kernel(const uint32_t *__restr
         // the anchors of a rescue: each mate's single-read winner, fetched from the lane that holds it
         const int64_t la = __shfl(a.left, a.bi, 64), lb = __shfl(b.left, b.bi, 64);
         const uint32_t sa = __shfl(a.strand, a.bi, 64), sb = __shfl(b.strand, b.bi, 64);
+        const uint32_t ca = __shfl(a.rid, a.bi, 64), cb = __shfl(b.rid, b.bi, 64);
         if (lane == 0) {
             o_err[2 * i] = a.err;
             o_err[2 * i + 1] = b.err;
@@ -616,8 +742,10 @@ __global__ __launch_bounds__(BT) void pair_reduce_kernel(const uint32_t *__restr
             const int64_t W = g.W;
             int64_t wlo = s == 0 ? left + q.min_insert - my - W : left + mx - q.max_insert - W;
             int64_t whi = s == 0 ? left + q.max_insert + W : left + mx - q.min_insert + my + W;
-            wlo = wlo > 0 ? wlo : 0;
-            whi = whi < (int64_t)g.n ? whi : (int64_t)g.n;
+            const uint32_t cx = lane == 0 ? ca : cb; // (0 without an anchor: any contig will do, nothing is asked)
+            const int64_t blo = REFS ? (int64_t)rv.start[cx] : 0, bhi = REFS ? (int64_t)rv.start[cx + 1] : (int64_t)g.n;
+            wlo = wlo > blo ? wlo : blo;
+            whi = whi < bhi ? whi : bhi;
             const bool ask = !found && q.rescue && anchored && ey == 0 && my >= 1 && wlo < whi;
             const uint64_t y = 2 * i + 1 - lane;
             rvalid[y] = ask;
@@ -677,6 +805,8 @@ constexpr uint32_t SRC_RESCUE = 0x80000000u; // a winner's source: a pair of the
 // One wave per pair, after the rescue score pass (rfirst is all zero when there was none).  Applies the success test and
 // the tie rule of the rescue, then writes every per-mate output but ref_start / read_start (map_finish_kernel's, from the
 // strings), tlen, wmap = 1 for a mapped mate and src = where its alignment is.
+// REFS: every mate gets its contig (a rescued one its anchor's) and a ref_end inside it.
+template <bool REFS>
 __global__ __launch_bounds__(BT) void pair_resolve_kernel(const uint32_t *__restrict__ pfirst, const uint64_t *__restrict__ off, uint64_t npairs,
                                                           MapShape g, PairShape q, int64_t min_score, const int64_t *__restrict__ pscore,
                                                           const uint32_t *__restrict__ pendA, const uint32_t *__restrict__ pendB,
@@ -691,7 +821,7 @@ __global__ __launch_bounds__(BT) void pair_resolve_kernel(const uint32_t *__rest
                                                           uint32_t *__restrict__ o_votes, uint32_t *__restrict__ o_rs, uint32_t *__restrict__ o_re,
                                                           uint32_t *__restrict__ o_qs, uint32_t *__restrict__ o_qe, int64_t *__restrict__ o_tlen,
                                                           uint64_t *__restrict__ slen, uint32_t *__restrict__ src, uint32_t *__restrict__ wmap,
-                                                          unsigned long long *__restrict__ cnt)
+                                                          RefView rv, unsigned long long *__restrict__ cnt)
 {
     const int lane = threadIdx.x & 63;
     uint32_t nmapped = 0, nproper = 0, nrescued = 0;
@@ -737,7 +867,14 @@ __global__ __launch_bounds__(BT) void pair_resolve_kernel(const uint32_t *__rest
                     o_score[r] = rscore[j];
                     o_flags[r] = 1u | (rstrand[r] << 1) | pair_bits | 8u;
                     o_votes[r] = 0;
-                    o_re[r] = rlo[r] + rendB[j];
+                    uint32_t base = 0;
+                    if (REFS) {
+                        const uint64_t ax = 2 * i + 1 - x; // the anchor: the other mate's chosen candidate
+                        const uint32_t id = rv.crid[ax * g.C + (uint32_t)choice[ax]];
+                        base = rv.start[id];
+                        rv.o_rid[r] = id;
+                    }
+                    o_re[r] = rlo[r] + rendB[j] - base;
                     o_qe[r] = rendA[j];
                     src[r] = SRC_RESCUE | j;
                 } else if (mapped) {
@@ -746,10 +883,18 @@ __global__ __launch_bounds__(BT) void pair_resolve_kernel(const uint32_t *__rest
                     o_score[r] = pscore[bp];
                     o_flags[r] = 1u | (cstrand[c] << 1) | pair_bits;
                     o_votes[r] = cvotes[c];
-                    o_re[r] = clo[c] + pendB[bp];
+                    uint32_t base = 0;
+                    if (REFS) {
+                        const uint32_t id = rv.crid[c];
+                        base = rv.start[id];
+                        rv.o_rid[r] = id;
+                    }
+                    o_re[r] = clo[c] + pendB[bp] - base;
                     o_qe[r] = pendA[bp];
                     src[r] = bp;
                 } else {
+                    if (REFS)
+                        rv.o_rid[r] = 0;
                     o_score[r] = 0;
                     o_flags[r] = 0;
                     o_votes[r] = 0;
@@ -859,6 +1004,8 @@ struct MapWork {
     int64_t *ptlen, *rscore;
     uint64_t *roffA, *roffB;
     uint8_t *rA, *rB;
+    // the refs calls': every seed's rows (first[] holds the kept hits), every kept candidate's contig
+    uint32_t *width, *crid;
 };
 
 // polyhip_map_reads_affine's gaps and what k3a::choose() fixed for the call
@@ -879,7 +1026,7 @@ size_t map_carve(const polyhip_scoring *sc, const MapShape &g, const MapAffine *
     const uint64_t slots = nr * g.strands * g.ns;
     w.hcap = slots * g.max_occ;
     w.pcap = nr * g.C;
-    if (w.hcap >= (1ull << 31) || w.pcap >= (1ull << 31))
+    if (w.hcap >= (1ull << 31) || w.pcap >= (1ull << 31) || (g.rcap && nr > g.rcap))
         return 0;
     w.lenB = g.max_len + 3 * g.W;
     w.lenW = af ? std::max(w.lenB, af->wide) : w.lenB;
@@ -966,6 +1113,10 @@ size_t map_carve(const polyhip_scoring *sc, const MapShape &g, const MapAffine *
     }
     w.soff = c.take<uint64_t>(nr + 1);
     w.best = c.take<uint32_t>(nr);
+    if (g.k) {
+        w.width = c.take<uint32_t>(slots);
+        w.crid = c.take<uint32_t>(w.pcap);
+    }
     if (out)
         *out = w;
     return c.used;
@@ -1017,12 +1168,35 @@ MapShape make_shape(const polyhip_map_params *p, uint64_t n, uint32_t max_len)
     g.ns = max_len >= g.L ? (max_len - g.L) / g.S + 1 : 0;
     g.max_len = max_len;
     g.dbits = (uint32_t)bits_for(n + max_len);
+    g.kbits = g.dbits;
     g.n = n;
     return g;
 }
 
+// the shape of a call on a reference set: a biased local diagonal is at most nmax + max_len, and the field also holds
+// + band, so that the cluster kernel's k0 + W stays inside it
+MapShape make_shape(const polyhip_map_params *p, const RefsHandle *rf, uint32_t max_len)
+{
+    MapShape g = make_shape(p, as_h(rf->index)->n, max_len);
+    g.k = rf->k;
+    g.cbits = (uint32_t)bits_for(rf->k - 1);
+    g.dbits = (uint32_t)bits_for((uint64_t)rf->nmax + max_len + p->band);
+    g.kbits = g.cbits + g.dbits;
+    const uint32_t left = 64 - g.kbits; // bits for read * 2 + strand
+    g.rcap = left >= 33 ? 0 : left >= 1 ? 1ull << (left - 1) : 1;
+    return g;
+}
+
+// a chunk of MAP_CHUNK reads can be sorted: its keys fit 64 bits
+bool keys_fit(const polyhip_map_params *p, const RefsHandle *rf, uint32_t max_len)
+{
+    const uint64_t rcap = make_shape(p, rf, max_len).rcap;
+    return rcap == 0 || rcap >= MAP_CHUNK;
+}
+
 thread_local polyhip_map_info t_info{};
 thread_local polyhip_map_affine_info t_ainfo{};
+thread_local polyhip_map_refs_info t_rinfo{};
 
 int validate(const char *who, const polyhip_bwt *hp, const polyhip_scoring *sc, const polyhip_map_params *p, uint32_t max_len)
 {
@@ -1046,7 +1220,14 @@ struct MapOut {
     uint8_t *alnA, *alnB;
     uint64_t *alnOff;
     uint64_t capacity;
+    uint32_t *rid = nullptr; // the refs calls'
 };
+
+// a refs call's view for its kernels (all null for one text); o_rid = the chunk's part of the per-entry contigs
+RefView ref_view(const RefsHandle *rf, const MapWork &w, uint32_t *o_rid)
+{
+    return rf ? RefView{rf->d_start, w.crid, o_rid} : RefView{nullptr, nullptr, nullptr};
+}
 
 // what a call leaves for polyhip_map_last_info, or (af) for polyhip_map_affine_last_info
 void keep_info(const polyhip_map_info &i, const MapAffine *af, uint64_t traced, uint64_t tb_cells, uint32_t tb_chunks)
@@ -1061,9 +1242,11 @@ void keep_info(const polyhip_map_info &i, const MapAffine *af, uint64_t traced, 
 
 // Steps 1-5 for a chunk of nr reads: seeds -> hits -> clusters -> the kept candidates as a pair batch -> its scores (the
 // affine score pass, or the linear aligner with every pair's strings).  *pairs_out = the candidates.
-int map_candidates(const BwtHandle *h, const polyhip_scoring *sc, const MapShape &g, const MapAffine *af, const MapWork &w,
-                   const uint8_t *d_reads, const uint64_t *off, uint64_t nr, hipStream_t st, polyhip_map_info &info, uint32_t *pairs_out)
+int map_candidates(const BwtHandle *h, const RefsHandle *rf, const polyhip_scoring *sc, const MapShape &g, const MapAffine *af,
+                   const MapWork &w, const uint8_t *d_reads, const uint64_t *off, uint64_t nr, hipStream_t st, polyhip_map_info &info,
+                   uint32_t *pairs_out)
 {
+    const RefView rv = ref_view(rf, w, nullptr);
     const uint64_t slots = nr * g.strands * g.ns;
     // seeds -> hits
     uint32_t nhits = 0;
@@ -1075,6 +1258,11 @@ int map_candidates(const BwtHandle *h, const polyhip_scoring *sc, const MapShape
             hipLaunchKernelGGL(map_seed_kernel<1>, dim3(grid_for(slots)), dim3(BT), 0, st, h->x, d_reads, off, slots, g, w.start, w.first,
                                w.cnt);
         PH_HIP(hipGetLastError());
+        if (rf) { // the seeds' rows -> the hits kept
+            hipLaunchKernelGGL(map_count_refs_kernel, dim3(grid_for(slots)), dim3(BT), 0, st, h->d_sa, w.start, slots, g, rf->d_start,
+                               w.first, w.width, w.cnt);
+            PH_HIP(hipGetLastError());
+        }
         PH_HIP(scan_excl<uint32_t>(w.first, w.first, slots, w.scratch, st));
         PH_HIP(hipMemcpyAsync(&nhits, w.first + slots, sizeof nhits, hipMemcpyDeviceToHost, st));
         PH_HIP(hipStreamSynchronize(st));
@@ -1084,12 +1272,20 @@ int map_candidates(const BwtHandle *h, const polyhip_scoring *sc, const MapShape
     uint64_t *ka = w.ka, *kb = w.kb;
     uint32_t *va = w.va, *vb = w.vb;
     if (nhits) {
-        hipLaunchKernelGGL(map_expand_kernel, dim3(grid_for(slots)), dim3(BT), 0, st, h->d_sa, w.start, w.first, slots, g, ka, va);
+        if (rf)
+            hipLaunchKernelGGL(map_expand_refs_kernel, dim3(grid_for(slots)), dim3(BT), 0, st, h->d_sa, w.start, w.width, w.first, slots, g,
+                               rf->d_start, ka, va);
+        else
+            hipLaunchKernelGGL(map_expand_kernel, dim3(grid_for(slots)), dim3(BT), 0, st, h->d_sa, w.start, w.first, slots, g, ka, va);
         PH_HIP(hipGetLastError());
-        if (int rc = radix_sort(ka, va, kb, vb, nhits, (int)g.dbits + bits_for(2 * nr - 1), w.hist, w.scratch, st))
+        if (int rc = radix_sort(ka, va, kb, vb, nhits, (int)g.kbits + bits_for(2 * nr - 1), w.hist, w.scratch, st))
             return rc;
-        hipLaunchKernelGGL(map_cluster_kernel, dim3(grid_for(nr * 64)), dim3(BT), 0, st, ka, w.first, off, nr, g, w.pfirst, w.cvotes,
-                           w.cstrand, w.clo, w.chi, w.cnt);
+        if (rf)
+            hipLaunchKernelGGL(map_cluster_kernel<true>, dim3(grid_for(nr * 64)), dim3(BT), 0, st, ka, w.first, off, nr, g, w.pfirst,
+                               w.cvotes, w.cstrand, w.clo, w.chi, rv, w.cnt);
+        else
+            hipLaunchKernelGGL(map_cluster_kernel<false>, dim3(grid_for(nr * 64)), dim3(BT), 0, st, ka, w.first, off, nr, g, w.pfirst,
+                               w.cvotes, w.cstrand, w.clo, w.chi, rv, w.cnt);
         PH_HIP(hipGetLastError());
         PH_HIP(scan_excl<uint32_t>(w.pfirst, w.pfirst, nr, w.scratch, st));
         PH_HIP(hipMemcpyAsync(&npairs, w.pfirst + nr, sizeof npairs, hipMemcpyDeviceToHost, st));
@@ -1123,11 +1319,13 @@ int map_candidates(const BwtHandle *h, const polyhip_scoring *sc, const MapShape
 
 // The call on device pointers, on the index's device (the caller has entered it).  *needed = the strings' bytes.
 // af: the extension has affine gaps and only the winners are traced (polyhip_map_reads_affine).
-int map_run(const BwtHandle *h, const polyhip_scoring *sc, const polyhip_map_params *p, const MapAffine *af, const uint8_t *d_reads,
-            const uint64_t *d_off, uint64_t nreads, uint32_t max_len, const MapOut &o, void *d_work, size_t work_bytes, hipStream_t st,
-            uint64_t *needed)
+int map_run(const BwtHandle *h, const RefsHandle *rf, const polyhip_scoring *sc, const polyhip_map_params *p, const MapAffine *af,
+            const uint8_t *d_reads, const uint64_t *d_off, uint64_t nreads, uint32_t max_len, const MapOut &o, void *d_work,
+            size_t work_bytes, hipStream_t st, uint64_t *needed)
 {
-    const char *who = af ? "polyhip_map_reads_affine" : "polyhip_map_reads";
+    const char *who = rf ? "polyhip_map_reads_refs" : af ? "polyhip_map_reads_affine" : "polyhip_map_reads";
+    if (rf)
+        t_rinfo = polyhip_map_refs_info{rf->k, 0};
     polyhip_map_info info{};
     uint64_t traced = 0;
     uint32_t tb_chunks = 0;
@@ -1142,7 +1340,7 @@ int map_run(const BwtHandle *h, const polyhip_scoring *sc, const polyhip_map_par
     PH_REQUIRE(d_off && o.score && o.second && o.flags && o.votes && o.ref_start && o.ref_end && o.read_start && o.read_end && o.err,
                "%s: null argument", who);
     PH_REQUIRE(!strings || (o.alnB && o.alnOff), "%s: alnA without alnB / alnOff", who);
-    const MapShape g = make_shape(p, h->n, max_len);
+    const MapShape g = rf ? make_shape(p, rf, max_len) : make_shape(p, h->n, max_len);
     const uint64_t per = map_chunk_reads(sc, g, af, nreads, d_work ? work_bytes : 0);
     PH_REQUIRE(per > 0, "%s: a workspace of %zu bytes does not hold a chunk of %llu reads (%zu bytes)", who, work_bytes,
                (unsigned long long)std::min<uint64_t>(nreads, MAP_CHUNK),
@@ -1160,14 +1358,15 @@ int map_run(const BwtHandle *h, const polyhip_scoring *sc, const polyhip_map_par
         const uint64_t nr = std::min(per, nreads - r0);
         const uint64_t *off = d_off + r0;
         uint32_t npairs = 0;
-        if (int rc = map_candidates(h, sc, g, af, w, d_reads, off, nr, st, info, &npairs))
+        if (int rc = map_candidates(h, rf, sc, g, af, w, d_reads, off, nr, st, info, &npairs))
             return rc;
         if (af) {
             // the winner of every read from scores, errs and ranks; then the strings of the winners alone
-            hipLaunchKernelGGL(map_reduce_kernel<true>, dim3(grid_for(nr * 64)), dim3(BT), 0, st, w.pfirst, off, nr, g, p->min_score, w.score,
-                               w.endA, w.endB, w.err, w.alnLen, w.slotA, w.slotB, w.stride, w.cvotes, w.cstrand, w.clo, o.score + r0,
-                               o.second + r0, o.flags + r0, o.votes + r0, o.ref_start + r0, o.ref_end + r0, o.read_start + r0,
-                               o.read_end + r0, o.err + r0, w.soff, w.best, w.wfirst, w.cnt);
+            const auto reduce = rf ? map_reduce_kernel<true, true> : map_reduce_kernel<true, false>;
+            hipLaunchKernelGGL(reduce, dim3(grid_for(nr * 64)), dim3(BT), 0, st, w.pfirst, off, nr, g, p->min_score, w.score, w.endA, w.endB,
+                               w.err, w.alnLen, w.slotA, w.slotB, w.stride, w.cvotes, w.cstrand, w.clo, o.score + r0, o.second + r0,
+                               o.flags + r0, o.votes + r0, o.ref_start + r0, o.ref_end + r0, o.read_start + r0, o.read_end + r0,
+                               o.err + r0, w.soff, w.best, w.wfirst, ref_view(rf, w, rf ? o.rid + r0 : nullptr), w.cnt);
             PH_HIP(hipGetLastError());
             uint32_t nwin = 0;
             PH_HIP(scan_excl<uint32_t>(w.wfirst, w.wfirst, nr, w.scratch, st));
@@ -1200,7 +1399,7 @@ int map_run(const BwtHandle *h, const polyhip_scoring *sc, const polyhip_map_par
             hipLaunchKernelGGL(map_reduce_kernel<false>, dim3(grid_for(nr * 64)), dim3(BT), 0, st, w.pfirst, off, nr, g, p->min_score, w.score,
                                w.endA, w.endB, w.err, w.alnLen, w.slotA, w.slotB, w.stride, w.cvotes, w.cstrand, w.clo, o.score + r0,
                                o.second + r0, o.flags + r0, o.votes + r0, o.ref_start + r0, o.ref_end + r0, o.read_start + r0,
-                               o.read_end + r0, o.err + r0, w.soff, w.best, (uint32_t *)nullptr, w.cnt);
+                               o.read_end + r0, o.err + r0, w.soff, w.best, (uint32_t *)nullptr, RefView{}, w.cnt);
             PH_HIP(hipGetLastError());
         }
         if (strings) {
@@ -1220,6 +1419,8 @@ int map_run(const BwtHandle *h, const polyhip_scoring *sc, const polyhip_map_par
     info.clusters = cnt[CNT_CLUSTERS];
     info.reads_mapped = cnt[CNT_MAPPED];
     keep_info(info, af, traced, cnt[CNT_TBCELLS], tb_chunks);
+    if (rf)
+        t_rinfo.straddling = cnt[CNT_STRADDLE];
     *needed = cnt[CNT_N];
     if (strings && *needed > o.capacity)
         return set_error(POLYHIP_ERR_INVALID, "%s: the aligned strings need %llu bytes, the buffers hold %llu", who,
@@ -1242,18 +1443,20 @@ size_t map_workspace(const polyhip_scoring *sc, const MapShape &g, const MapAffi
 
 // The host-pointer calls: polyhip_map_reads (gaps == nullptr) and polyhip_map_reads_affine (gaps = {open, extend}).
 // work_limit: the most workspace the call may use (0: the whole batch, capped).
-int map_host(const char *who, const polyhip_bwt *hp, const polyhip_scoring *sc, const polyhip_map_params *p, const int64_t *gaps,
-             uint64_t work_limit, const uint8_t *reads, const uint64_t *off, uint64_t nreads, uint32_t max_len, int64_t *score,
-             int64_t *second, uint32_t *flags, uint32_t *votes, uint32_t *ref_start, uint32_t *ref_end, uint32_t *read_start,
-             uint32_t *read_end, uint32_t *err, uint8_t *alnA, uint8_t *alnB, uint64_t *alnOff, uint64_t aln_capacity)
+// rf: the call is polyhip_map_reads_refs (hp is then the set's index, NULL for a NULL set) and rid is its extra output.
+int map_host(const char *who, const polyhip_bwt *hp, const RefsHandle *rf, const polyhip_scoring *sc, const polyhip_map_params *p,
+             const int64_t *gaps, uint64_t work_limit, const uint8_t *reads, const uint64_t *off, uint64_t nreads, uint32_t max_len,
+             int64_t *score, int64_t *second, uint32_t *flags, uint32_t *votes, uint32_t *rid, uint32_t *ref_start, uint32_t *ref_end,
+             uint32_t *read_start, uint32_t *read_end, uint32_t *err, uint8_t *alnA, uint8_t *alnB, uint64_t *alnOff,
+             uint64_t aln_capacity)
 {
     if (int rc = validate(who, hp, sc, p, max_len))
         return rc;
     const bool strings = alnA != nullptr;
     uint64_t nbytes = 0;
     if (nreads) {
-        PH_REQUIRE(off && score && second && flags && votes && ref_start && ref_end && read_start && read_end && err, "%s: null argument",
-                   who);
+        PH_REQUIRE(off && score && second && flags && votes && ref_start && ref_end && read_start && read_end && err && (rid || !rf),
+                   "%s: null argument", who);
         PH_REQUIRE(!strings || (alnB && alnOff), "%s: alnA without alnB / alnOff", who);
         for (uint64_t i = 0; i < nreads; ++i)
             PH_REQUIRE(off[i] <= off[i + 1], "%s: offsets are not ascending at %llu", who, (unsigned long long)i);
@@ -1279,10 +1482,15 @@ int map_host(const char *who, const polyhip_bwt *hp, const polyhip_scoring *sc, 
         aff.ge = (int)ge;
         af = &aff;
     }
+    if (rf && !keys_fit(p, rf, max_len))
+        return set_error(POLYHIP_ERR_UNSUPPORTED, "%s: %u contigs, the longest of %u bytes: the sort keys of 256 reads do not fit 64 bits",
+                         who, rf->k, rf->nmax);
     if (nreads == 0) {
         if (alnOff)
             alnOff[0] = 0;
         keep_info(polyhip_map_info{}, af, 0, 0, 0);
+        if (rf)
+            t_rinfo = polyhip_map_refs_info{rf->k, 0};
         return POLYHIP_OK;
     }
     const BwtHandle *h = as_h(hp);
@@ -1294,14 +1502,14 @@ int map_host(const char *who, const polyhip_bwt *hp, const polyhip_scoring *sc, 
         PH_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->dev));
         aff.c = k3a::choose(sc, cus);
     }
-    size_t wb = map_workspace(sc, make_shape(p, h->n, max_len), af, nreads);
+    size_t wb = map_workspace(sc, rf ? make_shape(p, rf, max_len) : make_shape(p, h->n, max_len), af, nreads);
     if (work_limit && work_limit < wb)
         wb = work_limit;
-    // outputs in one block: two int64 and seven uint32 per read, then the string offsets
+    // outputs in one block: two int64 and seven uint32 per read (eight with rid), then the string offsets
     DevBuf dreads, doff, dout, dA, dB, dwork;
     PH_HIP(dreads.alloc(nbytes + 64));
     PH_HIP(doff.alloc((nreads + 1) * sizeof(uint64_t)));
-    PH_HIP(dout.alloc(nreads * (2 * 8 + 7 * 4) + (nreads + 1) * 8));
+    PH_HIP(dout.alloc(nreads * (2 * 8 + (rf ? 8 : 7) * 4) + (nreads + 1) * 8));
     if (strings) {
         PH_HIP(dA.alloc(aln_capacity));
         PH_HIP(dB.alloc(aln_capacity));
@@ -1319,11 +1527,13 @@ int map_host(const char *who, const polyhip_bwt *hp, const polyhip_scoring *sc, 
     uint32_t *d32 = reinterpret_cast<uint32_t *>(dao + nreads + 1);
     const MapOut o{d64, d64 + nreads, d32, d32 + nreads, d32 + 2 * nreads, d32 + 3 * nreads, d32 + 4 * nreads, d32 + 5 * nreads,
                    d32 + 6 * nreads, strings ? dA.as<uint8_t>() : nullptr, strings ? dB.as<uint8_t>() : nullptr, strings ? dao : nullptr,
-                   aln_capacity};
+                   aln_capacity, rf ? d32 + 7 * nreads : nullptr};
     uint64_t needed = 0;
-    const int rc = map_run(h, sc, p, af, dreads.as<uint8_t>(), doff.as<uint64_t>(), nreads, max_len, o, dwork.p, wb, st, &needed);
+    const int rc = map_run(h, rf, sc, p, af, dreads.as<uint8_t>(), doff.as<uint64_t>(), nreads, max_len, o, dwork.p, wb, st, &needed);
     if (rc != POLYHIP_OK && !(strings && needed > aln_capacity))
         return rc;
+    if (rf)
+        PH_HIP(hipMemcpyAsync(rid, o.rid, nreads * 4, hipMemcpyDeviceToHost, st));
     // (a call whose only failure is the strings' capacity still delivers everything else)
     uint32_t *const h32[7] = {flags, votes, ref_start, ref_end, read_start, read_end, err};
     PH_HIP(hipMemcpyAsync(score, o.score, nreads * 8, hipMemcpyDeviceToHost, st));
@@ -1357,17 +1567,18 @@ uint64_t rescue_cols(const polyhip_map_params *p, const polyhip_map_pair_params 
 
 // The paired call on device pointers: d_reads / d_off hold the mates interleaved (2 * npairs reads).  A sibling of map_run's
 // affine branch: the same candidate pass and the same winners' traceback, with the pair rule and the rescue pass between.
-int pairs_run(const BwtHandle *h, const polyhip_scoring *sc, const polyhip_map_params *p, const PairShape &q, const MapAffine *af,
-              const uint8_t *d_reads, const uint64_t *d_off, uint64_t npairs, uint32_t max_len, const MapOut &o, int64_t *o_tlen,
-              void *d_work, size_t work_bytes, hipStream_t st, uint64_t *needed)
+int pairs_run(const char *who, const BwtHandle *h, const RefsHandle *rf, const polyhip_scoring *sc, const polyhip_map_params *p,
+              const PairShape &q, const MapAffine *af, const uint8_t *d_reads, const uint64_t *d_off, uint64_t npairs, uint32_t max_len,
+              const MapOut &o, int64_t *o_tlen, void *d_work, size_t work_bytes, hipStream_t st, uint64_t *needed)
 {
-    const char *who = "polyhip_map_pairs";
+    if (rf)
+        t_rinfo = polyhip_map_refs_info{rf->k, 0};
     polyhip_map_info info{};
     uint64_t traced = 0, attempts = 0;
     *needed = 0;
     const bool strings = o.alnA != nullptr;
     const uint64_t nreads = 2 * npairs;
-    const MapShape g = make_shape(p, h->n, max_len);
+    const MapShape g = rf ? make_shape(p, rf, max_len) : make_shape(p, h->n, max_len);
     const uint64_t per = map_chunk_reads(sc, g, af, nreads, d_work ? work_bytes : 0); // MAP_CHUNK reads are 128 pairs
     PH_REQUIRE(per > 0, "%s: a workspace of %zu bytes does not hold a chunk of %llu pairs (%zu bytes)", who, work_bytes,
                (unsigned long long)(std::min<uint64_t>(nreads, MAP_CHUNK) / 2),
@@ -1383,12 +1594,14 @@ int pairs_run(const BwtHandle *h, const polyhip_scoring *sc, const polyhip_map_p
         const uint64_t nr = std::min(per, nreads - r0), np = nr / 2;
         const uint64_t *off = d_off + r0;
         uint32_t ncand = 0;
-        if (int rc = map_candidates(h, sc, g, af, w, d_reads, off, nr, st, info, &ncand))
+        if (int rc = map_candidates(h, rf, sc, g, af, w, d_reads, off, nr, st, info, &ncand))
             return rc;
+        const RefView rv = ref_view(rf, w, rf ? o.rid + r0 : nullptr);
+        const auto reduce = rf ? pair_reduce_kernel<true> : pair_reduce_kernel<false>;
+        const auto resolve = rf ? pair_resolve_kernel<true> : pair_resolve_kernel<false>;
         // the pair rule on scores, errs, ranks and projections; then the rescue windows it asks for, scored
-        hipLaunchKernelGGL(pair_reduce_kernel, dim3(grid_for(np * 64)), dim3(BT), 0, st, w.pfirst, off, np, g, q, p->min_score, w.score,
-                           w.endA, w.endB, w.err, w.cstrand, w.clo, o.err + r0, w.choice, w.proper, w.ptlen, w.rfirst, w.rstrand, w.rlo,
-                           w.rhi);
+        hipLaunchKernelGGL(reduce, dim3(grid_for(np * 64)), dim3(BT), 0, st, w.pfirst, off, np, g, q, p->min_score, w.score, w.endA,
+                           w.endB, w.err, w.cstrand, w.clo, o.err + r0, w.choice, w.proper, w.ptlen, w.rfirst, w.rstrand, w.rlo, w.rhi, rv);
         PH_HIP(hipGetLastError());
         uint32_t nreq = 0;
         PH_HIP(scan_excl<uint32_t>(w.rfirst, w.rfirst, nr, w.scratch, st));
@@ -1410,10 +1623,10 @@ int pairs_run(const BwtHandle *h, const polyhip_scoring *sc, const polyhip_map_p
                                          w.rerr, w.band, k3a::grid_blocks(af->c, nreq, w.lenW), st))
                 return rc;
         }
-        hipLaunchKernelGGL(pair_resolve_kernel, dim3(grid_for(np * 64)), dim3(BT), 0, st, w.pfirst, off, np, g, q, p->min_score, w.score,
-                           w.endA, w.endB, w.cvotes, w.cstrand, w.clo, w.choice, w.proper, w.ptlen, w.rfirst, w.rstrand, w.rlo, w.rscore,
-                           w.rendA, w.rendB, w.rerr, o.score + r0, o.second + r0, o.flags + r0, o.votes + r0, o.ref_start + r0,
-                           o.ref_end + r0, o.read_start + r0, o.read_end + r0, o_tlen + r0 / 2, w.soff, w.best, w.wfirst, w.cnt);
+        hipLaunchKernelGGL(resolve, dim3(grid_for(np * 64)), dim3(BT), 0, st, w.pfirst, off, np, g, q, p->min_score, w.score, w.endA,
+                           w.endB, w.cvotes, w.cstrand, w.clo, w.choice, w.proper, w.ptlen, w.rfirst, w.rstrand, w.rlo, w.rscore, w.rendA,
+                           w.rendB, w.rerr, o.score + r0, o.second + r0, o.flags + r0, o.votes + r0, o.ref_start + r0, o.ref_end + r0,
+                           o.read_start + r0, o.read_end + r0, o_tlen + r0 / 2, w.soff, w.best, w.wfirst, rv, w.cnt);
         PH_HIP(hipGetLastError());
         uint32_t nwin = 0;
         PH_HIP(scan_excl<uint32_t>(w.wfirst, w.wfirst, nr, w.scratch, st));
@@ -1457,6 +1670,8 @@ int pairs_run(const BwtHandle *h, const polyhip_scoring *sc, const polyhip_map_p
     PH_HIP(hipStreamSynchronize(st));
     t_pinfo = polyhip_map_pairs_info{cnt[CNT_SEEDS], cnt[CNT_OVER], info.hits, cnt[CNT_CLUSTERS], info.pairs_aligned, cnt[CNT_MAPPED],
                                      cnt[CNT_PROPER], attempts, cnt[CNT_RESCUED], traced, info.chunks};
+    if (rf)
+        t_rinfo.straddling = cnt[CNT_STRADDLE];
     *needed = cnt[CNT_N];
     if (strings && *needed > o.capacity)
         return set_error(POLYHIP_ERR_INVALID, "%s: the aligned strings need %llu bytes, the buffers hold %llu", who,
@@ -1464,19 +1679,21 @@ int pairs_run(const BwtHandle *h, const polyhip_scoring *sc, const polyhip_map_p
     return POLYHIP_OK;
 }
 
-int pairs_host(const polyhip_bwt *hp, const polyhip_scoring *sc, const polyhip_map_params *p, const polyhip_map_pair_params *pp,
-               int64_t go, int64_t ge, const uint8_t *reads1, const uint64_t *off1, const uint8_t *reads2, const uint64_t *off2,
-               uint64_t npairs, uint32_t max_len, uint64_t work_limit, int64_t *score, int64_t *second, uint32_t *flags, uint32_t *votes,
-               uint32_t *ref_start, uint32_t *ref_end, uint32_t *read_start, uint32_t *read_end, uint32_t *err, int64_t *tlen,
-               uint8_t *alnA, uint8_t *alnB, uint64_t *alnOff, uint64_t aln_capacity)
+// rf: the call is polyhip_map_pairs_refs (hp is then the set's index, NULL for a NULL set) and rid is its extra output.
+int pairs_host(const char *who, const polyhip_bwt *hp, const RefsHandle *rf, const polyhip_scoring *sc, const polyhip_map_params *p,
+               const polyhip_map_pair_params *pp, int64_t go, int64_t ge, const uint8_t *reads1, const uint64_t *off1,
+               const uint8_t *reads2, const uint64_t *off2, uint64_t npairs, uint32_t max_len, uint64_t work_limit, int64_t *score,
+               int64_t *second, uint32_t *flags, uint32_t *votes, uint32_t *rid, uint32_t *ref_start, uint32_t *ref_end,
+               uint32_t *read_start, uint32_t *read_end, uint32_t *err, int64_t *tlen, uint8_t *alnA, uint8_t *alnB, uint64_t *alnOff,
+               uint64_t aln_capacity)
 {
-    const char *who = "polyhip_map_pairs";
     if (int rc = validate(who, hp, sc, p, max_len))
         return rc;
     const bool strings = alnA != nullptr;
     uint64_t nb1 = 0, nb2 = 0;
     if (npairs) {
-        PH_REQUIRE(off1 && off2 && score && second && flags && votes && ref_start && ref_end && read_start && read_end && err && tlen,
+        PH_REQUIRE(off1 && off2 && score && second && flags && votes && ref_start && ref_end && read_start && read_end && err && tlen &&
+                       (rid || !rf),
                    "%s: null argument", who);
         PH_REQUIRE(!strings || (alnB && alnOff), "%s: alnA without alnB / alnOff", who);
         for (uint64_t i = 0; i < npairs; ++i)
@@ -1507,10 +1724,15 @@ int pairs_host(const polyhip_bwt *hp, const polyhip_scoring *sc, const polyhip_m
         return set_error(POLYHIP_ERR_UNSUPPORTED,
                          "%s: a rescue window of max_insert - min_insert + max_len + 2 * band = %llu columns exceeds %u", who,
                          (unsigned long long)wide, MAP_MAX_RESCUE);
+    if (rf && !keys_fit(p, rf, max_len))
+        return set_error(POLYHIP_ERR_UNSUPPORTED, "%s: %u contigs, the longest of %u bytes: the sort keys of 256 reads do not fit 64 bits",
+                         who, rf->k, rf->nmax);
     if (npairs == 0) {
         if (alnOff)
             alnOff[0] = 0;
         t_pinfo = polyhip_map_pairs_info{};
+        if (rf)
+            t_rinfo = polyhip_map_refs_info{rf->k, 0};
         return POLYHIP_OK;
     }
     PH_REQUIRE(npairs < (1ull << 31), "%s: %llu pairs exceed 2^31 - 1", who, (unsigned long long)npairs);
@@ -1528,7 +1750,7 @@ int pairs_host(const polyhip_bwt *hp, const polyhip_scoring *sc, const polyhip_m
     aff.c = k3a::choose(sc, cus);
     const PairShape q{(int64_t)pp->min_insert, (int64_t)pp->max_insert, pp->rescue};
     const uint64_t nreads = 2 * npairs, nbytes = nb1 + nb2;
-    size_t wb = map_workspace(sc, make_shape(p, h->n, max_len), &aff, nreads);
+    size_t wb = map_workspace(sc, rf ? make_shape(p, rf, max_len) : make_shape(p, h->n, max_len), &aff, nreads);
     if (work_limit && work_limit < wb)
         wb = work_limit;
     // the mates as they came, the interleaved batch, and the outputs in one block: two int64 and seven uint32 per mate, the
@@ -1539,7 +1761,7 @@ int pairs_host(const polyhip_bwt *hp, const polyhip_scoring *sc, const polyhip_m
     PH_HIP(dreads.alloc(nbytes + 64));
     PH_HIP(doff.alloc((nreads + 1) * sizeof(uint64_t)));
     PH_HIP(dscan.alloc(scan_scratch_bytes<uint64_t>(nreads)));
-    PH_HIP(dout.alloc(nreads * (2 * 8 + 7 * 4) + (nreads + 1) * 8 + npairs * 8));
+    PH_HIP(dout.alloc(nreads * (2 * 8 + (rf ? 8 : 7) * 4) + (nreads + 1) * 8 + npairs * 8));
     if (strings) {
         PH_HIP(dA.alloc(aln_capacity));
         PH_HIP(dB.alloc(aln_capacity));
@@ -1570,11 +1792,14 @@ int pairs_host(const polyhip_bwt *hp, const polyhip_scoring *sc, const polyhip_m
     uint32_t *d32 = reinterpret_cast<uint32_t *>(dao + nreads + 1);
     const MapOut o{d64, d64 + nreads, d32, d32 + nreads, d32 + 2 * nreads, d32 + 3 * nreads, d32 + 4 * nreads, d32 + 5 * nreads,
                    d32 + 6 * nreads, strings ? dA.as<uint8_t>() : nullptr, strings ? dB.as<uint8_t>() : nullptr, strings ? dao : nullptr,
-                   aln_capacity};
+                   aln_capacity, rf ? d32 + 7 * nreads : nullptr};
     uint64_t needed = 0;
-    const int rc = pairs_run(h, sc, p, q, &aff, dreads.as<uint8_t>(), doff.as<uint64_t>(), npairs, max_len, o, dtl, dwork.p, wb, st, &needed);
+    const int rc = pairs_run(who, h, rf, sc, p, q, &aff, dreads.as<uint8_t>(), doff.as<uint64_t>(), npairs, max_len, o, dtl, dwork.p, wb, st,
+                             &needed);
     if (rc != POLYHIP_OK && !(strings && needed > aln_capacity))
         return rc;
+    if (rf)
+        PH_HIP(hipMemcpyAsync(rid, o.rid, nreads * 4, hipMemcpyDeviceToHost, st));
     // (a call whose only failure is the strings' capacity still delivers everything else)
     uint32_t *const h32[7] = {flags, votes, ref_start, ref_end, read_start, read_end, err};
     PH_HIP(hipMemcpyAsync(score, o.score, nreads * 8, hipMemcpyDeviceToHost, st));
@@ -1623,7 +1848,7 @@ int polyhip_map_reads_dev(const polyhip_bwt *hp, const polyhip_scoring *sc, cons
     const MapOut o{d_score, d_second, d_flags, d_votes, d_ref_start, d_ref_end, d_read_start, d_read_end, d_err, d_alnA, d_alnB, d_alnOff,
                    aln_capacity};
     uint64_t needed = 0;
-    return map_run(h, sc, p, nullptr, d_reads, d_off, nreads, max_len, o, d_work, work_bytes, as_stream(stream), &needed);
+    return map_run(h, nullptr, sc, p, nullptr, d_reads, d_off, nreads, max_len, o, d_work, work_bytes, as_stream(stream), &needed);
 }
 
 int polyhip_map_reads(const polyhip_bwt *hp, const polyhip_scoring *sc, const polyhip_map_params *p, const uint8_t *reads,
@@ -1631,8 +1856,8 @@ int polyhip_map_reads(const polyhip_bwt *hp, const polyhip_scoring *sc, const po
                       uint32_t *votes, uint32_t *ref_start, uint32_t *ref_end, uint32_t *read_start, uint32_t *read_end, uint32_t *err,
                       uint8_t *alnA, uint8_t *alnB, uint64_t *alnOff, uint64_t aln_capacity)
 {
-    return map_host("polyhip_map_reads", hp, sc, p, nullptr, 0, reads, off, nreads, max_len, score, second, flags, votes, ref_start,
-                    ref_end, read_start, read_end, err, alnA, alnB, alnOff, aln_capacity);
+    return map_host("polyhip_map_reads", hp, nullptr, sc, p, nullptr, 0, reads, off, nreads, max_len, score, second, flags, votes, nullptr,
+                    ref_start, ref_end, read_start, read_end, err, alnA, alnB, alnOff, aln_capacity);
 }
 
 int polyhip_map_reads_affine(const polyhip_bwt *hp, const polyhip_scoring *sc, const polyhip_map_params *p, int64_t gap_open,
@@ -1642,8 +1867,40 @@ int polyhip_map_reads_affine(const polyhip_bwt *hp, const polyhip_scoring *sc, c
                              uint64_t *alnOff, uint64_t aln_capacity)
 {
     const int64_t gaps[2] = {gap_open, gap_extend};
-    return map_host("polyhip_map_reads_affine", hp, sc, p, gaps, work_limit, reads, off, nreads, max_len, score, second, flags, votes,
-                    ref_start, ref_end, read_start, read_end, err, alnA, alnB, alnOff, aln_capacity);
+    return map_host("polyhip_map_reads_affine", hp, nullptr, sc, p, gaps, work_limit, reads, off, nreads, max_len, score, second, flags,
+                    votes, nullptr, ref_start, ref_end, read_start, read_end, err, alnA, alnB, alnOff, aln_capacity);
+}
+
+int polyhip_map_reads_refs(const polyhip_refs *rp, const polyhip_scoring *sc, const polyhip_map_params *p, int64_t gap_open,
+                           int64_t gap_extend, const uint8_t *reads, const uint64_t *off, uint64_t nreads, uint32_t max_len,
+                           uint64_t work_limit, int64_t *score, int64_t *second, uint32_t *flags, uint32_t *votes, uint32_t *rid,
+                           uint32_t *ref_start, uint32_t *ref_end, uint32_t *read_start, uint32_t *read_end, uint32_t *err, uint8_t *alnA,
+                           uint8_t *alnB, uint64_t *alnOff, uint64_t aln_capacity)
+{
+    const int64_t gaps[2] = {gap_open, gap_extend};
+    const RefsHandle *rf = as_refs(rp);
+    return map_host("polyhip_map_reads_refs", rf ? rf->index : nullptr, rf, sc, p, gaps, work_limit, reads, off, nreads, max_len, score,
+                    second, flags, votes, rid, ref_start, ref_end, read_start, read_end, err, alnA, alnB, alnOff, aln_capacity);
+}
+
+int polyhip_map_pairs_refs(const polyhip_refs *rp, const polyhip_scoring *sc, const polyhip_map_params *p,
+                           const polyhip_map_pair_params *pp, int64_t gap_open, int64_t gap_extend, const uint8_t *reads1,
+                           const uint64_t *off1, const uint8_t *reads2, const uint64_t *off2, uint64_t npairs, uint32_t max_len,
+                           uint64_t work_limit, int64_t *score, int64_t *second, uint32_t *flags, uint32_t *votes, uint32_t *rid,
+                           uint32_t *ref_start, uint32_t *ref_end, uint32_t *read_start, uint32_t *read_end, uint32_t *err, int64_t *tlen,
+                           uint8_t *alnA, uint8_t *alnB, uint64_t *alnOff, uint64_t aln_capacity)
+{
+    const RefsHandle *rf = as_refs(rp);
+    return pairs_host("polyhip_map_pairs_refs", rf ? rf->index : nullptr, rf, sc, p, pp, gap_open, gap_extend, reads1, off1, reads2, off2,
+                      npairs, max_len, work_limit, score, second, flags, votes, rid, ref_start, ref_end, read_start, read_end, err, tlen,
+                      alnA, alnB, alnOff, aln_capacity);
+}
+
+int polyhip_map_refs_last_info(polyhip_map_refs_info *info)
+{
+    PH_REQUIRE(info, "polyhip_map_refs_last_info: null argument");
+    *info = t_rinfo;
+    return POLYHIP_OK;
 }
 
 int polyhip_map_pairs(const polyhip_bwt *hp, const polyhip_scoring *sc, const polyhip_map_params *p, const polyhip_map_pair_params *pp,
@@ -1652,8 +1909,9 @@ int polyhip_map_pairs(const polyhip_bwt *hp, const polyhip_scoring *sc, const po
                       uint32_t *flags, uint32_t *votes, uint32_t *ref_start, uint32_t *ref_end, uint32_t *read_start, uint32_t *read_end,
                       uint32_t *err, int64_t *tlen, uint8_t *alnA, uint8_t *alnB, uint64_t *alnOff, uint64_t aln_capacity)
 {
-    return pairs_host(hp, sc, p, pp, gap_open, gap_extend, reads1, off1, reads2, off2, npairs, max_len, work_limit, score, second, flags,
-                      votes, ref_start, ref_end, read_start, read_end, err, tlen, alnA, alnB, alnOff, aln_capacity);
+    return pairs_host("polyhip_map_pairs", hp, nullptr, sc, p, pp, gap_open, gap_extend, reads1, off1, reads2, off2, npairs, max_len,
+                      work_limit, score, second, flags, votes, nullptr, ref_start, ref_end, read_start, read_end, err, tlen, alnA, alnB,
+                      alnOff, aln_capacity);
 }
 
 int polyhip_map_pairs_last_info(polyhip_map_pairs_info *info)

@@ -73,6 +73,7 @@ class MapResult:
     aln_off: np.ndarray | None = None
     status: int = 0
     tlen: np.ndarray | None = None      # map_pairs_packed only: one entry per pair
+    rid: np.ndarray | None = None       # the refs calls only: the contig of every entry (ref_start / ref_end are local to it)
 
 
 @dataclass
@@ -89,6 +90,7 @@ class MapRecord:
     alignA: object
     alignB: object
     err: int
+    rid: int = 0
 
 
 def _strings_short() -> bool:
@@ -109,10 +111,11 @@ def workspace_bytes(index, scoring, params: MapParams, nreads: int, max_len: int
 
 
 def _packed(call, buf: np.ndarray, offs: np.ndarray, params: MapParams | None, strings: bool, capacity: int | None,
-            max_len: int | None, per_read: int = 1) -> MapResult:
+            max_len: int | None, per_read: int = 1, with_rid: bool = False) -> MapResult:
     """what the host-pointer entry points share: the output arrays, the retry with the exact string capacity, the strings as
     lists.  call(params, reads, offs, n, max_len, *outputs, capacity) -> status.  per_read: output entries per read of
-    ``offs`` (2 for pairs, whose second batch the caller holds)"""
+    ``offs`` (2 for pairs, whose second batch the caller holds).  with_rid: the outputs hold ``rid`` before ``ref_start``
+    (the refs calls)"""
     params = params or MapParams()
     nin = len(offs) - 1
     n = nin * per_read
@@ -123,6 +126,8 @@ def _packed(call, buf: np.ndarray, offs: np.ndarray, params: MapParams | None, s
     p = params._c()
     score, second = np.zeros(n, np.int64), np.zeros(n, np.int64)
     u32 = [np.zeros(n, np.uint32) for _ in range(7)]
+    rid = np.zeros(n, np.uint32) if with_rid else None
+    outs = u32[:2] + ([rid] if with_rid else []) + u32[2:]
     off = np.zeros(n + 1, np.uint64)
     cap = int(capacity) if capacity is not None else int(int(offs[nin] - offs[0]) * 1.25 * per_read) + (64 << 10)
     alnA = alnB = None
@@ -131,7 +136,7 @@ def _packed(call, buf: np.ndarray, offs: np.ndarray, params: MapParams | None, s
         if strings:
             alnA, alnB = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.uint8)
         rc = call(C.byref(p), buf.ctypes.data, offs.ctypes.data, nin, int(max_len),
-                  score.ctypes.data, second.ctypes.data, *[a.ctypes.data for a in u32],
+                  score.ctypes.data, second.ctypes.data, *[a.ctypes.data for a in outs],
                   alnA.ctypes.data if strings else None, alnB.ctypes.data if strings else None, off.ctypes.data if strings else None, cap)
         if strings and rc == _lib.ERR_INVALID and _strings_short():  # the strings did not fit: off[n] says what they need
             if capacity is not None:
@@ -145,7 +150,7 @@ def _packed(call, buf: np.ndarray, offs: np.ndarray, params: MapParams | None, s
         o = off.astype(np.int64)
         sa = [alnA[o[i]:o[i + 1]].tobytes() for i in range(n)]
         sb = [alnB[o[i]:o[i + 1]].tobytes() for i in range(n)]
-    return MapResult(score, second, *u32, sa, sb, off if strings else None, int(rc))
+    return MapResult(score, second, *u32, sa, sb, off if strings else None, int(rc), rid=rid)
 
 
 def map_reads_packed(index, scoring, buf: np.ndarray, offs: np.ndarray, params: MapParams | None = None, strings: bool = True,
@@ -278,6 +283,87 @@ def MapPairs(index, scoring, reads1, reads2, gap_open: int, gap_extend: int, pai
                          int(r.votes[i]), int(r.ref_start[i]), int(r.ref_end[i]), int(r.read_start[i]), int(r.read_end[i]),
                          conv(r.alignA[i]), conv(r.alignB[i]), int(r.err[i]))
     return [(rec(2 * i), rec(2 * i + 1), bool(r.flags[2 * i] & FLAG_PROPER), int(r.tlen[i])) for i in range(len(reads1))]
+
+
+# ---- a reference of several contigs (polyhip_map_reads_refs, polyhip_map_pairs_refs; host pointers only) -------------------
+class _CRefsInfo(C.Structure):
+    _fields_ = [("contigs", C.c_uint64), ("straddling", C.c_uint64)]
+
+
+def last_refs_info() -> dict:
+    """polyhip_map_refs_last_info: the contigs of the calling thread's last refs call and the seed occurrences it dropped
+    because they straddle a boundary (the other counters are last_affine_info's / last_pairs_info's)"""
+    info = _CRefsInfo()
+    _lib.check(_lib.lib().polyhip_map_refs_last_info(C.byref(info)))
+    return {name: int(getattr(info, name)) for name, _ in _CRefsInfo._fields_}
+
+
+def map_reads_refs_packed(refset, scoring, gap_open: int, gap_extend: int, buf: np.ndarray, offs: np.ndarray,
+                          params: MapParams | None = None, strings: bool = True, capacity: int | None = None,
+                          max_len: int | None = None, work_limit: int = 0) -> MapResult:
+    """map_reads_affine_packed on a ``refs.RefSet``: no seed, cluster, window or alignment crosses a contig boundary;
+    ``rid`` is every entry's contig and ``ref_start`` / ``ref_end`` are positions in it (gap_open == gap_extend: linear gaps)"""
+    def call(p, reads, off, n, max_len_, *rest):
+        return _lib.lib().polyhip_map_reads_refs(refset.handle(), scoring.handle(), p, int(gap_open), int(gap_extend), reads, off, n,
+                                                 max_len_, int(work_limit), *rest)
+    return _packed(call, buf, offs, params, strings, capacity, max_len, with_rid=True)
+
+
+def _record(r: MapResult, i: int, conv) -> MapRecord:
+    return MapRecord(bool(r.flags[i] & FLAG_MAPPED), bool(r.flags[i] & FLAG_REVERSE), int(r.score[i]), int(r.second[i]),
+                     int(r.votes[i]), int(r.ref_start[i]), int(r.ref_end[i]), int(r.read_start[i]), int(r.read_end[i]),
+                     conv(r.alignA[i]), conv(r.alignB[i]), int(r.err[i]), int(r.rid[i]))
+
+
+def MapReadsRefs(refset, scoring, reads, gap_open: int, gap_extend: int, params: MapParams | None = None) -> list:
+    """Every read of a list placed on the set -> list of MapRecord (``rid`` = the contig, ``refset.names[rid]`` its name)"""
+    as_str = bool(reads) and all(isinstance(r, str) for r in reads)
+    buf, offs = _pack(reads)
+    r = map_reads_refs_packed(refset, scoring, gap_open, gap_extend, buf, offs, params)
+    conv = (lambda b: b.decode("latin-1")) if as_str else (lambda b: b)
+    return [_record(r, i, conv) for i in range(len(reads))]
+
+
+def map_pairs_refs_packed(refset, scoring, gap_open: int, gap_extend: int, buf1: np.ndarray, offs1: np.ndarray, buf2: np.ndarray,
+                          offs2: np.ndarray, params: MapParams | None = None, pair_params: PairParams | None = None,
+                          strings: bool = True, capacity: int | None = None, max_len: int | None = None,
+                          work_limit: int = 0) -> MapResult:
+    """map_pairs_packed on a ``refs.RefSet``: a proper pair lies on one contig, a rescue window inside the anchor's"""
+    if pair_params is None:
+        raise ValueError("map_pairs_refs_packed: pair_params is required")
+    n = len(offs1) - 1
+    if len(offs2) - 1 != n:
+        raise ValueError("map_pairs_refs_packed: the two batches hold different numbers of reads")
+    buf2 = np.ascontiguousarray(buf2, dtype=np.uint8)
+    offs2 = np.ascontiguousarray(offs2, dtype=np.uint64)
+    if max_len is None:
+        max_len = max((int(np.diff(o.astype(np.int64)).max()) for o in (np.asarray(offs1), offs2)), default=0) if n else 0
+    pp = pair_params._c()
+    tlen = np.zeros(n, np.int64)
+
+    def call(p, reads, off, n_, max_len_, *rest):
+        per_mate, tail = rest[:10], rest[10:]
+        return _lib.lib().polyhip_map_pairs_refs(refset.handle(), scoring.handle(), p, C.byref(pp), int(gap_open), int(gap_extend),
+                                                 reads, off, buf2.ctypes.data, offs2.ctypes.data, n_, max_len_, int(work_limit),
+                                                 *per_mate, tlen.ctypes.data, *tail)
+    r = _packed(call, buf1, offs1, params, strings, capacity, max_len, per_read=2, with_rid=True)
+    r.tlen = tlen
+    return r
+
+
+def MapPairsRefs(refset, scoring, reads1, reads2, gap_open: int, gap_extend: int, pair_params: PairParams,
+                 params: MapParams | None = None) -> list:
+    """Every pair placed on the set -> list of (MapRecord, MapRecord, proper, tlen)"""
+    if len(reads1) != len(reads2):
+        raise ValueError("MapPairsRefs: reads1 and reads2 differ in length")
+    both = list(reads1) + list(reads2)
+    as_str = bool(both) and all(isinstance(r, str) for r in both)
+    buf1, offs1 = _pack(reads1)
+    buf2, offs2 = _pack(reads2)
+    r = map_pairs_refs_packed(refset, scoring, gap_open, gap_extend, buf1, offs1, buf2, offs2, params, pair_params)
+    conv = (lambda b: b.decode("latin-1")) if as_str else (lambda b: b)
+    return [(_record(r, 2 * i, conv), _record(r, 2 * i + 1, conv), bool(r.flags[2 * i] & FLAG_PROPER), int(r.tlen[i]))
+            for i in range(len(reads1))]
 
 
 # ---- device-resident entry point (torch CUDA tensors) ---------------------------------------------------------------------

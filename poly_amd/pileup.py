@@ -126,3 +126,38 @@ def pileup(result, ref, records=None, region=None, min_mapq: int = 0, min_depth:
     return pileup_packed(result.flags, result.ref_start, result.ref_end, np.frombuffer(a, np.uint8), np.frombuffer(b, np.uint8), off,
                          ref, None if records is None else records.mapq, region, min_mapq, min_depth, min_alt_count,
                          min_alt_permille, site_capacity)
+
+
+def pileup_refs(result, refs, contig: int, records=None, region=None, min_mapq: int = 0, min_depth: int = 1,
+                min_alt_count: int = 1, min_alt_permille: int = 0, site_capacity: int | None = None) -> Pileup:
+    """The pileup of one contig of a ``refs.RefSet`` from the result of ``mapper.map_reads_refs_packed`` /
+    ``map_pairs_refs_packed`` on that set.  ``region``: (lo, hi) inside the contig, the whole contig by default.
+    polyhip_pileup runs on the set's concatenated text (``refs.text()``, read back from the index) with every entry moved
+    to ``ref_start + starts[rid]`` and the region to ``[starts[contig] + lo, starts[contig] + hi)``; entries of other contigs
+    are passed as unmapped.  No alignment crosses a contig, so nothing else is needed.  The Pileup that comes back is local
+    to the contig: ``region_lo`` and the sites' ``pos`` are positions in it."""
+    if result.alignA is None or result.alignB is None:
+        raise ValueError("pileup.pileup_refs: the MapResult holds no strings")
+    if result.rid is None:
+        raise ValueError("pileup.pileup_refs: the MapResult holds no contigs (it is not the result of a refs call)")
+    c = int(contig)
+    if not 0 <= c < len(refs):
+        raise ValueError(f"pileup.pileup_refs: contig {c} of {len(refs)}")
+    base, length = int(refs.starts[c]), int(refs.lengths[c])
+    lo, hi = (0, length) if region is None else (int(region[0]), int(region[1]))
+    if not 0 <= lo <= hi <= length:
+        raise ValueError(f"pileup.pileup_refs: region [{lo}, {hi}) is not inside the contig of {length} bytes")
+    a, b = b"".join(result.alignA), b"".join(result.alignB)
+    off = np.zeros(len(result.alignA) + 1, np.uint64)
+    off[1:] = np.cumsum([len(s) for s in result.alignA], dtype=np.uint64)
+    ref = refs.text()
+    here = np.asarray(result.rid) == c
+    shift = refs.starts[np.asarray(result.rid, dtype=np.int64)]
+    flags = np.where(here, result.flags, 0).astype(np.uint32)
+    out = pileup_packed(flags, (result.ref_start + shift).astype(np.uint32), (result.ref_end + shift).astype(np.uint32),
+                        np.frombuffer(a, np.uint8), np.frombuffer(b, np.uint8), off, ref, None if records is None else records.mapq,
+                        (base + lo, base + hi), min_mapq, min_depth, min_alt_count, min_alt_permille, site_capacity)
+    out.region_lo = lo
+    if out.sites is not None:
+        out.sites["pos"] -= np.uint32(base)
+    return out

@@ -161,3 +161,44 @@ def write(fh, ref_name: str, ref_len: int, names, reads, quals, result, records:
         if live[i]:
             fields += [f"NM:i:{int(records.nm[i])}", f"MD:Z:{records.md_string(i)}", f"AS:i:{int(result.score[i])}"]
         fh.write("\t".join(fields) + "\n")
+
+
+def write_refs(fh, refs, names, reads, quals, result, records: AlnRecords, paired: bool = False) -> None:
+    """``write`` for the result of ``mapper.map_reads_refs_packed`` / ``map_pairs_refs_packed`` on the ``refs.RefSet`` it was
+    mapped to: one @SQ line per contig, in the set's order; RNAME is the name of ``result.rid[i]``'s contig and POS a position
+    in it.  With ``paired``: RNEXT is '=' when the live mate is on the same contig (an entry that is not live takes its live
+    mate's RNAME and POS, so '=' too), else the mate's contig name; TLEN is 0 unless both mates are live on one contig.
+    Everything else is ``write``'s."""
+    n = len(records.sam_flag)
+    fh.write("@HD\tVN:1.6\tSO:unsorted\n")
+    for name, length in zip(refs.names, refs.lengths):
+        fh.write(f"@SQ\tSN:{name}\tLN:{int(length)}\n")
+    live = (records.sam_flag & FLAG_UNMAPPED) == 0
+    for i in range(n):
+        flag = int(records.sam_flag[i])
+        rname, pos, mapq, cigar = "*", 0, 0, "*"
+        if live[i]:
+            rname, pos, mapq, cigar = refs.names[int(result.rid[i])], int(result.ref_start[i]) + 1, int(records.mapq[i]), \
+                records.cigar_string(i)
+        rnext, pnext, tlen = "*", 0, 0
+        if paired and live[i ^ 1]:
+            m = i ^ 1
+            mate_name = refs.names[int(result.rid[m])]
+            pnext = int(result.ref_start[m]) + 1
+            if live[i]:
+                rnext = "=" if result.rid[i] == result.rid[m] else mate_name
+                if result.rid[i] == result.rid[m]:
+                    first = i if (int(result.ref_start[i]), i) <= (int(result.ref_start[m]), m) else m
+                    tlen = int(result.tlen[i >> 1]) * (1 if first == i else -1)
+            else:
+                rname, pos, rnext = mate_name, pnext, "="
+        seq = reads[i] if isinstance(reads[i], bytes) else _text(reads[i]).encode("latin-1")
+        qual = None if quals is None else _text(quals[i])
+        if live[i] and flag & FLAG_REVERSE:
+            seq = _revcomp(seq).replace(b"\x00", b"N")
+            qual = None if qual is None else qual[::-1]
+        fields = [_text(names[i]), str(flag), rname, str(pos), str(mapq), cigar, rnext, str(pnext), str(tlen),
+                  _text(seq) or "*", qual or "*"]
+        if live[i]:
+            fields += [f"NM:i:{int(records.nm[i])}", f"MD:Z:{records.md_string(i)}", f"AS:i:{int(result.score[i])}"]
+        fh.write("\t".join(fields) + "\n")
