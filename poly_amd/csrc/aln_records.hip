@@ -10,7 +10,7 @@
 // masks with __ballot.  A run starts where a class mask has a bit its own left shift lacks (the last class of the step
 // before is carried into bit 0), so the runs of a step, their lengths and their output slots are popcounts and leading-zero
 // counts of wave-uniform masks; only the MD bytes, whose decimal widths differ per lane, take a wave scan.  No LDS.
-#include "bwt_index.h"
+#include "device_prims.h"
 #include "host_pipeline.h"
 
 namespace polyhip {
@@ -33,8 +33,6 @@ __device__ __forceinline__ void put_dec(uint8_t *p, uint32_t k, uint32_t w)
     }
 }
 
-__device__ __forceinline__ uint64_t lanes_below(int lane) { return (1ull << lane) - 1ull; }
-__device__ __forceinline__ int top_bit(uint64_t m) { return 63 - __clzll((long long)m); } // m != 0
 __device__ __forceinline__ uint32_t wave_total(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)dpp_incl_scan(v), 63); }
 
 // EMIT == false: ncig / nmd (uint64, n + 1 slots for the scans), nm and err are written, cigar / md are not touched.
@@ -218,25 +216,6 @@ __global__ __launch_bounds__(BT) void finish_kernel(uint64_t n, uint32_t paired,
 
 thread_local polyhip_aln_records_info t_info{};
 
-unsigned grid_of(uint64_t items, uint64_t per_block)
-{
-    const uint64_t nb = (items + per_block - 1) / per_block;
-    return (unsigned)std::min<uint64_t>(std::max<uint64_t>(nb, 1), 1u << 20);
-}
-
-// one device allocation, carved in 256-byte steps
-struct Arena {
-    DevBuf buf;
-    size_t used = 0;
-    size_t reserve(size_t bytes)
-    {
-        const size_t at = used;
-        used += align256(bytes ? bytes : 1);
-        return at;
-    }
-    template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(buf.as<uint8_t>() + off); }
-};
-
 } // namespace
 } // namespace polyhip
 
@@ -294,7 +273,7 @@ int polyhip_aln_records(const polyhip_aln_records_params *params, uint64_t n, co
             PH_HIP(hipMemcpyAsync(w.at<uint8_t>(x.at), x.src, x.bytes, hipMemcpyHostToDevice, st));
     PH_HIP(hipMemsetAsync(w.at<uint8_t>(o_info), 0, 3 * sizeof(unsigned long long), st));
 
-    const unsigned wgrid = grid_of(n, AR_WAVES);
+    const unsigned wgrid = grid_for(n, AR_WAVES, 1u << 20);
     hipLaunchKernelGGL(records_kernel<false>, dim3(wgrid), dim3(BT), 0, st, n, params->eqx, w.at<uint32_t>(o_flags), w.at<uint32_t>(o_rs),
                        w.at<uint32_t>(o_re), w.at<uint32_t>(o_rl), w.at<uint8_t>(o_a), w.at<uint8_t>(o_b), w.at<uint64_t>(o_off),
                        w.at<uint64_t>(o_coff), w.at<uint64_t>(o_moff), w.at<uint32_t>(o_nm), w.at<uint32_t>(o_err), (uint32_t *)nullptr,
@@ -302,7 +281,7 @@ int polyhip_aln_records(const polyhip_aln_records_params *params, uint64_t n, co
     PH_HIP(hipGetLastError());
     PH_HIP(scan_excl<uint64_t>(w.at<uint64_t>(o_coff), w.at<uint64_t>(o_coff), n, w.at<uint8_t>(o_scan), st));
     PH_HIP(scan_excl<uint64_t>(w.at<uint64_t>(o_moff), w.at<uint64_t>(o_moff), n, w.at<uint8_t>(o_scan), st));
-    hipLaunchKernelGGL(finish_kernel, dim3(std::min(grid_of(n, BT), 1024u)), dim3(BT), 0, st, n, params->paired, w.at<uint32_t>(o_flags),
+    hipLaunchKernelGGL(finish_kernel, dim3(grid_for(n, BT, 1024)), dim3(BT), 0, st, n, params->paired, w.at<uint32_t>(o_flags),
                        w.at<int64_t>(o_score), w.at<int64_t>(o_second), w.at<uint64_t>(o_off), w.at<uint32_t>(o_err), w.at<uint8_t>(o_mapq),
                        w.at<uint32_t>(o_sf), w.at<unsigned long long>(o_info));
     PH_HIP(hipGetLastError());

@@ -9,9 +9,9 @@
 //      byte order, '$' = 0) and the layout (choose_layout: the one place that decides).
 //   2. suffix array by prefix doubling: round 0 sorts every suffix by its first k symbols packed into one 64-bit
 //      key (k = 64 / bits(sigma): 21 for DNA), round r by (rank[i], rank[i + h]) with h = k * 2^(r-1); each round
-//      is an LSD radix sort over the key's significant bits only (histogram / exclusive scan / stable scatter, the
-//      style of mash_distance.hip) and a re-rank by adjacent compare + scan.  The loop stops as soon as the group
-//      count reaches N, so a text whose longest repeat is R takes ceil(log2(R / k)) + 1 rounds.
+//      is an LSD radix sort over the key's significant bits only (device_prims.h: histogram / exclusive scan /
+//      stable scatter, the style of mash_distance.hip) and a re-rank by adjacent compare + scan.  The loop stops as
+//      soon as the group count reaches N, so a text whose longest repeat is R takes ceil(log2(R / k)) + 1 rounds.
 //   3. L[j] = T[SA[j] - 1] ('$' for SA[j] == 0, the primary row), the C array and an occurrence structure:
 //        nucleotide layout (sigma <= 4): 128-byte lines, 4 x uint32 checkpoint counts + 448 2-bit symbols, so an
 //          LF step reads one line per range end; the primary row holds code 0 and is subtracted where it counts;
@@ -19,7 +19,10 @@
 //          sigma uint32 checkpoint counts per 64 rows.
 // Queries run one pattern per lane (Count: backward search, a lane stops when its range is empty) or one wave
 // per pattern / request (Locate, Extract: coalesced copies).
+#include <cstring>
+
 #include "bwt_index.h"
+#include "device_prims.h"
 
 namespace polyhip {
 namespace {
@@ -286,29 +289,37 @@ __global__ __launch_bounds__(BT) void transform_kernel(const uint8_t *__restrict
         out[j] = L[j];
 }
 
-// workspace of the build, carved in this order
 // general-layout blocks / nucleotide lines cover rows [0, N] (a range end can be N)
 uint64_t gen_blocks(uint64_t N) { return N / GEN_ROWS + 1; }
 uint64_t nuc_lines(uint64_t N) { return N / NUC_SYMS + 1; }
 
-size_t build_workspace(uint64_t n, Carve *c)
+// workspace of the build, carved in this order (base == nullptr: sizes only)
+struct BuildWork {
+    uint64_t *ka, *kb;                          // keys A, B
+    uint32_t *va, *vb, *rank, *shared, *bhist;  // vals A, B; rank; the shared region (below); the byte histogram
+    uint8_t *scratch;                           // of the scans over `shared`
+    size_t bytes;
+};
+
+BuildWork build_carve(uint64_t n, uint8_t *base)
 {
     const uint64_t N = n + 1, nb = radix_blocks(N);
-    Carve local{nullptr};
-    Carve &w = c ? *c : local;
-    w.take<uint64_t>(N); // keys A
-    w.take<uint64_t>(N); // keys B
-    w.take<uint32_t>(N); // vals A
-    w.take<uint32_t>(N); // vals B
-    w.take<uint32_t>(N); // rank
+    Carve c{base};
+    BuildWork w{};
+    w.ka = c.take<uint64_t>(N);
+    w.kb = c.take<uint64_t>(N);
+    w.va = c.take<uint32_t>(N);
+    w.vb = c.take<uint32_t>(N);
+    w.rank = c.take<uint32_t>(N);
     // head flags + their scan, the radix histogram + its scan, and later the occurrence counts + their scan share one
     // region: the largest of the three
     const uint64_t occ_items = std::max<uint64_t>(gen_blocks(N) * 255, nuc_lines(N) * 4);
     const uint64_t shared_items = std::max<uint64_t>(std::max<uint64_t>(N + 1, 256 * nb + 1), occ_items + 1);
-    w.take<uint32_t>(shared_items);
-    w.take<uint32_t>(256); // byte histogram
-    w.take<uint8_t>(scan_scratch_bytes<uint32_t>(shared_items));
-    return w.used;
+    w.shared = c.take<uint32_t>(shared_items);
+    w.bhist = c.take<uint32_t>(256);
+    w.scratch = c.take<uint8_t>(scan_scratch_bytes<uint32_t>(shared_items));
+    w.bytes = c.used;
+    return w;
 }
 
 // The one place that chooses the occurrence layout.  POLYHIP_BWT_GENERAL=1 forces the general layout (testing aid:
@@ -320,17 +331,11 @@ int choose_layout(uint32_t sigma) { return (sigma <= 4 && !env_is("POLYHIP_BWT_G
 int build(BwtHandle *h, const uint8_t *d_seq, uint64_t n, void *d_work, size_t work_bytes, hipStream_t st)
 {
     const uint64_t N = n + 1;
-    PH_REQUIRE(work_bytes >= build_workspace(n, nullptr), "polyhip_bwt_create_dev: workspace of %zu bytes, %zu needed", work_bytes,
-               build_workspace(n, nullptr));
-    Carve w{static_cast<uint8_t *>(d_work)};
-    uint64_t *ka = w.take<uint64_t>(N), *kb = w.take<uint64_t>(N);
-    uint32_t *va = w.take<uint32_t>(N), *vb = w.take<uint32_t>(N), *rank = w.take<uint32_t>(N);
-    const uint64_t nb = radix_blocks(N);
-    const uint64_t occ_items = std::max<uint64_t>(gen_blocks(N) * 255, nuc_lines(N) * 4);
-    const uint64_t shared_items = std::max<uint64_t>(std::max<uint64_t>(N + 1, 256 * nb + 1), occ_items + 1);
-    uint32_t *shared = w.take<uint32_t>(shared_items);
-    uint32_t *bhist = w.take<uint32_t>(256);
-    uint8_t *scratch = w.take<uint8_t>(scan_scratch_bytes<uint32_t>(shared_items));
+    const BuildWork w = build_carve(n, static_cast<uint8_t *>(d_work));
+    PH_REQUIRE(work_bytes >= w.bytes, "polyhip_bwt_create_dev: workspace of %zu bytes, %zu needed", work_bytes, w.bytes);
+    uint64_t *ka = w.ka, *kb = w.kb;
+    uint32_t *va = w.va, *vb = w.vb, *rank = w.rank, *shared = w.shared, *bhist = w.bhist;
+    uint8_t *scratch = w.scratch;
 
     h->n = n;
     PH_HIP(hipMalloc(&h->d_text, N));
@@ -460,7 +465,7 @@ int create_common(const uint8_t *seq, uint64_t n, bool on_device, void *d_work, 
         if (seqbuf.alloc(n) != hipSuccess || hipMemcpyAsync(seqbuf.p, seq, n, hipMemcpyHostToDevice, st) != hipSuccess)
             return fail(set_error(POLYHIP_ERR_HIP, "polyhip_bwt_create: upload of %llu bytes failed", (unsigned long long)n));
         d_seq = seqbuf.as<uint8_t>();
-        work_bytes = build_workspace(n, nullptr);
+        work_bytes = build_carve(n, nullptr).bytes;
         if (work.alloc(work_bytes) != hipSuccess)
             return fail(set_error(POLYHIP_ERR_HIP, "polyhip_bwt_create: workspace of %zu bytes", work_bytes));
         d_work = work.p;
@@ -516,7 +521,7 @@ using namespace polyhip;
 
 extern "C" {
 
-size_t polyhip_bwt_workspace_bytes(uint64_t n) { return build_workspace(n, nullptr); }
+size_t polyhip_bwt_workspace_bytes(uint64_t n) { return build_carve(n, nullptr).bytes; }
 
 int polyhip_bwt_create(const uint8_t *seq, uint64_t n, polyhip_bwt **out)
 {

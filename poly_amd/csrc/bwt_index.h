@@ -1,10 +1,7 @@
-// bwt_index.h -- what the FM-index (bwt.hip) and the read mapper (map_reads.hip) share: the index handle and its occurrence
-// functions, the exclusive scans and the LSD radix sort of (uint64 key, uint32 value).  Kernels and helpers sit in an
-// anonymous namespace: every translation unit that includes this header gets its own copies.
+// bwt_index.h -- the FM-index as its users see it (bwt.hip builds it; bwt_mismatch.hip, map_reads.hip and refs.hip read it):
+// the index handle and the reference-set handle, the index as the query kernels get it, and its occurrence functions, which
+// are inlined into the kernels of the unit that calls them.
 #pragma once
-#include <algorithm>
-#include <cstring>
-
 #include "common.h"
 
 namespace polyhip {
@@ -24,193 +21,9 @@ struct Index {
 
 namespace {
 
-constexpr int BT = 256;           // threads per block everywhere in this file
-constexpr int ITEMS = 16;         // items per thread of a scan / radix tile
-constexpr int TILE = BT * ITEMS;  // 4096
 constexpr int NUC_SYMS = 448;     // 2-bit symbols per 128-byte line (16 bytes of counts + 112 bytes of symbols)
 constexpr int GEN_ROWS = 64;      // rows per checkpoint of the general layout
 constexpr uint8_t NULL_CHAR = '$';
-
-constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// ---- exclusive scan (uint32 or uint64), three phases, recursive over the block sums ------------------------------------
-// out[0..M] = exclusive prefix sums of in[0..M), out[M] = the total; in == out is allowed (out then has M + 1 slots).
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) { return dpp_incl_scan(v); }
-__device__ __forceinline__ uint64_t wave_incl_scan(uint64_t v)
-{
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t u = __shfl_up(v, d, 64);
-        if (lane >= d)
-            v += u;
-    }
-    return v;
-}
-
-// exclusive prefix of `v` over the block, and the block's total
-template <class T> __device__ __forceinline__ T block_excl_scan(T v, T &total)
-{
-    __shared__ T wsum[BT / 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const T inc = wave_incl_scan(v);
-    if (lane == 63)
-        wsum[w] = inc;
-    __syncthreads();
-    T before = 0, all = 0;
-#pragma unroll
-    for (int q = 0; q < BT / 64; ++q) {
-        before += q < w ? wsum[q] : T(0);
-        all += wsum[q];
-    }
-    __syncthreads();
-    total = all;
-    return before + inc - v;
-}
-
-template <class T> __global__ __launch_bounds__(BT) void scan_reduce_kernel(const T *__restrict__ in, uint64_t m, T *__restrict__ sums)
-{
-    const uint64_t base = (uint64_t)blockIdx.x * TILE + (uint64_t)threadIdx.x * ITEMS;
-    T s = 0;
-#pragma unroll
-    for (int q = 0; q < ITEMS; ++q)
-        if (base + q < m)
-            s += in[base + q];
-    T total;
-    (void)block_excl_scan<T>(s, total);
-    if (threadIdx.x == 0)
-        sums[blockIdx.x] = total;
-}
-
-// offs == nullptr: a single block, offset 0
-template <class T>
-__global__ __launch_bounds__(BT) void scan_apply_kernel(const T *in, T *out, uint64_t m, const T *__restrict__ offs)
-{
-    const uint64_t base = (uint64_t)blockIdx.x * TILE + (uint64_t)threadIdx.x * ITEMS;
-    T v[ITEMS];
-    T s = 0;
-#pragma unroll
-    for (int q = 0; q < ITEMS; ++q) {
-        v[q] = base + q < m ? in[base + q] : T(0);
-        s += v[q];
-    }
-    T total;
-    T run = block_excl_scan<T>(s, total) + (offs ? offs[blockIdx.x] : T(0));
-#pragma unroll
-    for (int q = 0; q < ITEMS; ++q)
-        if (base + q < m) {
-            out[base + q] = run;
-            run += v[q];
-        }
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == BT - 1)
-        out[m] = run;
-}
-
-template <class T> size_t scan_scratch_bytes(uint64_t m)
-{
-    if (m <= (uint64_t)TILE)
-        return 0;
-    const uint64_t nb = (m + TILE - 1) / TILE;
-    return align256((nb + 1) * sizeof(T)) + scan_scratch_bytes<T>(nb);
-}
-
-template <class T> hipError_t scan_excl(const T *in, T *out, uint64_t m, uint8_t *scratch, hipStream_t st)
-{
-    if (m == 0)
-        return hipMemsetAsync(out, 0, sizeof(T), st);
-    const uint64_t nb = (m + TILE - 1) / TILE;
-    if (nb == 1) {
-        hipLaunchKernelGGL(scan_apply_kernel<T>, dim3(1), dim3(BT), 0, st, in, out, m, (const T *)nullptr);
-        return hipGetLastError();
-    }
-    T *sums = reinterpret_cast<T *>(scratch);
-    hipLaunchKernelGGL(scan_reduce_kernel<T>, dim3((unsigned)nb), dim3(BT), 0, st, in, m, sums);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess)
-        e = scan_excl<T>(sums, sums, nb, scratch + align256((nb + 1) * sizeof(T)), st);
-    if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL(scan_apply_kernel<T>, dim3((unsigned)nb), dim3(BT), 0, st, in, out, m, (const T *)sums);
-    return hipGetLastError();
-}
-
-// ---- LSD radix sort of (uint64 key, uint32 value), 8 bits per pass, stable ---------------------------------------------
-// Lanes of one wave holding the same digit: eight ballots (no LDS atomics on a skewed digit, e.g. a one-symbol text).
-__device__ __forceinline__ uint64_t same_digit_lanes(uint32_t d, bool valid)
-{
-    uint64_t m = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-        const bool bit = (d >> b) & 1u;
-        const uint64_t v = __ballot(bit);
-        m &= bit ? v : ~v;
-    }
-    return m;
-}
-
-// hist[d * nblocks + block] = items of the block's tile with digit d
-__global__ __launch_bounds__(BT) void radix_hist_kernel(const uint64_t *__restrict__ keys, uint64_t n, int shift,
-                                                        uint32_t *__restrict__ hist, uint32_t nblocks)
-{
-    __shared__ uint32_t cnt[256];
-    cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const uint64_t tile0 = (uint64_t)blockIdx.x * TILE;
-    for (int it = 0; it < ITEMS; ++it) {
-        const uint64_t i = tile0 + (uint64_t)it * BT + threadIdx.x;
-        const bool valid = i < n;
-        const uint32_t d = valid ? (uint32_t)(keys[i] >> shift) & 255u : 0u;
-        const uint64_t m = same_digit_lanes(d, valid);
-        if (valid && (m & ((1ull << lane) - 1)) == 0)
-            atomicAdd(&cnt[d], (uint32_t)__popcll(m));
-    }
-    __syncthreads();
-    hist[(uint64_t)threadIdx.x * nblocks + blockIdx.x] = cnt[threadIdx.x];
-}
-
-// base = the exclusive scan of hist: every item goes to base[digit][block] + (items of that digit before it in the tile)
-__global__ __launch_bounds__(BT) void radix_scatter_kernel(const uint64_t *__restrict__ kin, const uint32_t *__restrict__ vin,
-                                                           uint64_t *__restrict__ kout, uint32_t *__restrict__ vout, uint64_t n,
-                                                           int shift, const uint32_t *__restrict__ base, uint32_t nblocks)
-{
-    __shared__ uint32_t run[256];
-    __shared__ uint32_t wcnt[BT / 64][256];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    run[threadIdx.x] = base[(uint64_t)threadIdx.x * nblocks + blockIdx.x];
-#pragma unroll
-    for (int q = 0; q < BT / 64; ++q)
-        wcnt[q][threadIdx.x] = 0;
-    __syncthreads();
-    const uint64_t tile0 = (uint64_t)blockIdx.x * TILE;
-    for (int it = 0; it < ITEMS; ++it) {
-        const uint64_t i = tile0 + (uint64_t)it * BT + threadIdx.x;
-        const bool valid = i < n;
-        const uint64_t k = valid ? kin[i] : 0;
-        const uint32_t d = (uint32_t)(k >> shift) & 255u;
-        const uint64_t m = same_digit_lanes(d, valid);
-        const uint64_t below = m & ((1ull << lane) - 1);
-        if (valid && below == 0)
-            wcnt[w][d] = (uint32_t)__popcll(m);
-        __syncthreads();
-        if (valid) {
-            uint32_t pos = run[d] + (uint32_t)__popcll(below);
-            for (int q = 0; q < w; ++q)
-                pos += wcnt[q][d];
-            kout[pos] = k;
-            vout[pos] = vin[i];
-        }
-        __syncthreads();
-        uint32_t add = 0;
-#pragma unroll
-        for (int q = 0; q < BT / 64; ++q) {
-            add += wcnt[q][threadIdx.x];
-            wcnt[q][threadIdx.x] = 0;
-        }
-        run[threadIdx.x] += add;
-        __syncthreads();
-    }
-}
 
 // ---- occurrences: rows [0, i) of L that hold a symbol --------------------------------------------------------------------
 __device__ __forceinline__ uint32_t occ_nuc(const Index &x, uint32_t c, uint32_t i)
@@ -306,38 +119,6 @@ __device__ __forceinline__ uint32_t occ_gen(const Index &x, uint32_t c, uint8_t 
     return r;
 }
 
-unsigned grid_for(uint64_t items, uint64_t per_block = BT)
-{
-    uint64_t g = (items + per_block - 1) / per_block;
-    if (g < 1)
-        g = 1;
-    if (g > 256 * 64)
-        g = 256 * 64;
-    return (unsigned)g;
-}
-
-int bits_for(uint64_t v) // bits needed to hold 0..v
-{
-    int b = 1;
-    while (b < 64 && (v >> b))
-        ++b;
-    return b;
-}
-
-// a workspace carved in order
-struct Carve {
-    uint8_t *p;
-    size_t used = 0;
-    template <class T> T *take(uint64_t count)
-    {
-        T *r = reinterpret_cast<T *>(p ? p + used : nullptr);
-        used += align256(count * sizeof(T));
-        return r;
-    }
-};
-
-uint64_t radix_blocks(uint64_t N) { return (N + TILE - 1) / TILE; }
-
 } // namespace
 
 // ---- the handle --------------------------------------------------------------------------------------------------------
@@ -373,46 +154,7 @@ struct RefsHandle {
     uint64_t *starts = nullptr;  // the same on the host, as polyhip_refs_starts returns them
 };
 
-namespace {
+inline const BwtHandle *as_h(const polyhip_bwt *h) { return reinterpret_cast<const BwtHandle *>(h); }
+inline const RefsHandle *as_refs(const polyhip_refs *h) { return reinterpret_cast<const RefsHandle *>(h); }
 
-const RefsHandle *as_refs(const polyhip_refs *h) { return reinterpret_cast<const RefsHandle *>(h); }
-
-// the calling thread runs a bwt call on the handle's device and gets its own device back afterwards
-struct DeviceScope {
-    int prev = -1;
-    hipError_t enter(int dev)
-    {
-        hipError_t e = hipGetDevice(&prev);
-        if (e == hipSuccess && prev != dev)
-            e = hipSetDevice(dev);
-        else
-            prev = -1;
-        return e;
-    }
-    ~DeviceScope()
-    {
-        if (prev >= 0)
-            (void)hipSetDevice(prev);
-    }
-};
-
-int radix_sort(uint64_t *&ka, uint32_t *&va, uint64_t *&kb, uint32_t *&vb, uint64_t N, int bits, uint32_t *hist, uint8_t *scratch,
-               hipStream_t st)
-{
-    const uint64_t nb = radix_blocks(N);
-    for (int shift = 0; shift < bits; shift += 8) {
-        hipLaunchKernelGGL(radix_hist_kernel, dim3((unsigned)nb), dim3(BT), 0, st, ka, N, shift, hist, (uint32_t)nb);
-        PH_HIP(hipGetLastError());
-        PH_HIP(scan_excl<uint32_t>(hist, hist, 256 * nb, scratch, st));
-        hipLaunchKernelGGL(radix_scatter_kernel, dim3((unsigned)nb), dim3(BT), 0, st, ka, va, kb, vb, N, shift, hist, (uint32_t)nb);
-        PH_HIP(hipGetLastError());
-        std::swap(ka, kb);
-        std::swap(va, vb);
-    }
-    return POLYHIP_OK;
-}
-
-const BwtHandle *as_h(const polyhip_bwt *h) { return reinterpret_cast<const BwtHandle *>(h); }
-
-} // namespace
 } // namespace polyhip

@@ -19,8 +19,9 @@
 //     computes one child (two occ_gen).
 // Locate: the count pass gives the per-pattern totals and their scan `first`; a second search writes (pattern << B | SA[r],
 // d) for every row of every leaf into the pattern's segment (a leaf of WIDE rows or more is written by the whole wave),
-// and the LSD radix sort of bwt_index.h orders them by (pattern, position) over the significant bits.
+// and the LSD radix sort of device_prims.h orders them by (pattern, position) over the significant bits.
 #include "bwt_index.h"
+#include "device_prims.h"
 
 namespace polyhip {
 namespace {

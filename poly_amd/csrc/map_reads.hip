@@ -11,7 +11,7 @@
 //                       the complement table, last byte first), interval start + width
 //   scan_excl           hit offsets; the total comes back to the host (grid of the sort)
 //   map_expand_kernel   64-bit keys (read * 2 + strand) << dbits | (d + max_len), one lane per seed
-//   radix_sort          bwt's LSD radix sort over the key's significant bits
+//   radix_sort          the LSD radix sort of device_prims.h over the key's significant bits (scan_excl comes from there too)
 //   map_cluster_kernel  one wave per read: greedy clusters by ballots over 64 sorted hits at a time, the kept candidates
 //                       held rank per lane (insertion by one ballot), windows out
 //   scan_excl           candidate -> pair offsets; the pair count comes back to the host
@@ -44,6 +44,7 @@
 //   map_reduce_kernel<true, true> / pair_resolve_kernel<true>   rid out, ref_end made local (ref_start follows from it)
 //   pair_reduce_kernel<true>   proper only within one contig; the rescue window clipped to the anchor's contig
 #include "bwt_index.h"
+#include "device_prims.h"
 #include "sw_affine.h"
 #include "sw_scoring.h"
 

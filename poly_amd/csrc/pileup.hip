@@ -13,7 +13,7 @@
 // below the lane; the anchor of a run that starts at the lane is that position minus one, whichever step the column before
 // it sat in, so the only other carry is the class of the step's last column.  counts is channel-major: the lanes of a run
 // of matching columns add to consecutive words of one plane.  Sums of integers do not depend on the order of the adds.
-#include "bwt_index.h"
+#include "device_prims.h"
 #include "host_pipeline.h"
 
 namespace polyhip {
@@ -23,8 +23,6 @@ constexpr int PU_WAVES = BT / 64;       // entries a block walks at a time
 constexpr unsigned PU_MAX_BLOCKS = 4096; // the walk is a grid-stride loop: a wave adds to the info counters once
 enum : int { INFO_USED = 0, INFO_SKIPPED, INFO_BAD, INFO_COLUMNS, INFO_EDGE, INFO_WORDS };
 enum : uint32_t { CH_OTHER = 4, CH_DEL = 5, CH_INS_EVENT = 6, CH_DEL_EVENT = 7, CH_STRAND = 8 };
-
-__device__ __forceinline__ uint64_t lanes_below(int lane) { return (1ull << lane) - 1ull; }
 
 // A/a, C/c, G/g, T/t -> 0..3, every other byte 4 (c | 0x20 is 'a' for 'A' and 'a' only, and so on)
 __device__ __forceinline__ uint32_t base_class(uint32_t c)
@@ -180,25 +178,6 @@ __global__ __launch_bounds__(BT) void call_kernel(uint64_t lo, uint64_t L, uint3
 
 thread_local polyhip_pileup_info t_info{};
 
-unsigned grid_of(uint64_t items, uint64_t per_block, unsigned most)
-{
-    const uint64_t nb = (items + per_block - 1) / per_block;
-    return (unsigned)std::min<uint64_t>(std::max<uint64_t>(nb, 1), most);
-}
-
-// one device allocation, carved in 256-byte steps
-struct Arena {
-    DevBuf buf;
-    size_t used = 0;
-    size_t reserve(size_t bytes)
-    {
-        const size_t at = used;
-        used += align256(bytes ? bytes : 1);
-        return at;
-    }
-    template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(buf.as<uint8_t>() + off); }
-};
-
 } // namespace
 } // namespace polyhip
 
@@ -259,7 +238,7 @@ int polyhip_pileup(const polyhip_pileup_params *params, uint64_t n, const uint32
         PH_HIP(hipMemsetAsync(w.at<uint8_t>(o_counts), 0, POLYHIP_PILEUP_CHANNELS * L * 4, st));
 
     if (n) {
-        const unsigned wgrid = grid_of(n, PU_WAVES, PU_MAX_BLOCKS);
+        const unsigned wgrid = grid_for(n, PU_WAVES, PU_MAX_BLOCKS);
         hipLaunchKernelGGL(walk_kernel<false>, dim3(wgrid), dim3(BT), 0, st, n, params->min_mapq, lo, L, ref_len, w.at<uint32_t>(o_flags),
                            w.at<uint8_t>(o_mapq), w.at<uint32_t>(o_rs), w.at<uint32_t>(o_re), w.at<uint8_t>(o_a), w.at<uint8_t>(o_b),
                            w.at<uint64_t>(o_off), w.at<uint8_t>(o_ref), w.at<uint32_t>(o_err), w.at<uint32_t>(o_counts),
@@ -273,7 +252,7 @@ int polyhip_pileup(const polyhip_pileup_params *params, uint64_t n, const uint32
         PH_HIP(hipGetLastError());
     }
     const uint32_t min_depth = std::max(params->min_depth, 1u), min_count = std::max(params->min_alt_count, 1u);
-    const unsigned cgrid = grid_of(L, BT, 1u << 20);
+    const unsigned cgrid = grid_for(L, BT, 1u << 20);
     if (L) {
         hipLaunchKernelGGL(call_kernel<false>, dim3(cgrid), dim3(BT), 0, st, lo, L, min_depth, min_count, params->min_alt_permille,
                            w.at<uint32_t>(o_counts), w.at<uint8_t>(o_ref), w.at<uint8_t>(o_cons), w.at<uint64_t>(o_nsite),

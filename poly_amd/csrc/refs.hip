@@ -4,9 +4,11 @@
 // off[c] - off[0].  The index is polyhip_bwt_create's, on the device current at creation; the set owns it and lends it out
 // (polyhip_refs_index).  start[] lives on that device for the mapper's refs kernels (map_reads.hip) and for
 //   resolve_kernel   one lane per entry: binary search of a position of C over start[], the contig and the local position
+#include <cstring>
 #include <vector>
 
 #include "bwt_index.h"
+#include "device_prims.h"
 
 namespace polyhip {
 namespace {

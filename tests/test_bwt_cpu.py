@@ -108,6 +108,18 @@ def test_library_exports_bwt_symbols():
         assert hasattr(L, n), n
 
 
+# polyhip_bwt_workspace_bytes(n) as the library of commit c417f13 (the last one with two copies of the build's carve order)
+# returned it; the function is host arithmetic and the library loads without a device
+WORKSPACE_BYTES = {1: 3584, 2: 3584, 447: 21760, 448: 23040, 4095: 182272, 4096: 183552, 4097: 183552, 65537: 2883328,
+                   1000003: 43944960, 5000000: 219710976, 2**32 - 2: 188726842880}
+
+
+@pytest.mark.parametrize("n", sorted(WORKSPACE_BYTES))
+def test_build_workspace_bytes_are_unchanged(n):
+    from poly_amd import _lib
+    assert _lib.lib().polyhip_bwt_workspace_bytes(n) == WORKSPACE_BYTES[n]
+
+
 def test_create_refuses_without_touching_a_device():
     """Empty text: the reference's error text, from the library itself (no device needed to refuse it)."""
     from poly_amd import _lib

@@ -102,7 +102,7 @@ def _check_index(seq: bytes, layout, max_rounds=None):
     return idx
 
 
-@pytest.mark.parametrize("n", [1, 2, 3, 31, 447, 448, 449, 895, 896, 4096, 4097, 65_537, 1_000_003, 5_000_000])
+@pytest.mark.parametrize("n", [1, 2, 3, 31, 447, 448, 449, 895, 896, 4095, 4096, 4097, 65_537, 1_000_003, 5_000_000])
 def test_suffix_array_random_dna(layout, n):
     _check_index(_dna(np.random.default_rng(n), n), layout)
 
@@ -230,6 +230,21 @@ def test_locate_capacity(layout):
     assert st == _lib.ERR_INVALID and list(first) == [0, 3, 5] and not out.any()
     first, got = idx.LocateBatch(["a", "na"], capacity=5)
     assert list(first) == [0, 3, 5] and list(got) == [5, 3, 1, 4, 2]
+
+
+@pytest.mark.parametrize("npat", [4096, 4097])
+def test_locate_at_the_scan_tile_edge(layout, npat):
+    """The offsets of a Locate batch are a uint64 scan over the patterns: 4096 of them are the most its single block takes,
+    4097 the fewest that go through block sums."""
+    rng = np.random.default_rng(npat)
+    seq = _dna(rng, 200)
+    idx = _new(seq, layout)
+    o = bo.Oracle(seq, width=4)
+    pats = [_dna(rng, int(m)) for m in rng.integers(1, 5, npat)]      # 1-mers with ~50 rows down to 4-mers, some absent
+    want = [np.array(o.locate(p), np.int64) for p in pats]
+    first, got = idx.LocateBatch(pats)
+    assert (first == np.concatenate([[0], np.cumsum([len(w) for w in want])])).all()
+    assert (got == np.concatenate(want)).all()
 
 
 # ---------------------------------------------------------------- device-resident entry points
