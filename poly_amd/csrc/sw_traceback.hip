@@ -284,6 +284,81 @@ __global__ __launch_bounds__(256) void tb_profile_kernel(const uint8_t *__restri
         col[c * 4] = c < live ? lutc[c * 256 + b] : (int8_t)-128;
 }
 
+// What a lane of tb_prof_kernel and of the three half-float kernels knows of its pair before it sweeps.
+// The score pass may have left the end cell to the traceback (k3p::SW_END_DEFERRED): eB is then the last column of
+// the ONE block of four columns that holds the maximum, and the first cell worth M in row-major order is found
+// while that block -- the last of the window -- is swept.  The window is sized with lenA for the unknown end row.
+// TB_DEFERRED: the caller is the fused entry point, whose score pass may have deferred end cells; without it the
+// end arrays are the caller's read-only input, a sentinel (or any row beyond the read) there means "no alignment"
+struct TbPair {
+    uint32_t lenA, eA, eB; // the read's length; the end cell (1-based, 0 = none; tb_pair_end fills in a deferred one)
+    int64_t M;             // the score pass's maximum
+    const uint8_t *ap;     // the read, A + oA
+    uint64_t oA;
+    bool locate;           // the end cell is deferred: search it in the window's last block
+    uint32_t rowsA;        // rows the window is sized for
+    bool work;             // there is something to sweep and walk
+    uint32_t jb0, nblk;    // the window: its first column (0-based, on a block boundary) and its blocks of TBU columns
+};
+// RA = the rows the kernel holds per pair; OWN_B: the pair has a B of its own, lenB long (tb_pair16_kernel)
+template <int RA, bool OWN_B = false>
+__device__ __forceinline__ TbPair tb_pair_load(uint64_t pair, uint64_t pair1, const uint8_t *A, const uint64_t *offA,
+                                               const uint32_t *err, const uint32_t *endA, const uint32_t *endB,
+                                               const int64_t *score, uint32_t wcols, int wide, int smax, int gap,
+                                               uint32_t lenB = 0)
+{
+    TbPair p = {0u, 0u, 0u, 0, A, 0u, false, 0u, false, 0u, 0u};
+    const bool active = pair < pair1;
+    if (active) {
+        p.oA = offA[pair];
+        p.lenA = (uint32_t)(offA[pair + 1] - p.oA);
+        p.ap = A + p.oA;
+        if (err[pair] == 0u) {
+            p.eA = endA[pair];
+            p.eB = endB[pair];
+            p.M = score[pair];
+        }
+    }
+    p.locate = active && (wide & TB_DEFERRED) && p.eA == k3p::SW_END_DEFERRED;
+    p.rowsA = p.locate ? p.lenA : p.eA;
+    p.work = active && p.rowsA > 0 && p.rowsA <= p.lenA && p.eB > 0 && (!OWN_B || p.eB <= lenB) && p.M > 0 && p.lenA <= RA;
+    const uint32_t mycols =
+        p.work ? min(wcols + 4u, pair_window(wcols, p.rowsA, p.M, smax, gap, wide & TB_WIDE) + (p.locate ? 4u : 0u)) : 0u;
+    const uint32_t c_s = (p.work && p.eB > mycols) ? p.eB - mycols + 1u : 1u; // first column (1-based) of my window
+    p.jb0 = (c_s - 1u) & ~3u;
+    p.nblk = p.work ? (p.eB - p.jb0 + TBU - 1) / TBU : 0u; // <= nblk_alloc, less one per band that lags behind
+    return p;
+}
+// After the sweep: a deferred end cell (key = (row << 2) | column of the last block, from the search) becomes the pair's
+// end cell, in p and in the caller's arrays.  Returns whether there is an alignment to walk.
+__device__ __forceinline__ bool tb_pair_end(TbPair &p, uint64_t pair, uint32_t key, uint32_t *endA,
+                                            uint32_t *endB, uint32_t *err)
+{
+    bool lost = false;
+    if (p.work && p.locate) {
+        lost = key == 0xFFFFFFFFu; // cannot happen: the packed pass saw M in this block
+        p.eA = lost ? 0u : (key >> 2) + 1u;
+        p.eB = lost ? 0u : p.eB - 3u + (key & 3u);
+        endA[pair] = p.eA;
+        endB[pair] = p.eB;
+        if (lost)
+            err[pair] = 0xFFFFFFFEu;
+    } else if (p.locate) { // deferred, but nothing to walk (cannot happen either: M > 0 and lenA > 0)
+        endA[pair] = 0u;
+        endB[pair] = 0u;
+    }
+    return p.work && !lost;
+}
+// Lanes sweep different numbers of blocks.  They are aligned at the END: a lane with fewer blocks idles first, so
+// that the wave's last iteration is every lane's last block and the locate code is paid once per wave.
+__device__ __forceinline__ uint32_t tb_wave_max(uint32_t nmax)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1)
+        nmax = max(nmax, (uint32_t)__shfl_xor((int)nmax, d, 64));
+    return nmax;
+}
+
 // w = 2 * w + (x > y).  FIND (the wave's last block only): the first cell worth M in row-major order -- rows are
 // visited in ascending order and a row's four columns left to right, so the first hit is it
 #define PH_TB_CELL(S, DIAG, UP, LEFT, HOUT, C)         \
@@ -354,31 +429,9 @@ __global__ __launch_bounds__(THREADS) void tb_prof_kernel(
 
     const uint64_t pair = pair0 + (uint64_t)blockIdx.x * THREADS + tid;
     const bool active = pair < pair1;
-    uint32_t lenA = 0, eA = 0, eB = 0;
-    int64_t M = 0;
-    const uint8_t *ap = A;
-    if (active) {
-        const uint64_t o0 = offA[pair];
-        lenA = (uint32_t)(offA[pair + 1] - o0);
-        ap = A + o0;
-        if (err[pair] == 0u) {
-            eA = endA[pair];
-            eB = endB[pair];
-            M = score[pair];
-        }
-    }
-    // The score pass may have left the end cell to this kernel (k3p::SW_END_DEFERRED): eB is then the last column of
-    // the ONE block of four columns that holds the maximum, and the first cell worth M in row-major order is found
-    // while that block -- the last of the window -- is swept.  The window is sized with lenA for the unknown end row.
-    // TB_DEFERRED: the caller is the fused entry point, whose score pass may have deferred end cells; without it the
-    // end arrays are the caller's read-only input, a sentinel (or any row beyond the read) there means "no alignment"
-    const bool locate = active && (wide & TB_DEFERRED) && eA == k3p::SW_END_DEFERRED;
-    const uint32_t rowsA = locate ? lenA : eA;
-    const bool work = active && rowsA > 0 && rowsA <= lenA && eB > 0 && M > 0 && lenA <= RA;
-    const uint32_t mycols = work ? min(wcols + 4u, pair_window(wcols, rowsA, M, smax, gap, wide & TB_WIDE) + (locate ? 4u : 0u)) : 0u;
-    const uint32_t c_s = (work && eB > mycols) ? eB - mycols + 1u : 1u; // first column (1-based) of my window
-    const uint32_t jb0 = (c_s - 1u) & ~3u;                               // 0-based, on a block boundary
-    const uint32_t nblk = work ? (eB - jb0 + TBU - 1) / TBU : 0u;        // <= nblk_alloc
+    TbPair p = tb_pair_load<RA>(pair, pair1, A, offA, err, endA, endB, score, wcols, wide, smax, gap);
+    const uint32_t lenA = p.lenA, jb0 = p.jb0, nblk = p.nblk;
+    const uint8_t *ap = p.ap;
 
     // packed byte offsets (code * 4) of my rows inside a profile block; rows >= lenA use the pad code
     uint32_t apk[RA / 4];
@@ -389,7 +442,7 @@ __global__ __launch_bounds__(THREADS) void tb_prof_kernel(
         for (int b = 0; b < 4; ++b) {
             const int i = 4 * w + b;
             uint32_t code = (uint32_t)ncodes;
-            if (work && (uint32_t)i < lenA) {
+            if (p.work && (uint32_t)i < lenA) {
                 const uint32_t c = codeL[ap[i]];
                 code = c == 0xFFu ? (uint32_t)ncodes : c;
             }
@@ -407,14 +460,8 @@ __global__ __launch_bounds__(THREADS) void tb_prof_kernel(
     uint32_t *dirw = dirbuf + wave_global * ((size_t)nblk_alloc * TBU * NG * 2 * 64) + lane;
     const uint32_t lds_base = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(P));
 
-    // Lanes sweep different numbers of blocks.  They are aligned at the END: a lane with fewer blocks idles first, so
-    // that the wave's last iteration is every lane's last block and the locate code is paid once per wave.
-    uint32_t nmax = nblk;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-        nmax = max(nmax, (uint32_t)__shfl_xor((int)nmax, d, 64));
-    const uint32_t lag = nmax - nblk;
-    const int Mi = (int)M;
+    const uint32_t nmax = tb_wave_max(nblk), lag = nmax - nblk; // lanes are aligned at the end
+    const int Mi = (int)p.M;
     uint32_t key = 0xFFFFFFFFu;
     // tt = the wave's iteration (uniform: the direction words of one iteration are stored side by side, 256 B per
     // store), bt = tt - lag = the lane's own block
@@ -444,7 +491,7 @@ __global__ __launch_bounds__(THREADS) void tb_prof_kernel(
             wa3 = wb3;
         }
     };
-    const bool any_locate = __any(locate) != 0; // wave-uniform
+    const bool any_locate = __any(p.locate) != 0; // wave-uniform
     const uint32_t nplain = any_locate && nmax > 0 ? nmax - 1u : nmax;
     for (uint32_t t = 0; t < nplain; ++t)
         if (t >= lag) // (nblk == 0: lag == nmax, never)
@@ -455,24 +502,11 @@ __global__ __launch_bounds__(THREADS) void tb_prof_kernel(
     if (!active)
         return;
     uint32_t len = 0;
-    bool lost = false;
-    if (work && locate) {
-        lost = key == 0xFFFFFFFFu; // cannot happen: the packed pass saw M in this block
-        eA = lost ? 0u : (key >> 2) + 1u;
-        eB = lost ? 0u : eB - 3u + (key & 3u);
-        endA[pair] = eA;
-        endB[pair] = eB;
-        if (lost)
-            err[pair] = 0xFFFFFFFEu;
-    } else if (locate) { // deferred, but nothing to walk (cannot happen either: M > 0 and lenA > 0)
-        endA[pair] = 0u;
-        endB[pair] = 0u;
-    }
-    if (work && !lost) {
+    if (tb_pair_end(p, pair, key, endA, endB, err)) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); // my own stores, read back by me
         uint8_t *outA = alnA + pair * stride, *outB = alnB + pair * stride;
-        uint32_t i = eA, j = eB;
-        int h = (int)M;
+        uint32_t i = p.eA, j = p.eB;
+        int h = Mi;
         while (h > 0 && i > 0 && j > jb0 && len < stride) {
             const uint32_t jj = j - 1u, rel = jj - jb0 + TBU * lag, r = i - 1u, g = r >> 5; // (stored by wave iteration)
             const uint32_t rows = min(32u, (uint32_t)RA - 32u * g);
@@ -505,7 +539,7 @@ __global__ __launch_bounds__(THREADS) void tb_prof_kernel(
             ++len;
         }
     }
-    alnLen[pair] = (active && rowsA > 0 && lenA > RA) ? 0xFFFFFFFFu : len;
+    alnLen[pair] = (active && p.rowsA > 0 && lenA > RA) ? 0xFFFFFFFFu : len;
 }
 #undef PH_TB_ROW
 #undef PH_TB_CELL
@@ -636,47 +670,52 @@ __global__ __launch_bounds__(256) void tb_profile16_kernel(const uint8_t *__rest
             o_[1] = make_uint4(wG[2], wL[2], wG[3], wL[3]);                 \
         }                                                                   \
     } while (0)
-// Two row pairs at a time with their cells interleaved along the anti-diagonal (row r's cell c + 1 and row r + 1's cell c
-// depend on nothing of each other): twice the independent work between two dependent packed instructions.  Only where no
-// end cell is searched (FIND == 0: the search needs row-major order).  -DPH_TBF_WF: a measured variant (scripts/build_variant.sh).
-#define PH_TBF_ROW2(R, XA0, XA1, YA0, YA1, XB0, XB1, YB0, YB1)                 \
-    do {                                                                       \
-        const uint32_t wa0 = __builtin_amdgcn_perm((YA0), (XA0), 0x05040100u); \
-        const uint32_t wa1 = __builtin_amdgcn_perm((YA0), (XA0), 0x07060302u); \
-        const uint32_t wa2 = __builtin_amdgcn_perm((YA1), (XA1), 0x05040100u); \
-        const uint32_t wa3 = __builtin_amdgcn_perm((YA1), (XA1), 0x07060302u); \
-        const uint32_t wb0 = __builtin_amdgcn_perm((YB0), (XB0), 0x05040100u); \
-        const uint32_t wb1 = __builtin_amdgcn_perm((YB0), (XB0), 0x07060302u); \
-        const uint32_t wb2 = __builtin_amdgcn_perm((YB1), (XB1), 0x05040100u); \
-        const uint32_t wb3 = __builtin_amdgcn_perm((YB1), (XB1), 0x07060302u); \
-        const uint32_t lefta = H[(R)], leftb = H[(R) + 1];                     \
-        const uint32_t gla = tbf_addc(lefta, gap2), glb = tbf_addc(leftb, gap2); \
-        uint32_t ha0, ha1, ha2, ha3, ga0, ga1, ga2, ga3, hb0, hb1, hb2, hb3, gb0, gb1, gb2, gb3; \
-        { const int r_ = (R);     PH_TBF_CELL(wa0, pdiag, pg0, gla, ha0, ga0, 0); } \
-        { const int r_ = (R);     PH_TBF_CELL(wa1, pr0, pg1, ga0, ha1, ga1, 1); }   \
-        { const int r_ = (R) + 1; PH_TBF_CELL(wb0, lefta, ga0, glb, hb0, gb0, 0); } \
-        { const int r_ = (R);     PH_TBF_CELL(wa2, pr1, pg2, ga1, ha2, ga2, 2); }   \
-        { const int r_ = (R) + 1; PH_TBF_CELL(wb1, ha0, ga1, gb0, hb1, gb1, 1); }   \
-        { const int r_ = (R);     PH_TBF_CELL(wa3, pr2, pg3, ga2, ha3, ga3, 3); }   \
-        { const int r_ = (R) + 1; PH_TBF_CELL(wb2, ha1, ga2, gb1, hb2, gb2, 2); }   \
-        { const int r_ = (R) + 1; PH_TBF_CELL(wb3, ha2, ga3, gb2, hb3, gb3, 3); }   \
-        pdiag = leftb;                                                         \
-        pr0 = hb0;                                                             \
-        pr1 = hb1;                                                             \
-        pr2 = hb2;                                                             \
-        pr3 = hb3;                                                             \
-        pg0 = gb0;                                                             \
-        pg1 = gb1;                                                             \
-        pg2 = gb2;                                                             \
-        pg3 = gb3;                                                             \
-        H[(R)] = ha3;                                                          \
-        H[(R) + 1] = hb3;                                                      \
-        if ((((R) + 1) & 15) == 15 || (R) + 1 == RB - 1) {                     \
-            uint4 *o_ = reinterpret_cast<uint4 *>(dirw + ((size_t)tt * NG + (((R) + 1) >> 4)) * (64 * 8)); \
-            o_[0] = make_uint4(wG[0], wL[0], wG[1], wL[1]);                    \
-            o_[1] = make_uint4(wG[2], wL[2], wG[3], wL[3]);                    \
-        }                                                                      \
-    } while (0)
+// (Two row pairs at a time, cells interleaved along the anti-diagonal, was measured and dropped: HISTORY.md "Round 4" (iv), profiles/r04_tb_wavefront_variant.log.)
+// What every half-float kernel declares before its sweep, under the names the row macros use: the H column, the lane's
+// piece of its wave's direction words, the end-aligned lanes (nmax, lag: tb_wave_max; a lane runs one iteration more per
+// band that lags behind), the packed constants, the search key, and the row that a lane's second band finds above its
+// first row: its first band's last row of the block before, already in the high halves
+#define PH_TBF_SETUP(NBLK)                                                                                          \
+    uint32_t H[RB];                                                                                                 \
+    _Pragma("unroll") for (int i = 0; i < RB; ++i) H[i] = 0;                                                        \
+    static_assert(TBU == 4, "a lane's piece of direction words is (G, L) x four columns");                          \
+    uint32_t *dirw = dirbuf + ((((uint64_t)blockIdx.x * THREADS + tid) >> 6) * ((size_t)nblk_alloc * TBU * NG * 2 * 64)) + lane * 8; \
+    const uint32_t nmax = tb_wave_max(NBLK), lag = nmax - (NBLK);                                                   \
+    const uint32_t gh = tbf_half_bits(gap); /* gap < 0 */                                                           \
+    const uint32_t gap2 = gh | (gh << 16), one2 = 0x00010001u, two2 = 0x00020002u;                                  \
+    uint32_t key = 0xFFFFFFFFu;                                                                                     \
+    uint32_t hh0 = 0, hh1 = 0, hh2 = 0, hh3 = 0, hg0 = 0, hg1 = 0, hg2 = 0, hg3 = 0, hd = 0
+// The rows of one sweep iteration: RB row pairs against the profile entries at base0 (first band) and base1 (second band),
+// the next group of four in flight while one is computed.  Leaves the first band's last row in pr0..3 / pg0..3 for the
+// kernel to hand over.  Expanded inside each kernel's sweep lambda, which must keep ONE call site per instantiation (see
+// tb_prof16x2_kernel).
+#define PH_TBF_ROW_GROUPS()                                                                                         \
+    uint32_t pr0 = hh0, pr1 = hh1, pr2 = hh2, pr3 = hh3, pg0 = hg0, pg1 = hg1, pg2 = hg2, pg3 = hg3, pdiag = hd;    \
+    uint32_t wG[TBU] = {0u, 0u, 0u, 0u}, wL[TBU] = {0u, 0u, 0u, 0u};                                                \
+    tbf_u32x2 xa[4], ya[4], xb[4], yb[4];                                                                           \
+    PH_TBF_ISSUE(apk0[0], apk1[0], xa, ya);                                                                         \
+    _Pragma("unroll") for (int g = 0; g < RB / 4; ++g)                                                              \
+    {                                                                                                               \
+        if (g + 1 < RB / 4) {                                                                                       \
+            PH_TBF_ISSUE(apk0[g + 1], apk1[g + 1], xb, yb);                                                         \
+            asm volatile("s_waitcnt lgkmcnt(8)"                                                                     \
+                         : "+v"(xa[0]), "+v"(xa[1]), "+v"(xa[2]), "+v"(xa[3]), "+v"(ya[0]), "+v"(ya[1]), "+v"(ya[2]), \
+                           "+v"(ya[3]));                                                                            \
+        } else {                                                                                                    \
+            asm volatile("s_waitcnt lgkmcnt(0)"                                                                     \
+                         : "+v"(xa[0]), "+v"(xa[1]), "+v"(xa[2]), "+v"(xa[3]), "+v"(ya[0]), "+v"(ya[1]), "+v"(ya[2]), \
+                           "+v"(ya[3]));                                                                            \
+        }                                                                                                           \
+        PH_TBF_ROW(4 * g + 0, xa[0].x, xa[0].y, ya[0].x, ya[0].y);                                                  \
+        PH_TBF_ROW(4 * g + 1, xa[1].x, xa[1].y, ya[1].x, ya[1].y);                                                  \
+        PH_TBF_ROW(4 * g + 2, xa[2].x, xa[2].y, ya[2].x, ya[2].y);                                                  \
+        PH_TBF_ROW(4 * g + 3, xa[3].x, xa[3].y, ya[3].x, ya[3].y);                                                  \
+        _Pragma("unroll") for (int q = 0; q < 4; ++q)                                                               \
+        {                                                                                                           \
+            xa[q] = xb[q];                                                                                          \
+            ya[q] = yb[q];                                                                                          \
+        }                                                                                                           \
+    }
 // the profile entries of four row pairs (one packed register of code offsets per band): eight ds_read_b64
 #define PH_TBF_ISSUE(pk0, pk1, X, Y)                                                                       \
     do {                                                                                                   \
@@ -787,6 +826,60 @@ __device__ __forceinline__ uint32_t tbf_walk(const uint32_t *__restrict__ dirw, 
     return len;
 }
 
+// Byte offsets (code * 8) inside a profile block of the 2 RB rows a lane holds, rows row0 .. row0 + 2 RB - 1 of its pair
+// (row0 = 0, or the odd lane's half in tb_prof16x2_kernel): four rows per register and band, rows >= lenA the pad code.
+// The read's bytes come as RL / 4 + 1 aligned dwords, all in flight at once, through a buffer resource over this
+// launch's reads (as sw_pk1_kernel does; a byte at a time the prologue was RL dependent round trips).  Beyond the
+// batch's last byte a buffer load returns 0: those rows are >= lenA.  4 GB and more keep the byte loads.
+// (A is not __restrict__: p.ap points into it.)
+template <int RB>
+__device__ __forceinline__ void tbf_row_codes(const uint8_t *A, const uint64_t *offA, uint64_t pair1,
+                                              const TbPair &p, uint32_t row0, const uint8_t *codeL, int ncodes,
+                                              uint32_t (&apk0)[RB / 4], uint32_t (&apk1)[RB / 4])
+{
+    constexpr int RL = 2 * RB;
+    auto pack = [&](auto sym) { // sym(i) = the read's symbol in the lane's row i
+#pragma unroll
+        for (int w = 0; w < RB / 4; ++w) {
+            uint32_t k0 = 0, k1 = 0;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const int i0 = 4 * w + b, i1 = RB + 4 * w + b;
+                uint32_t c0 = (uint32_t)ncodes, c1 = (uint32_t)ncodes;
+                if (p.work && row0 + i0 < p.lenA) {
+                    const uint32_t c = codeL[sym(i0)];
+                    c0 = c == 0xFFu ? (uint32_t)ncodes : c;
+                }
+                if (p.work && row0 + i1 < p.lenA) {
+                    const uint32_t c = codeL[sym(i1)];
+                    c1 = c == 0xFFu ? (uint32_t)ncodes : c;
+                }
+                k0 |= (c0 * 8u) << (8 * b);
+                k1 |= (c1 * 8u) << (8 * b);
+            }
+            apk0[w] = k0;
+            apk1[w] = k1;
+        }
+    };
+    const uint64_t totalA = offA[pair1];
+    if (totalA < 0xFFFFFFF0ull) {
+        const uint32_t misA = (uint32_t)(reinterpret_cast<uintptr_t>(A) & 3u);
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(A) - misA, 0,
+                                                                            (int)(((uint32_t)totalA + misA + 3u) & ~3u), 0x00020000);
+        const uint32_t b0 = (uint32_t)p.oA + misA + row0;
+        uint32_t aw[RL / 4 + 1], dd[RL / 4];
+#pragma unroll
+        for (int w = 0; w <= RL / 4; ++w)
+            aw[w] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, (int)((b0 & ~3u) + 4u * w), 0, 0);
+#pragma unroll
+        for (int w = 0; w < RL / 4; ++w)
+            dd[w] = __builtin_amdgcn_alignbyte(aw[w + 1], aw[w], b0 & 3u);
+        pack([&](int i) { return (dd[i >> 2] >> (8 * (i & 3))) & 0xFFu; });
+    } else {
+        pack([&](int i) { return (uint32_t)p.ap[row0 + i]; });
+    }
+}
+
 template <int RB>
 __global__ __launch_bounds__(THREADS, 2) void tb_prof16_kernel(
     const uint8_t *__restrict__ A, const uint64_t *__restrict__ offA, uint64_t pair0, uint64_t pair1,
@@ -813,156 +906,21 @@ __global__ __launch_bounds__(THREADS, 2) void tb_prof16_kernel(
 
     const uint64_t pair = pair0 + (uint64_t)blockIdx.x * THREADS + tid;
     const bool active = pair < pair1;
-    uint32_t lenA = 0, eA = 0, eB = 0;
-    int64_t M = 0;
-    const uint8_t *ap = A;
-    uint64_t oA = 0;
-    if (active) {
-        const uint64_t o0 = offA[pair];
-        oA = o0;
-        lenA = (uint32_t)(offA[pair + 1] - o0);
-        ap = A + o0;
-        if (err[pair] == 0u) {
-            eA = endA[pair];
-            eB = endB[pair];
-            M = score[pair];
-        }
-    }
-    const bool locate = active && (wide & TB_DEFERRED) && eA == k3p::SW_END_DEFERRED; // as tb_prof_kernel
-    const uint32_t rowsA = locate ? lenA : eA;
-    const bool work = active && rowsA > 0 && rowsA <= lenA && eB > 0 && M > 0 && lenA <= RA;
-    const uint32_t mycols = work ? min(wcols + 4u, pair_window(wcols, rowsA, M, smax, gap, wide & TB_WIDE) + (locate ? 4u : 0u)) : 0u;
-    const uint32_t c_s = (work && eB > mycols) ? eB - mycols + 1u : 1u;
-    const uint32_t jb0 = (c_s - 1u) & ~3u;
-    const uint32_t nblk = work ? (eB - jb0 + TBU - 1) / TBU : 0u; // <= nblk_alloc - 1
-
-    // byte offsets (code * 8) of my rows inside a profile block, four rows per register and band.  The read's bytes come as
-    // RA / 4 + 1 aligned dwords, all in flight at once, through a buffer resource over this launch's reads (as
-    // sw_pk1_kernel does; a byte at a time the prologue was RA dependent round trips); 4 GB and more keep the byte loads.
+    TbPair p = tb_pair_load<RA>(pair, pair1, A, offA, err, endA, endB, score, wcols, wide, smax, gap);
+    const uint32_t jb0 = p.jb0, nblk = p.nblk; // nblk <= nblk_alloc - 1
     uint32_t apk0[RB / 4], apk1[RB / 4];
-    const uint64_t totalA = offA[pair1];
-    if (totalA < 0xFFFFFFF0ull) {
-        const uint32_t misA = (uint32_t)(reinterpret_cast<uintptr_t>(A) & 3u);
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(A) - misA, 0,
-                                                                            (int)(((uint32_t)totalA + misA + 3u) & ~3u), 0x00020000);
-        const uint32_t b0 = (uint32_t)oA + misA;
-        uint32_t dd[RA / 4];
-        {
-            uint32_t aw[RA / 4 + 1];
-#pragma unroll
-            for (int w = 0; w <= RA / 4; ++w)
-                aw[w] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, (int)((b0 & ~3u) + 4u * w), 0, 0);
-#pragma unroll
-            for (int w = 0; w < RA / 4; ++w)
-                dd[w] = __builtin_amdgcn_alignbyte(aw[w + 1], aw[w], b0 & 3u);
-        }
-#pragma unroll
-        for (int w = 0; w < RB / 4; ++w) {
-            uint32_t k0 = 0, k1 = 0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const int i0 = 4 * w + b, i1 = RB + 4 * w + b;
-                uint32_t c0 = (uint32_t)ncodes, c1 = (uint32_t)ncodes;
-                if (work && (uint32_t)i0 < lenA) {
-                    const uint32_t c = codeL[(dd[w] >> (8 * b)) & 0xFFu];
-                    c0 = c == 0xFFu ? (uint32_t)ncodes : c;
-                }
-                if (work && (uint32_t)i1 < lenA) {
-                    const uint32_t c = codeL[(dd[RB / 4 + w] >> (8 * b)) & 0xFFu];
-                    c1 = c == 0xFFu ? (uint32_t)ncodes : c;
-                }
-                k0 |= (c0 * 8u) << (8 * b);
-                k1 |= (c1 * 8u) << (8 * b);
-            }
-            apk0[w] = k0;
-            apk1[w] = k1;
-        }
-    } else {
-#pragma unroll
-        for (int w = 0; w < RB / 4; ++w) {
-            uint32_t k0 = 0, k1 = 0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const int i0 = 4 * w + b, i1 = RB + 4 * w + b;
-                uint32_t c0 = (uint32_t)ncodes, c1 = (uint32_t)ncodes;
-                if (work && (uint32_t)i0 < lenA) {
-                    const uint32_t c = codeL[ap[i0]];
-                    c0 = c == 0xFFu ? (uint32_t)ncodes : c;
-                }
-                if (work && (uint32_t)i1 < lenA) {
-                    const uint32_t c = codeL[ap[i1]];
-                    c1 = c == 0xFFu ? (uint32_t)ncodes : c;
-                }
-                k0 |= (c0 * 8u) << (8 * b);
-                k1 |= (c1 * 8u) << (8 * b);
-            }
-            apk0[w] = k0;
-            apk1[w] = k1;
-        }
-    }
+    tbf_row_codes<RB>(A, offA, pair1, p, 0u, codeL, ncodes, apk0, apk1);
 
-    uint32_t H[RB];
-#pragma unroll
-    for (int i = 0; i < RB; ++i)
-        H[i] = 0;
-
-    const uint64_t wave_global = ((uint64_t)blockIdx.x * THREADS + tid) >> 6;
-    static_assert(TBU == 4, "a lane's piece of direction words is (G, L) x four columns");
-    uint32_t *dirw = dirbuf + wave_global * ((size_t)nblk_alloc * TBU * NG * 2 * 64) + lane * 8;
+    PH_TBF_SETUP(nblk); // a lane runs nblk + 1 iterations (band 1 finishes one block later)
     const uint32_t lds_base = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(P));
     const uint32_t pad_base = lds_base + nqB * pstride;
-
-    // end-aligned lanes as in tb_prof_kernel; a lane runs nblk + 1 iterations (band 1 finishes one block later)
-    uint32_t nmax = nblk;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-        nmax = max(nmax, (uint32_t)__shfl_xor((int)nmax, d, 64));
-    const uint32_t lag = nmax - nblk;
-    const uint32_t gh = tbf_half_bits(gap); // gap < 0
-    const uint32_t gap2 = gh | (gh << 16), one2 = 0x00010001u, two2 = 0x00020002u;
-    const uint32_t Mh = tbf_half_bits((int)M);
-    uint32_t key = 0xFFFFFFFFu;
-    // band 0's last row of the block before, already in the high halves: what band 1 finds above its first row
-    uint32_t hh0 = 0, hh1 = 0, hh2 = 0, hh3 = 0, hg0 = 0, hg1 = 0, hg2 = 0, hg3 = 0, hd = 0;
+    const uint32_t Mh = tbf_half_bits((int)p.M);
     auto sweep = [&](uint32_t tt, auto find_tag) {
         constexpr int FIND = decltype(find_tag)::value; // 0, 1 = search band 0's cells, 2 = band 1's
         const uint32_t bt = tt - lag;                   // band 0's block; band 1 works on bt - 1
         const uint32_t base0 = bt < nblk ? lds_base + ((jb0 >> 2) + bt) * pstride : pad_base;
         const uint32_t base1 = bt >= 1u ? lds_base + ((jb0 >> 2) + bt - 1u) * pstride : pad_base;
-        uint32_t pr0 = hh0, pr1 = hh1, pr2 = hh2, pr3 = hh3, pg0 = hg0, pg1 = hg1, pg2 = hg2, pg3 = hg3, pdiag = hd;
-        uint32_t wG[TBU] = {0u, 0u, 0u, 0u}, wL[TBU] = {0u, 0u, 0u, 0u};
-        tbf_u32x2 xa[4], ya[4], xb[4], yb[4];
-        PH_TBF_ISSUE(apk0[0], apk1[0], xa, ya);
-#pragma unroll
-        for (int g = 0; g < RB / 4; ++g) {
-            if (g + 1 < RB / 4) {
-                PH_TBF_ISSUE(apk0[g + 1], apk1[g + 1], xb, yb);
-                asm volatile("s_waitcnt lgkmcnt(8)"
-                             : "+v"(xa[0]), "+v"(xa[1]), "+v"(xa[2]), "+v"(xa[3]), "+v"(ya[0]), "+v"(ya[1]), "+v"(ya[2]),
-                               "+v"(ya[3]));
-            } else {
-                asm volatile("s_waitcnt lgkmcnt(0)"
-                             : "+v"(xa[0]), "+v"(xa[1]), "+v"(xa[2]), "+v"(xa[3]), "+v"(ya[0]), "+v"(ya[1]), "+v"(ya[2]),
-                               "+v"(ya[3]));
-            }
-#ifdef PH_TBF_WF
-            if constexpr (FIND == 0) {
-                PH_TBF_ROW2(4 * g + 0, xa[0].x, xa[0].y, ya[0].x, ya[0].y, xa[1].x, xa[1].y, ya[1].x, ya[1].y);
-                PH_TBF_ROW2(4 * g + 2, xa[2].x, xa[2].y, ya[2].x, ya[2].y, xa[3].x, xa[3].y, ya[3].x, ya[3].y);
-            } else
-#endif
-            {
-            PH_TBF_ROW(4 * g + 0, xa[0].x, xa[0].y, ya[0].x, ya[0].y);
-            PH_TBF_ROW(4 * g + 1, xa[1].x, xa[1].y, ya[1].x, ya[1].y);
-            PH_TBF_ROW(4 * g + 2, xa[2].x, xa[2].y, ya[2].x, ya[2].y);
-            PH_TBF_ROW(4 * g + 3, xa[3].x, xa[3].y, ya[3].x, ya[3].y);
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                xa[q] = xb[q];
-                ya[q] = yb[q];
-            }
-        }
+        PH_TBF_ROW_GROUPS();
         // band 0's last row (low halves) becomes band 1's row above (high halves) of the next iteration
         hd = hh3;
         hh0 = pr0 << 16;
@@ -974,7 +932,7 @@ __global__ __launch_bounds__(THREADS, 2) void tb_prof16_kernel(
         hg2 = pg2 << 16;
         hg3 = pg3 << 16;
     };
-    const bool any_locate = __any(locate) != 0; // wave-uniform
+    const bool any_locate = __any(p.locate) != 0; // wave-uniform
     // iterations 0 .. nmax; with a deferred end cell in the wave the last two carry the search (band 0's last block,
     // then band 1's)
     for (uint32_t t = 0; t <= nmax; ++t) {
@@ -991,25 +949,12 @@ __global__ __launch_bounds__(THREADS, 2) void tb_prof16_kernel(
     if (!active)
         return;
     uint32_t len = 0;
-    bool lost = false;
-    if (work && locate) {
-        lost = key == 0xFFFFFFFFu; // cannot happen: the packed pass saw M in this block
-        eA = lost ? 0u : (key >> 2) + 1u;
-        eB = lost ? 0u : eB - 3u + (key & 3u);
-        endA[pair] = eA;
-        endB[pair] = eB;
-        if (lost)
-            err[pair] = 0xFFFFFFFEu;
-    } else if (locate) {
-        endA[pair] = 0u;
-        endB[pair] = 0u;
-    }
-    if (work && !lost) {
+    if (tb_pair_end(p, pair, key, endA, endB, err)) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); // my own stores, read back by me
-        len = tbf_walk<RB, 1>(dirw, jb0, lag, eA, eB, (int)M, gap, ncp, reinterpret_cast<const uint16_t *>(P), codeL, ap, B,
+        len = tbf_walk<RB, 1>(dirw, jb0, lag, p.eA, p.eB, (int)p.M, gap, ncp, reinterpret_cast<const uint16_t *>(P), codeL, p.ap, B,
                               alnA + pair * stride, alnB + pair * stride, stride);
     }
-    alnLen[pair] = (active && rowsA > 0 && lenA > RA) ? 0xFFFFFFFFu : len;
+    alnLen[pair] = (active && p.rowsA > 0 && p.lenA > RA) ? 0xFFFFFFFFu : len;
 }
 
 // ---- every pair with its own B (reads against reads) on packed halves ---------------------------------------------------
@@ -1052,107 +997,21 @@ __global__ __launch_bounds__(THREADS, 2) void tb_pair16_kernel(
 
     const uint64_t pair = pair0 + (uint64_t)blockIdx.x * THREADS + tid;
     const bool active = pair < pair1;
-    uint32_t lenA = 0, eA = 0, eB = 0;
-    int64_t M = 0;
-    const uint8_t *ap = A, *B = Ball;
-    uint64_t oA = 0;
+    const uint8_t *B = Ball;
     uint32_t lenB = 0;
     if (active) {
-        const uint64_t o0 = offA[pair];
-        oA = o0;
-        lenA = (uint32_t)(offA[pair + 1] - o0);
-        ap = A + o0;
         const uint64_t ob = offB[pair];
         B = Ball + ob;
         lenB = (uint32_t)(offB[pair + 1] - ob);
-        if (err[pair] == 0u) {
-            eA = endA[pair];
-            eB = endB[pair];
-            M = score[pair];
-        }
     }
-    const bool locate = active && (wide & TB_DEFERRED) && eA == k3p::SW_END_DEFERRED; // as tb_prof_kernel
-    const uint32_t rowsA = locate ? lenA : eA;
-    const bool work = active && rowsA > 0 && rowsA <= lenA && eB > 0 && eB <= lenB && M > 0 && lenA <= RA;
-    const uint32_t mycols = work ? min(wcols + 4u, pair_window(wcols, rowsA, M, smax, gap, wide & TB_WIDE) + (locate ? 4u : 0u)) : 0u;
-    const uint32_t c_s = (work && eB > mycols) ? eB - mycols + 1u : 1u;
-    const uint32_t jb0 = (c_s - 1u) & ~3u;
-    const uint32_t nblk = work ? (eB - jb0 + TBU - 1) / TBU : 0u; // <= nblk_alloc - 1
-
-    // byte offsets (code * 8) of my rows inside a profile block, four rows per register and band.  The read's bytes come as
-    // RA / 4 + 1 aligned dwords, all in flight at once, through a buffer resource over this launch's reads (as
-    // sw_pk1_kernel does; a byte at a time the prologue was RA dependent round trips); 4 GB and more keep the byte loads.
+    TbPair p = tb_pair_load<RA, true>(pair, pair1, A, offA, err, endA, endB, score, wcols, wide, smax, gap, lenB);
+    const uint32_t jb0 = p.jb0, nblk = p.nblk; // nblk <= nblk_alloc - 1
     uint32_t apk0[RB / 4], apk1[RB / 4];
-    const uint64_t totalA = offA[pair1];
-    if (totalA < 0xFFFFFFF0ull) {
-        const uint32_t misA = (uint32_t)(reinterpret_cast<uintptr_t>(A) & 3u);
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(A) - misA, 0,
-                                                                            (int)(((uint32_t)totalA + misA + 3u) & ~3u), 0x00020000);
-        const uint32_t b0 = (uint32_t)oA + misA;
-        uint32_t dd[RA / 4];
-        {
-            uint32_t aw[RA / 4 + 1];
-#pragma unroll
-            for (int w = 0; w <= RA / 4; ++w)
-                aw[w] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, (int)((b0 & ~3u) + 4u * w), 0, 0);
-#pragma unroll
-            for (int w = 0; w < RA / 4; ++w)
-                dd[w] = __builtin_amdgcn_alignbyte(aw[w + 1], aw[w], b0 & 3u);
-        }
-#pragma unroll
-        for (int w = 0; w < RB / 4; ++w) {
-            uint32_t k0 = 0, k1 = 0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const int i0 = 4 * w + b, i1 = RB + 4 * w + b;
-                uint32_t c0 = (uint32_t)ncodes, c1 = (uint32_t)ncodes;
-                if (work && (uint32_t)i0 < lenA) {
-                    const uint32_t c = codeL[(dd[w] >> (8 * b)) & 0xFFu];
-                    c0 = c == 0xFFu ? (uint32_t)ncodes : c;
-                }
-                if (work && (uint32_t)i1 < lenA) {
-                    const uint32_t c = codeL[(dd[RB / 4 + w] >> (8 * b)) & 0xFFu];
-                    c1 = c == 0xFFu ? (uint32_t)ncodes : c;
-                }
-                k0 |= (c0 * 8u) << (8 * b);
-                k1 |= (c1 * 8u) << (8 * b);
-            }
-            apk0[w] = k0;
-            apk1[w] = k1;
-        }
-    } else {
-#pragma unroll
-        for (int w = 0; w < RB / 4; ++w) {
-            uint32_t k0 = 0, k1 = 0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const int i0 = 4 * w + b, i1 = RB + 4 * w + b;
-                uint32_t c0 = (uint32_t)ncodes, c1 = (uint32_t)ncodes;
-                if (work && (uint32_t)i0 < lenA) {
-                    const uint32_t c = codeL[ap[i0]];
-                    c0 = c == 0xFFu ? (uint32_t)ncodes : c;
-                }
-                if (work && (uint32_t)i1 < lenA) {
-                    const uint32_t c = codeL[ap[i1]];
-                    c1 = c == 0xFFu ? (uint32_t)ncodes : c;
-                }
-                k0 |= (c0 * 8u) << (8 * b);
-                k1 |= (c1 * 8u) << (8 * b);
-            }
-            apk0[w] = k0;
-            apk1[w] = k1;
-        }
-    }
+    tbf_row_codes<RB>(A, offA, pair1, p, 0u, codeL, ncodes, apk0, apk1);
 
-    uint32_t H[RB];
-#pragma unroll
-    for (int i = 0; i < RB; ++i)
-        H[i] = 0;
-
-    const uint64_t wave_global = ((uint64_t)blockIdx.x * THREADS + tid) >> 6;
-    static_assert(TBU == 4, "a lane's piece of direction words is (G, L) x four columns");
-    uint32_t *dirw = dirbuf + wave_global * ((size_t)nblk_alloc * TBU * NG * 2 * 64) + lane * 8;
+    PH_TBF_SETUP(nblk); // a lane runs nblk + 1 iterations (band 1 finishes one block later)
     const uint32_t slot_base = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(slots)) + (uint32_t)tid * SLOT;
+    const uint32_t Mh = tbf_half_bits((int)p.M);
     // the four B symbols of a block, as the bytes of one register (0xFF = past the end of B: the pad score); block 0 now,
     // the others an iteration ahead
     auto block_syms = [&](uint32_t bt) -> uint32_t {
@@ -1167,19 +1026,6 @@ __global__ __launch_bounds__(THREADS, 2) void tb_pair16_kernel(
         return w;
     };
     uint32_t bnext = block_syms(0);
-
-    // end-aligned lanes as in tb_prof_kernel; a lane runs nblk + 1 iterations (band 1 finishes one block later)
-    uint32_t nmax = nblk;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-        nmax = max(nmax, (uint32_t)__shfl_xor((int)nmax, d, 64));
-    const uint32_t lag = nmax - nblk;
-    const uint32_t gh = tbf_half_bits(gap); // gap < 0
-    const uint32_t gap2 = gh | (gh << 16), one2 = 0x00010001u, two2 = 0x00020002u;
-    const uint32_t Mh = tbf_half_bits((int)M);
-    uint32_t key = 0xFFFFFFFFu;
-    // band 0's last row of the block before, already in the high halves: what band 1 finds above its first row
-    uint32_t hh0 = 0, hh1 = 0, hh2 = 0, hh3 = 0, hg0 = 0, hg1 = 0, hg2 = 0, hg3 = 0, hd = 0;
     auto sweep = [&](uint32_t tt, auto find_tag) {
         constexpr int FIND = decltype(find_tag)::value; // 0, 1 = search band 0's cells, 2 = band 1's
         const uint32_t bt = tt - lag;                   // band 0's block; band 1 works on bt - 1
@@ -1200,32 +1046,7 @@ __global__ __launch_bounds__(THREADS, 2) void tb_pair16_kernel(
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         }
-        uint32_t pr0 = hh0, pr1 = hh1, pr2 = hh2, pr3 = hh3, pg0 = hg0, pg1 = hg1, pg2 = hg2, pg3 = hg3, pdiag = hd;
-        uint32_t wG[TBU] = {0u, 0u, 0u, 0u}, wL[TBU] = {0u, 0u, 0u, 0u};
-        tbf_u32x2 xa[4], ya[4], xb[4], yb[4];
-        PH_TBF_ISSUE(apk0[0], apk1[0], xa, ya);
-#pragma unroll
-        for (int g = 0; g < RB / 4; ++g) {
-            if (g + 1 < RB / 4) {
-                PH_TBF_ISSUE(apk0[g + 1], apk1[g + 1], xb, yb);
-                asm volatile("s_waitcnt lgkmcnt(8)"
-                             : "+v"(xa[0]), "+v"(xa[1]), "+v"(xa[2]), "+v"(xa[3]), "+v"(ya[0]), "+v"(ya[1]), "+v"(ya[2]),
-                               "+v"(ya[3]));
-            } else {
-                asm volatile("s_waitcnt lgkmcnt(0)"
-                             : "+v"(xa[0]), "+v"(xa[1]), "+v"(xa[2]), "+v"(xa[3]), "+v"(ya[0]), "+v"(ya[1]), "+v"(ya[2]),
-                               "+v"(ya[3]));
-            }
-            PH_TBF_ROW(4 * g + 0, xa[0].x, xa[0].y, ya[0].x, ya[0].y);
-            PH_TBF_ROW(4 * g + 1, xa[1].x, xa[1].y, ya[1].x, ya[1].y);
-            PH_TBF_ROW(4 * g + 2, xa[2].x, xa[2].y, ya[2].x, ya[2].y);
-            PH_TBF_ROW(4 * g + 3, xa[3].x, xa[3].y, ya[3].x, ya[3].y);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                xa[q] = xb[q];
-                ya[q] = yb[q];
-            }
-        }
+        PH_TBF_ROW_GROUPS();
         // band 0's last row (low halves) becomes band 1's row above (high halves) of the next iteration
         hd = hh3;
         hh0 = pr0 << 16;
@@ -1237,7 +1058,7 @@ __global__ __launch_bounds__(THREADS, 2) void tb_pair16_kernel(
         hg2 = pg2 << 16;
         hg3 = pg3 << 16;
     };
-    const bool any_locate = __any(locate) != 0; // wave-uniform
+    const bool any_locate = __any(p.locate) != 0; // wave-uniform
     // iterations 0 .. nmax; with a deferred end cell in the wave the last two carry the search (band 0's last block,
     // then band 1's)
     for (uint32_t t = 0; t <= nmax; ++t) {
@@ -1254,25 +1075,12 @@ __global__ __launch_bounds__(THREADS, 2) void tb_pair16_kernel(
     if (!active)
         return;
     uint32_t len = 0;
-    bool lost = false;
-    if (work && locate) {
-        lost = key == 0xFFFFFFFFu; // cannot happen: the packed pass saw M in this block
-        eA = lost ? 0u : (key >> 2) + 1u;
-        eB = lost ? 0u : eB - 3u + (key & 3u);
-        endA[pair] = eA;
-        endB[pair] = eB;
-        if (lost)
-            err[pair] = 0xFFFFFFFEu;
-    } else if (locate) {
-        endA[pair] = 0u;
-        endB[pair] = 0u;
-    }
-    if (work && !lost) {
+    if (tb_pair_end(p, pair, key, endA, endB, err)) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); // my own stores, read back by me
-        len = tbf_walk<RB, 1, true>(dirw, jb0, lag, eA, eB, (int)M, gap, ncp, H16, codeL, ap, B, alnA + pair * stride,
+        len = tbf_walk<RB, 1, true>(dirw, jb0, lag, p.eA, p.eB, (int)p.M, gap, ncp, H16, codeL, p.ap, B, alnA + pair * stride,
                                     alnB + pair * stride, stride);
     }
-    alnLen[pair] = (active && rowsA > 0 && lenA > RA) ? 0xFFFFFFFFu : len;
+    alnLen[pair] = (active && p.rowsA > 0 && p.lenA > RA) ? 0xFFFFFFFFu : len;
 }
 
 // ---- 153..256 rows on packed halves: TWO LANES per pair, four bands of RB rows ---------------------------------------
@@ -1314,118 +1122,19 @@ __global__ __launch_bounds__(THREADS, 2) void tb_prof16x2_kernel(
 
     const uint64_t pair = pair0 + (((uint64_t)blockIdx.x * THREADS + tid) >> 1);
     const bool active = pair < pair1;
-    uint32_t lenA = 0, eA = 0, eB = 0;
-    int64_t M = 0;
-    const uint8_t *ap = A;
-    uint64_t oA = 0;
-    if (active) {
-        const uint64_t o0 = offA[pair];
-        oA = o0;
-        lenA = (uint32_t)(offA[pair + 1] - o0);
-        ap = A + o0;
-        if (err[pair] == 0u) {
-            eA = endA[pair];
-            eB = endB[pair];
-            M = score[pair];
-        }
-    }
-    // everything below is the same in both lanes of a pair (its rows apart)
-    const bool locate = active && (wide & TB_DEFERRED) && eA == k3p::SW_END_DEFERRED; // as tb_prof_kernel
-    const uint32_t rowsA = locate ? lenA : eA;
-    const bool work = active && rowsA > 0 && rowsA <= lenA && eB > 0 && M > 0 && lenA <= RA;
-    const uint32_t mycols = work ? min(wcols + 4u, pair_window(wcols, rowsA, M, smax, gap, wide & TB_WIDE) + (locate ? 4u : 0u)) : 0u;
-    const uint32_t c_s = (work && eB > mycols) ? eB - mycols + 1u : 1u;
-    const uint32_t jb0 = (c_s - 1u) & ~3u;
-    const uint32_t nblk = work ? (eB - jb0 + TBU - 1) / TBU : 0u; // <= nblk_alloc - 3
-
-    // byte offsets (code * 8) of my RL rows inside a profile block, four rows per register and band (as tb_prof16_kernel)
+    // the pair's state is the same in both of its lanes (their rows apart)
+    TbPair p = tb_pair_load<RA>(pair, pair1, A, offA, err, endA, endB, score, wcols, wide, smax, gap);
+    const uint32_t jb0 = p.jb0, nblk = p.nblk; // nblk <= nblk_alloc - 3
     uint32_t apk0[RB / 4], apk1[RB / 4];
-    const uint32_t row0 = hl * RL;
-    const uint64_t totalA = offA[pair1];
-    if (totalA < 0xFFFFFFF0ull) {
-        const uint32_t misA = (uint32_t)(reinterpret_cast<uintptr_t>(A) & 3u);
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(A) - misA, 0,
-                                                                            (int)(((uint32_t)totalA + misA + 3u) & ~3u), 0x00020000);
-        const uint32_t b0 = (uint32_t)oA + misA + row0; // beyond the batch's last byte a buffer load returns 0: masked below
-        uint32_t dd[RL / 4];
-        {
-            uint32_t aw[RL / 4 + 1];
-#pragma unroll
-            for (int w = 0; w <= RL / 4; ++w)
-                aw[w] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, (int)((b0 & ~3u) + 4u * w), 0, 0);
-#pragma unroll
-            for (int w = 0; w < RL / 4; ++w)
-                dd[w] = __builtin_amdgcn_alignbyte(aw[w + 1], aw[w], b0 & 3u);
-        }
-#pragma unroll
-        for (int w = 0; w < RB / 4; ++w) {
-            uint32_t k0 = 0, k1 = 0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const uint32_t i0 = row0 + 4 * w + b, i1 = row0 + RB + 4 * w + b;
-                uint32_t c0 = (uint32_t)ncodes, c1 = (uint32_t)ncodes;
-                if (work && i0 < lenA) {
-                    const uint32_t c = codeL[(dd[w] >> (8 * b)) & 0xFFu];
-                    c0 = c == 0xFFu ? (uint32_t)ncodes : c;
-                }
-                if (work && i1 < lenA) {
-                    const uint32_t c = codeL[(dd[RB / 4 + w] >> (8 * b)) & 0xFFu];
-                    c1 = c == 0xFFu ? (uint32_t)ncodes : c;
-                }
-                k0 |= (c0 * 8u) << (8 * b);
-                k1 |= (c1 * 8u) << (8 * b);
-            }
-            apk0[w] = k0;
-            apk1[w] = k1;
-        }
-    } else {
-#pragma unroll
-        for (int w = 0; w < RB / 4; ++w) {
-            uint32_t k0 = 0, k1 = 0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const uint32_t i0 = row0 + 4 * w + b, i1 = row0 + RB + 4 * w + b;
-                uint32_t c0 = (uint32_t)ncodes, c1 = (uint32_t)ncodes;
-                if (work && i0 < lenA) {
-                    const uint32_t c = codeL[ap[i0]];
-                    c0 = c == 0xFFu ? (uint32_t)ncodes : c;
-                }
-                if (work && i1 < lenA) {
-                    const uint32_t c = codeL[ap[i1]];
-                    c1 = c == 0xFFu ? (uint32_t)ncodes : c;
-                }
-                k0 |= (c0 * 8u) << (8 * b);
-                k1 |= (c1 * 8u) << (8 * b);
-            }
-            apk0[w] = k0;
-            apk1[w] = k1;
-        }
-    }
+    tbf_row_codes<RB>(A, offA, pair1, p, hl * RL, codeL, ncodes, apk0, apk1);
 
-    uint32_t H[RB];
-#pragma unroll
-    for (int i = 0; i < RB; ++i)
-        H[i] = 0;
-
-    const uint64_t wave_global = ((uint64_t)blockIdx.x * THREADS + tid) >> 6;
-    uint32_t *dirw = dirbuf + wave_global * ((size_t)nblk_alloc * TBU * NG * 2 * 64) + lane * 8;
+    PH_TBF_SETUP(nblk); // a lane runs nblk + 3 iterations (band b finishes b blocks later)
     const uint32_t lds_base = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(P));
     const uint32_t pad_base = lds_base + nqB * pstride;
-
-    // end-aligned lanes as in tb_prof_kernel; a lane runs nblk + 3 iterations (band b finishes b blocks later)
-    uint32_t nmax = nblk;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-        nmax = max(nmax, (uint32_t)__shfl_xor((int)nmax, d, 64));
-    const uint32_t lag = nmax - nblk;
-    const uint32_t gh = tbf_half_bits(gap); // gap < 0
-    const uint32_t gap2 = gh | (gh << 16), one2 = 0x00010001u, two2 = 0x00020002u;
-    const uint32_t Mh_pair = tbf_half_bits((int)M);
-    uint32_t key = 0xFFFFFFFFu;
-    const uint32_t oddmask = hl ? 0xFFFFFFFFu : 0u;
-    // what the band above my first band left behind for the block it finished one iteration ago, and my first band's own
-    // last row already in the high halves: what my two bands find above their first rows
-    uint32_t hh0 = 0, hh1 = 0, hh2 = 0, hh3 = 0, hg0 = 0, hg1 = 0, hg2 = 0, hg3 = 0, hd = 0;
+    const uint32_t Mh_pair = tbf_half_bits((int)p.M);
+    const uint32_t oddmask = 0u - hl; // all ones in the odd lane (as a mask, so that the DPP move below takes the AND with it)
+    // hh / hg / hd in this kernel: what the band above my first band left behind for the block it finished one iteration ago,
+    // and my first band's own last row already in the high halves
     // find_tag: 0, 1 = search my first band's cells for the deferred end cell, 2 = my second band's; Mh = the maximum as a
     // half, or a pattern no H has (0xFFFF) in the lanes whose turn it is not
     auto sweep = [&](uint32_t tt, auto find_tag, const uint32_t Mh) __attribute__((always_inline)) {
@@ -1433,32 +1142,7 @@ __global__ __launch_bounds__(THREADS, 2) void tb_prof16x2_kernel(
         const uint32_t bt = tt - lag - 2u * hl;         // my first band's block (as an unsigned number: "negative" = none yet)
         const uint32_t base0 = bt < nblk ? lds_base + ((jb0 >> 2) + bt) * pstride : pad_base;
         const uint32_t base1 = bt - 1u < nblk ? lds_base + ((jb0 >> 2) + bt - 1u) * pstride : pad_base;
-        uint32_t pr0 = hh0, pr1 = hh1, pr2 = hh2, pr3 = hh3, pg0 = hg0, pg1 = hg1, pg2 = hg2, pg3 = hg3, pdiag = hd;
-        uint32_t wG[TBU] = {0u, 0u, 0u, 0u}, wL[TBU] = {0u, 0u, 0u, 0u};
-        tbf_u32x2 xa[4], ya[4], xb[4], yb[4];
-        PH_TBF_ISSUE(apk0[0], apk1[0], xa, ya);
-#pragma unroll
-        for (int g = 0; g < RB / 4; ++g) {
-            if (g + 1 < RB / 4) {
-                PH_TBF_ISSUE(apk0[g + 1], apk1[g + 1], xb, yb);
-                asm volatile("s_waitcnt lgkmcnt(8)"
-                             : "+v"(xa[0]), "+v"(xa[1]), "+v"(xa[2]), "+v"(xa[3]), "+v"(ya[0]), "+v"(ya[1]), "+v"(ya[2]),
-                               "+v"(ya[3]));
-            } else {
-                asm volatile("s_waitcnt lgkmcnt(0)"
-                             : "+v"(xa[0]), "+v"(xa[1]), "+v"(xa[2]), "+v"(xa[3]), "+v"(ya[0]), "+v"(ya[1]), "+v"(ya[2]),
-                               "+v"(ya[3]));
-            }
-            PH_TBF_ROW(4 * g + 0, xa[0].x, xa[0].y, ya[0].x, ya[0].y);
-            PH_TBF_ROW(4 * g + 1, xa[1].x, xa[1].y, ya[1].x, ya[1].y);
-            PH_TBF_ROW(4 * g + 2, xa[2].x, xa[2].y, ya[2].x, ya[2].y);
-            PH_TBF_ROW(4 * g + 3, xa[3].x, xa[3].y, ya[3].x, ya[3].y);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                xa[q] = xb[q];
-                ya[q] = yb[q];
-            }
-        }
+        PH_TBF_ROW_GROUPS();
         // My first band's last row (low halves) becomes my second band's row above (high halves) of the next iteration; the
         // low halves of an odd lane take what the even lane's second band (its high halves) has just finished -- the row
         // above this lane's first band in the next iteration.  Even lanes: zeros (row 0 has H = 0 above it).
@@ -1476,7 +1160,7 @@ __global__ __launch_bounds__(THREADS, 2) void tb_prof16x2_kernel(
         hg2 = pass(pg2);
         hg3 = pass(pg3);
     };
-    const bool any_locate = __any(locate) != 0; // wave-uniform
+    const bool any_locate = __any(p.locate) != 0; // wave-uniform
     const uint32_t Mh_even = hl ? 0xFFFFu : Mh_pair, Mh_odd = hl ? Mh_pair : 0xFFFFu;
     // iterations 0 .. nmax + 2 (nblk is the same in both lanes of a pair, so a lane and the partner it reads are in step);
     // with a deferred end cell in the wave the last four carry the search: band b sweeps the pair's last block in
@@ -1501,30 +1185,16 @@ __global__ __launch_bounds__(THREADS, 2) void tb_prof16x2_kernel(
     if (!active || hl != 0u)
         return;
     uint32_t len = 0;
-    bool lost = false;
-    if (work && locate) {
-        lost = key == 0xFFFFFFFFu; // cannot happen: the packed pass saw M in this block
-        eA = lost ? 0u : (key >> 2) + 1u;
-        eB = lost ? 0u : eB - 3u + (key & 3u);
-        endA[pair] = eA;
-        endB[pair] = eB;
-        if (lost)
-            err[pair] = 0xFFFFFFFEu;
-    } else if (locate) {
-        endA[pair] = 0u;
-        endB[pair] = 0u;
-    }
-    if (work && !lost) {
+    if (tb_pair_end(p, pair, key, endA, endB, err)) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); // this wave's own stores (my partner's included), read back by me
-        len = tbf_walk<RB, 2>(dirw, jb0, lag, eA, eB, (int)M, gap, ncp, reinterpret_cast<const uint16_t *>(P), codeL, ap, B,
+        len = tbf_walk<RB, 2>(dirw, jb0, lag, p.eA, p.eB, (int)p.M, gap, ncp, reinterpret_cast<const uint16_t *>(P), codeL, p.ap, B,
                               alnA + pair * stride, alnB + pair * stride, stride);
     }
-    alnLen[pair] = (rowsA > 0 && lenA > RA) ? 0xFFFFFFFFu : len;
+    alnLen[pair] = (p.rowsA > 0 && p.lenA > RA) ? 0xFFFFFFFFu : len;
 }
 #undef PH_TBF_ISSUE
 #undef PH_TBF_ADDR
 #undef PH_TBF_ROW
-#undef PH_TBF_ROW2
 #undef PH_TBF_CELL
 
 // ---- reads longer than the 256 rows a lane can hold: ONE WAVE PER PAIR (like sw_wave.hip) ---------------

@@ -849,3 +849,74 @@ def test_fused_align_equals_two_passes(al, monkeypatch, tb_cell, kind, L):
         Lp = int(ln[p])
         got = (int(score[p]), int(ea[p]), int(eb[p]), alnA[p, stride - Lp:].tobytes().decode(), alnB[p, stride - Lp:].tobytes().decode())
         assert got == (ws, wea, web, wa, wb), (p, got, (ws, wea, web, wa, wb))
+
+
+@pytest.mark.parametrize("maxA,maxB", [(64, None), (152, None), (256, None), (64, 90), (152, 90)])
+def test_read_batch_at_an_unaligned_address(al, tb_cell, maxA, maxB):
+    """A at byte offset 1, 2 and 3 of a device tensor: the row-code fetch of the half-float kernels reads aligned dwords and
+    funnels them by the batch's misalignment.  300 pairs (the second workgroup partly filled) of ragged lengths 0 .. maxA,
+    the last read one symbol long (the funnelled loads of the last pairs run past the batch's end), against one 600-symbol
+    reference (paths 1 and 5; the 32-bit fixture: 1 and 4) or every pair its own B of up to 90 symbols (path 6; 2): all
+    outputs equal to the same call on the aligned copy, a sample equal to the oracle."""
+    import torch
+    align = al[0]
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(maxA * 100 + (maxB or 0))
+    n, LB = 300, 600
+    ref = orc.synth_dna(0xA1, LB)
+    la = rng.integers(0, maxA + 1, n)
+    la[:8] = maxA
+    la[-1] = 1
+    As, Bs = [], []
+    for p in range(n):
+        lb = int(rng.integers(1, maxB + 1)) if maxB else LB
+        o = int(rng.integers(0, LB - max(lb if maxB else 0, int(la[p])) + 1))
+        b = ref[o:o + lb] if maxB else ref
+        a = np.resize(ref[o:o + max(1, min(lb, int(la[p])))], int(la[p])).copy()
+        hit = rng.random(len(a)) < (0.5 if p % 4 == 0 else 0.06)
+        a[hit] = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, int(hit.sum()))]
+        As.append(a.tobytes())
+        Bs.append(b.tobytes())
+    A, offA = _pack(As)
+    sc = _scoring(al, "-ACGT", al[2].NUC_4, -2)
+    oAt = torch.from_numpy(offA.astype(np.int64)).to(dev)
+    if maxB:
+        Bf, offB = _pack(Bs)
+        Bt, oBt, lenB = torch.from_numpy(Bf).to(dev), torch.from_numpy(offB.astype(np.int64)).to(dev), maxB
+    else:
+        Bt, oBt, lenB = torch.from_numpy(ref.copy()).to(dev), None, LB
+    stride = align.sw_traceback_stride(sc, maxA, lenB)
+    work = torch.empty(align.sw_workspace_bytes(sc, n, maxA, lenB, maxB is None), dtype=torch.uint8, device=dev)
+    tbw = torch.empty(align.sw_traceback_workspace_bytes(sc, n, maxA, lenB), dtype=torch.uint8, device=dev)
+    want_path = (6 if tb_cell == "half" else 2) if maxB else 1 if maxA <= 152 else 5 if tb_cell == "half" else 4
+    outs = []
+    for mis in range(4):
+        base = torch.zeros(len(A) + 8, dtype=torch.uint8, device=dev)
+        At = base[mis:mis + len(A)]
+        At.copy_(torch.from_numpy(A))
+        assert At.data_ptr() % 4 == mis
+        score = torch.zeros(n, dtype=torch.int64, device=dev)
+        ea, eb, er, ln = (torch.full((n,), 9, dtype=torch.int32, device=dev) for _ in range(4))
+        alnA = torch.zeros((n, stride), dtype=torch.uint8, device=dev)
+        alnB = torch.zeros((n, stride), dtype=torch.uint8, device=dev)
+        align.sw_align_dev(sc, At, oAt, maxA, Bt, oBt, lenB, score, ea, eb, er, alnA, alnB, ln, work, tbw)
+        torch.cuda.synchronize()
+        assert align.sw_traceback_last_path() == want_path
+        if want_path == 1:
+            assert align.sw_traceback_last_half() == (tb_cell == "half")
+        outs.append((score, ea, eb, er, ln, alnA, alnB))
+    live = torch.arange(stride, device=dev)[None, :] >= (stride - outs[0][4].long())[:, None]
+    for mis in (1, 2, 3):
+        for x, y in zip(outs[0][:5], outs[mis][:5]):
+            assert torch.equal(x, y), mis
+        assert bool(((outs[0][5] == outs[mis][5]) | ~live).all()) and bool(((outs[0][6] == outs[mis][6]) | ~live).all()), mis
+    om = orc.SubstitutionMatrix("-ACGT", "-ACGT", orc.NUC_4_SCORES)
+    score, ea, eb, er, ln, alnA, alnB = (t.cpu().numpy() for t in outs[1])
+    assert not er.any()
+    for p in [0, 255, 256, n - 2, n - 1] + [int(x) for x in rng.choice(n - 2, 15, replace=False)]:
+        ws, wa, wb, wea, web = orc.smith_waterman(As[p], Bs[p], om, -2)
+        wa = wa if isinstance(wa, bytes) else wa.encode()
+        wb = wb if isinstance(wb, bytes) else wb.encode()
+        Lp = int(ln[p])
+        got = (int(score[p]), int(ea[p]), int(eb[p]), alnA[p, stride - Lp:].tobytes(), alnB[p, stride - Lp:].tobytes())
+        assert got == (ws, wea, web, wa, wb), (p, got, (ws, wea, web, wa, wb))
