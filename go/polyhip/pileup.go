@@ -110,3 +110,100 @@ func LastPileupInfo() (PileupInfo, error) {
 	return PileupInfo{Entries: uint64(ci.entries), Used: uint64(ci.used), SkippedMapq: uint64(ci.skipped_mapq), Bad: uint64(ci.bad),
 		Columns: uint64(ci.columns), EdgeEvents: uint64(ci.edge_events), Sites: uint64(ci.sites)}, err
 }
+
+// PileupQualParams is polyhip_pileup_qual_params: PileupParams plus the minimum base quality (0..93) and the Phred offset of
+// the quality bytes (33 for FASTQ).
+type PileupQualParams struct {
+	PileupParams
+	MinBaseQual, QualOffset uint32
+}
+
+// PileupQualInfo is polyhip_pileup_qual_info: PileupInfo plus the base columns of used entries below MinBaseQual.
+type PileupQualInfo struct {
+	PileupInfo
+	FilteredBases uint64
+}
+
+// PileupQualResult: PileupResult of the bases that reached MinBaseQual, plus Qsum[(4*strand+k)*L+(p-RegionLo)], k = 0..3: the
+// sum of the qualities of the counted bases.  Deleted bases and events are not filtered.
+type PileupQualResult struct {
+	PileupResult
+	Qsum []uint32
+}
+
+// PileupQual is Pileup with the reads' base qualities: quals[qualOff[i]:qualOff[i+1]] is entry i's quality string as
+// sequenced (FastqPackQual's Quals and QualOffsets when QualMismatch is 0; for MapPairs the mates' strings interleaved).
+func PileupQual(r *MapResult, mapq []uint8, quals []byte, qualOff []uint64, ref []byte, p PileupQualParams, siteCap int) (*PileupQualResult, error) {
+	n := len(r.Flags)
+	if len(r.AlnOff) != n+1 || len(qualOff) != n+1 || len(r.RefStart) != n || len(r.RefEnd) != n || len(r.ReadStart) != n ||
+		(mapq != nil && len(mapq) != n) {
+		return nil, fmt.Errorf("polyhip.PileupQual: the arrays hold different numbers of entries")
+	}
+	if p.RegionLo > p.RegionHi || p.RegionHi > uint64(len(ref)) {
+		return nil, fmt.Errorf("polyhip.PileupQual: the region [%d, %d) is not inside the text of %d bytes", p.RegionLo, p.RegionHi, len(ref))
+	}
+	var cp C.polyhip_pileup_qual_params
+	cp.base.region_lo, cp.base.region_hi = C.uint64_t(p.RegionLo), C.uint64_t(p.RegionHi)
+	cp.base.min_mapq, cp.base.min_depth = C.uint32_t(p.MinMapq), C.uint32_t(p.MinDepth)
+	cp.base.min_alt_count, cp.base.min_alt_permille = C.uint32_t(p.MinAltCount), C.uint32_t(p.MinAltPermille)
+	cp.min_base_qual, cp.qual_offset = C.uint32_t(p.MinBaseQual), C.uint32_t(p.QualOffset)
+	pad32 := func(s []uint32) []uint32 { // an empty batch still needs &s[0]
+		if len(s) == 0 {
+			return []uint32{0}
+		}
+		return s
+	}
+	padB := func(s []byte) []byte {
+		if len(s) == 0 {
+			return []byte{0}
+		}
+		return s
+	}
+	flags, refStart, refEnd, readStart := pad32(r.Flags), pad32(r.RefStart), pad32(r.RefEnd), pad32(r.ReadStart)
+	alnA, alnB, qual, text := padB(r.AlignA), padB(r.AlignB), padB(quals), padB(ref)
+	var mq *C.uint8_t // nil: no mapq, MinMapq must be 0
+	if len(mapq) > 0 {
+		mq = (*C.uint8_t)(unsafe.Pointer(&mapq[0]))
+	}
+	L := int(p.RegionHi - p.RegionLo)
+	out := &PileupQualResult{PileupResult: PileupResult{Counts: make([]uint32, PileupChannels*L+1), Consensus: make([]byte, L+1),
+		Errs: make([]uint32, n+1)}, Qsum: make([]uint32, PileupChannels/2*L+1)}
+	var nsites C.uint64_t
+	var err error
+	for attempt := 0; attempt < 2; attempt++ {
+		out.Sites = make([]PileupSite, siteCap+1)
+		err = call(func() C.int {
+			return C.polyhip_pileup_qual((*C.polyhip_pileup_qual_params)(unsafe.Pointer(&cp)), C.uint64_t(n),
+				(*C.uint32_t)(unsafe.Pointer(&flags[0])), (*C.uint8_t)(unsafe.Pointer(mq)),
+				(*C.uint32_t)(unsafe.Pointer(&refStart[0])), (*C.uint32_t)(unsafe.Pointer(&refEnd[0])),
+				(*C.uint32_t)(unsafe.Pointer(&readStart[0])),
+				(*C.uint8_t)(unsafe.Pointer(&alnA[0])), (*C.uint8_t)(unsafe.Pointer(&alnB[0])),
+				(*C.uint64_t)(unsafe.Pointer(&r.AlnOff[0])), (*C.uint8_t)(unsafe.Pointer(&qual[0])),
+				(*C.uint64_t)(unsafe.Pointer(&qualOff[0])), (*C.uint8_t)(unsafe.Pointer(&text[0])), C.uint64_t(len(ref)),
+				(*C.uint32_t)(unsafe.Pointer(&out.Counts[0])), (*C.uint32_t)(unsafe.Pointer(&out.Qsum[0])),
+				(*C.uint8_t)(unsafe.Pointer(&out.Consensus[0])),
+				(*C.uint64_t)(unsafe.Pointer(&nsites)), (*C.polyhip_pileup_site)(unsafe.Pointer(&out.Sites[0])),
+				C.uint64_t(siteCap), (*C.uint32_t)(unsafe.Pointer(&out.Errs[0])))
+		})
+		if err == nil || uint64(nsites) <= uint64(siteCap) {
+			break
+		}
+		siteCap = int(nsites)
+	}
+	if err != nil {
+		return nil, err
+	}
+	out.Counts, out.Consensus, out.Errs = out.Counts[:PileupChannels*L], out.Consensus[:L], out.Errs[:n]
+	out.Qsum = out.Qsum[:PileupChannels/2*L]
+	out.Sites = out.Sites[:nsites]
+	return out, nil
+}
+
+// LastPileupQualInfo must run on the OS thread that made the call (runtime.LockOSThread around both).
+func LastPileupQualInfo() (PileupQualInfo, error) {
+	var ci C.polyhip_pileup_qual_info
+	err := call(func() C.int { return C.polyhip_pileup_qual_last_info((*C.polyhip_pileup_qual_info)(unsafe.Pointer(&ci))) })
+	return PileupQualInfo{PileupInfo: PileupInfo{Entries: uint64(ci.entries), Used: uint64(ci.used), SkippedMapq: uint64(ci.skipped_mapq),
+		Bad: uint64(ci.bad), Columns: uint64(ci.columns), EdgeEvents: uint64(ci.edge_events), Sites: uint64(ci.sites)},
+		FilteredBases: uint64(ci.filtered_bases)}, err
+}

@@ -419,6 +419,41 @@ func FastqPack(file []byte) (Packed, error) {
 	return p, nil
 }
 
+// PackedQual is Packed plus the Quality field of every record: Quals[QualOffsets[i]:QualOffsets[i+1]] is line 4 of record i
+// without its '\n'.  QualMismatch counts the records whose quality is not as long as their sequence (PileupQual needs 0).
+type PackedQual struct {
+	Packed
+	Quals        []byte
+	QualOffsets  []uint64
+	QualMismatch uint64
+}
+
+// FastqPackQual is FastqPack that also packs the qualities on the device (polyhip_fastq_pack_qual).
+func FastqPackQual(file []byte) (PackedQual, error) {
+	most := len(file)/7 + 1 // shortest record: "@\nA\n\nI\n"
+	p := PackedQual{Packed: Packed{Seqs: make([]byte, len(file)+1), Offsets: make([]uint64, most+2), RecStart: make([]uint64, most+1)},
+		Quals: make([]byte, len(file)+1), QualOffsets: make([]uint64, most+2)}
+	var result [6]uint64
+	var pf *C.uint8_t
+	if len(file) > 0 {
+		pf = (*C.uint8_t)(unsafe.Pointer(&file[0]))
+	}
+	err := call(func() C.int {
+		return C.polyhip_fastq_pack_qual(pf, C.uint64_t(len(file)), (*C.uint8_t)(unsafe.Pointer(&p.Seqs[0])),
+			(*C.uint64_t)(unsafe.Pointer(&p.Offsets[0])), (*C.uint8_t)(unsafe.Pointer(&p.Quals[0])),
+			(*C.uint64_t)(unsafe.Pointer(&p.QualOffsets[0])), (*C.uint64_t)(unsafe.Pointer(&p.RecStart[0])), C.uint64_t(most),
+			(*C.uint64_t)(unsafe.Pointer(&result[0])))
+	})
+	if err != nil {
+		return PackedQual{}, err
+	}
+	n := int(result[0])
+	p.Code, p.Line = int(result[1]), result[2]
+	p.Seqs, p.Offsets, p.RecStart = p.Seqs[:result[3]], p.Offsets[:n+1], p.RecStart[:n]
+	p.Quals, p.QualOffsets, p.QualMismatch = p.Quals[:result[4]], p.QualOffsets[:n+1], result[5]
+	return p, nil
+}
+
 // FastaPack parses a whole FASTA image on the device (io/fasta (*Parser).ParseAll semantics).
 func FastaPack(file []byte) (Packed, error) {
 	most := len(file)/2 + 2 // ">\n" is the shortest header line

@@ -739,6 +739,20 @@ int polyhip_fastq_pack_dev(const uint8_t *d_file, uint64_t nbytes,
 int polyhip_fastq_pack(const uint8_t *file, uint64_t nbytes, uint8_t *seqs,
                        uint64_t *offsets, uint64_t *rec_start,
                        uint64_t max_records, uint64_t *result);
+/*
+ * polyhip_fastq_pack_qual: the same parse, which also packs the Quality field (fastq.go:199, 205-210).  Records, error
+ * codes, line numbers, the ParseN rule, max_records and the capacities are polyhip_fastq_pack's; seqs, offsets, rec_start
+ * and result[0..3] are what that call gives on the same image.  Quality of record i is line 4 without its '\n' (a '\r'
+ * stays, no byte is interpreted), at quals[qual_offsets[i] .. qual_offsets[i + 1]), n + 1 offsets.  The reference does not
+ * require len(Quality) == len(Sequence) and neither does this call: hence offsets of their own.
+ * result has six words: [4] = total quality bytes of the n kept records, [5] = the number of kept records whose quality
+ * length differs from their sequence length (polyhip_pileup_qual needs 0).
+ * Capacities: quals nbytes, qual_offsets as offsets.  Host pointers only: the qualities are parsed, scanned and gathered on
+ * the device in the passes of polyhip_fastq_pack_dev, but there is no device-resident flavour of this call yet.
+ */
+int polyhip_fastq_pack_qual(const uint8_t *file, uint64_t nbytes, uint8_t *seqs,
+                            uint64_t *offsets, uint8_t *quals, uint64_t *qual_offsets,
+                            uint64_t *rec_start, uint64_t max_records, uint64_t *result);
 
 /* ---- read feeder: io/fasta (*Parser).ParseNext / ParseN  (io/fasta/fasta.go:102-238) ---- */
 /*
@@ -1251,7 +1265,8 @@ int polyhip_aln_records_last_info(polyhip_aln_records_info *info);
  * and L == 0 are successful calls; with L == 0 the only outputs are err and *nsites = 0.
  * Host pointers only, no stream: the call copies the arrays in, runs on the calling thread's current device and copies the
  * results out; nothing that depends on n or on the region is allocated before the checks above; the device list does not
- * apply.  One text only; base qualities and the inserted bytes themselves are not looked at.
+ * apply.  One text only; base qualities (polyhip_pileup_qual below takes them) and the inserted bytes themselves are not
+ * looked at.
  * polyhip_pileup_last_info: the calling thread's last call: entries = n; used = used entries; skipped_mapq = entries
  * skipped by min_mapq; bad = entries with err != 0; columns = the columns of the used entries; edge_events = events dropped
  * for anchor -1; sites = *nsites.
@@ -1278,6 +1293,57 @@ int polyhip_pileup(const polyhip_pileup_params *params, uint64_t n, const uint32
                    uint64_t *nsites, polyhip_pileup_site *sites, uint64_t site_capacity,
                    uint32_t *err);
 int polyhip_pileup_last_info(polyhip_pileup_info *info);
+
+/*
+ * polyhip_pileup_qual is polyhip_pileup with the base qualities of the reads: a minimum base quality and, per base and
+ * strand, the sum of the counted qualities.  Everything not named here is polyhip_pileup's definition, unchanged.
+ *  Qualities: entry i's quality string is qual[qualOff[i] .. qualOff[i + 1]), of length m_i; n + 1 offsets.  It is in the
+ *   orientation of the read as sequenced (the FASTQ's), NOT in that of the oriented read q.  With polyhip_fastq_pack_qual
+ *   and result[5] == 0 these are quals and qual_offsets themselves; for polyhip_map_pairs the caller interleaves the mates'
+ *   strings in entry order 2i, 2i + 1.
+ *  Quality of a column: a column c of entry i with a != '-' has the index x = read_start[i] + (earlier columns of the entry
+ *   with a != '-') in q; its index in the read as sequenced is y = x on the forward strand and y = m_i - 1 - x when flags
+ *   bit 1 is set;  Q = qual[qualOff[i] + y] - qual_offset.
+ *  err[i], the first that applies, in this order: 4, 1, 2, 3, 5 as in polyhip_pileup;  6 = read_start[i] plus the number
+ *   of columns with a != '-' exceeds m_i;  7 = some byte of the entry's WHOLE quality string, clipped parts included, is
+ *   below qual_offset or above qual_offset + 93.  The whole entry is judged before any of its adds.
+ *  counts, the same 16 planes: a base column (k = 0..4) is counted only if Q >= min_base_qual.  D columns (k = 5) and the
+ *   events (k = 6, 7) are NOT filtered: a deleted base has no quality of its own and this call does not lend it a
+ *   neighbour's; an event is counted whatever the qualities of the inserted bases.
+ *  qsum, 8 planes of L uint32: qsum[(4 * s + k) * L + (p - region_lo)], k = 0..3 = the sum of Q over the counted base
+ *   columns of that base and strand at p (at most 93 per entry: hence the bound on n below).  Zeroed by the call; may be
+ *   NULL only when L == 0.
+ *  consensus and sites: the unchanged rules applied to the filtered counts.
+ *  info: filtered_bases = the base columns of used entries with Q < min_base_qual, whatever the region (as edge_events is
+ *   counted); the other fields as in polyhip_pileup_info.
+ * Errors, in this order: what polyhip_pileup checks on params->base, in its order (NULL params, region_lo, region_hi,
+ * min_alt_permille);  min_base_qual > 93 or qual_offset > 162 (_INVALID, naming the field);  n * 93 >= 2^32
+ * (POLYHIP_ERR_UNSUPPORTED: qsum is uint32; before any array is read, it takes the place of the n >= 2^32 check);
+ * min_mapq > 0 with mapq == NULL;  the NULL-array checks, where with n > 0 read_start and qualOff are needed too, qual may be
+ * NULL when qualOff[n] == qualOff[0] and qsum goes with counts;  alnOff or qualOff not ascending (_INVALID).
+ * Capacity behaviour, n == 0, L == 0, host pointers only and "nothing that depends on n or the region is allocated before
+ * the checks" are polyhip_pileup's.  Only [qualOff[0], qualOff[n]) of qual is copied in.
+ * Identity: with min_base_qual == 0 and quality strings that raise neither 6 nor 7, counts, consensus, sites, err and the
+ * shared info fields equal polyhip_pileup's on the same arrays.
+ */
+#define POLYHIP_PILEUP_QSUM_PLANES 8u
+typedef struct polyhip_pileup_qual_params {
+    polyhip_pileup_params base;
+    uint32_t min_base_qual;   /* 0..93; a base column with Q < min_base_qual is not counted */
+    uint32_t qual_offset;     /* Phred offset of the quality bytes, 33 for FASTQ; qual_offset + 93 <= 255 */
+} polyhip_pileup_qual_params;
+typedef struct polyhip_pileup_qual_info {
+    uint64_t entries, used, skipped_mapq, bad, columns, edge_events, sites;   /* as polyhip_pileup_info */
+    uint64_t filtered_bases;
+} polyhip_pileup_qual_info;
+int polyhip_pileup_qual(const polyhip_pileup_qual_params *params, uint64_t n, const uint32_t *flags,
+                        const uint8_t *mapq, const uint32_t *ref_start, const uint32_t *ref_end,
+                        const uint32_t *read_start, const uint8_t *alnA, const uint8_t *alnB,
+                        const uint64_t *alnOff, const uint8_t *qual, const uint64_t *qualOff,
+                        const uint8_t *ref, uint64_t ref_len, uint32_t *counts, uint32_t *qsum,
+                        uint8_t *consensus, uint64_t *nsites, polyhip_pileup_site *sites,
+                        uint64_t site_capacity, uint32_t *err);
+int polyhip_pileup_qual_last_info(polyhip_pileup_qual_info *info);
 
 /* ---- R1: the path's one collective -- all-gather of per-rank sketches (RCCL over xGMI) ---- */
 /*

@@ -108,6 +108,7 @@ SIGNATURES = {
     "polyhip_fastq_workspace_bytes": (C.c_size_t, [_u64]),
     "polyhip_fastq_pack_dev": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, C.c_size_t, _vp]),
     "polyhip_fastq_pack": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _u64, _vp]),
+    "polyhip_fastq_pack_qual": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "polyhip_fasta_workspace_bytes": (C.c_size_t, [_u64]),
     "polyhip_fasta_pack_dev": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, C.c_size_t, _vp]),
     "polyhip_fasta_pack": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _u64, _vp]),
@@ -159,6 +160,9 @@ SIGNATURES = {
     "polyhip_aln_records_last_info": (C.c_int, [_vp]),
     "polyhip_pileup": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp]),
     "polyhip_pileup_last_info": (C.c_int, [_vp]),
+    "polyhip_pileup_qual": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64,
+                                      _vp]),
+    "polyhip_pileup_qual_last_info": (C.c_int, [_vp]),
     "polyhip_comm_unique_id": (C.c_int, [_vp]),
     "polyhip_comm_init_rank": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "polyhip_comm_destroy": (C.c_int, [_vp]),

@@ -4,7 +4,7 @@
 //
 //   walk_kernel<false>  one wave per entry, 64 columns per step: err of the entry (the whole entry is judged before any add)
 //   walk_kernel<true>   the same walk over the used entries: one 32-bit integer atomic add per counted column or event
-//   call_kernel<false>  one lane per position: the consensus byte and the number of sites (uint64, for the scan)
+//   call_kernel<false>  (pileup_call.h) one lane per position: the consensus byte and the number of sites (uint64, for the scan)
 //   scan_excl           site offsets; the total comes back to the host with counts, consensus and err
 //   call_kernel<true>   the same pass, writing the sites at the scanned offsets (after the host compared total and capacity)
 //
@@ -15,21 +15,10 @@
 // of matching columns add to consecutive words of one plane.  Sums of integers do not depend on the order of the adds.
 #include "device_prims.h"
 #include "host_pipeline.h"
+#include "pileup_call.h"
 
 namespace polyhip {
 namespace {
-
-constexpr int PU_WAVES = BT / 64;       // entries a block walks at a time
-constexpr unsigned PU_MAX_BLOCKS = 4096; // the walk is a grid-stride loop: a wave adds to the info counters once
-enum : int { INFO_USED = 0, INFO_SKIPPED, INFO_BAD, INFO_COLUMNS, INFO_EDGE, INFO_WORDS };
-enum : uint32_t { CH_OTHER = 4, CH_DEL = 5, CH_INS_EVENT = 6, CH_DEL_EVENT = 7, CH_STRAND = 8 };
-
-// A/a, C/c, G/g, T/t -> 0..3, every other byte 4 (c | 0x20 is 'a' for 'A' and 'a' only, and so on)
-__device__ __forceinline__ uint32_t base_class(uint32_t c)
-{
-    c |= 0x20u;
-    return c == 'a' ? 0u : c == 'c' ? 1u : c == 'g' ? 2u : c == 't' ? 3u : CH_OTHER;
-}
 
 // ADD == false: err[i] is written, info[USED, SKIPPED, BAD, COLUMNS] are added to, counts is not touched.
 // ADD == true: err[i] is read, the used entries add to counts, info[EDGE] is added to.
@@ -120,59 +109,6 @@ __global__ __launch_bounds__(BT) void walk_kernel(uint64_t n, uint32_t min_mapq,
             atomicAdd(&info[INFO_BAD], (unsigned long long)n_bad);
         if (n_edge)
             atomicAdd(&info[INFO_EDGE], (unsigned long long)n_edge);
-    }
-}
-
-// One lane per position of the region.  EMIT == false: consensus[j] and nsite[j] (L + 1 slots for the scan) are written.
-// EMIT == true: nsite (now the offsets) is read and the position's sites are written.
-template <bool EMIT>
-__global__ __launch_bounds__(BT) void call_kernel(uint64_t lo, uint64_t L, uint32_t min_depth, uint32_t min_count, uint32_t permille,
-                                                  const uint32_t *__restrict__ counts, const uint8_t *__restrict__ ref,
-                                                  uint8_t *__restrict__ consensus, uint64_t *nsite, polyhip_pileup_site *__restrict__ sites)
-{
-    for (uint64_t j = (uint64_t)blockIdx.x * BT + threadIdx.x; j < L; j += (uint64_t)gridDim.x * BT) {
-        uint32_t fwd[8], two[8]; // an entry adds at most one to a cell and n < 2^32: no sum below overflows
-#pragma unroll
-        for (uint32_t k = 0; k < 8; ++k) {
-            fwd[k] = counts[k * L + j];
-            two[k] = fwd[k] + counts[(CH_STRAND + k) * L + j];
-        }
-        uint32_t depth = 0, best = 0, most = two[0];
-#pragma unroll
-        for (uint32_t k = 0; k < 6; ++k) {
-            depth += two[k];
-            if (two[k] > most) { // ties stay with the lowest k
-                most = two[k];
-                best = k;
-            }
-        }
-        const bool deep = depth >= min_depth;
-        if (!EMIT)
-            consensus[j] = deep ? (uint8_t)"ACGTN*"[best] : (uint8_t)'N';
-        const uint32_t rb = ref[lo + j], rc = base_class(rb);
-        uint64_t at = EMIT ? nsite[j] : 0;
-#pragma unroll
-        for (uint32_t s = 0; s < 6; ++s) { // SNV to A, C, G, T, then the insertion and the deletion events
-            const uint32_t k = s < 4 ? s : s + 2;
-            const bool is = deep && (s >= 4 || k != rc) && two[k] >= min_count && (uint64_t)two[k] * 1000u >= (uint64_t)permille * depth;
-            if (!is)
-                continue;
-            if (EMIT) {
-                polyhip_pileup_site x;
-                x.pos = (uint32_t)(lo + j);
-                x.depth = depth;
-                x.count = two[k];
-                x.count_fwd = fwd[k];
-                x.kind = (uint8_t)(s < 4 ? 1u : s - 2);
-                x.ref = (uint8_t)rb;
-                x.alt = s < 4 ? (uint8_t)"ACGT"[s] : (uint8_t)0;
-                x.pad = 0;
-                sites[at] = x;
-            }
-            ++at;
-        }
-        if (!EMIT)
-            nsite[j] = at;
     }
 }
 

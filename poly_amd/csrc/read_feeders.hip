@@ -51,7 +51,7 @@ namespace fq {
 constexpr int THREADS = 256;
 constexpr uint32_t PER_BLOCK = THREADS * 16; // bytes a workgroup scans for newlines
 
-enum { R_NREC = 0, R_CODE = 1, R_LINE = 2, R_SEQBYTES = 3, R_NLINES = 4, R_FIRSTBAD = 5, R_WORDS = 8 };
+enum { R_NREC = 0, R_CODE = 1, R_LINE = 2, R_SEQBYTES = 3, R_NLINES = 4, R_FIRSTBAD = 5, R_QUALBYTES = 6, R_QUALDIFF = 7, R_WORDS = 8 };
 
 // ---- single-workgroup exclusive scan of u32 counts into u64 offsets (out[n] = total) --------
 // n = n_host, or *n_dev / div when n_dev != NULL (a count that only exists on the device)
@@ -571,13 +571,15 @@ __device__ uint32_t header_panics(const uint8_t *__restrict__ file, uint64_t s, 
     return 0;
 }
 
-// one thread per complete 4-line record: validate, measure the sequence
+// one thread per complete 4-line record: validate, measure the sequence; QUAL: and the quality, line 4 without its '\n'
+template <bool QUAL>
 __global__ __launch_bounds__(THREADS) void records_kernel(const uint8_t *__restrict__ file,
                                                          const uint64_t *__restrict__ line_end,
                                                          const uint64_t *__restrict__ nlines_dev,
                                                          uint32_t *__restrict__ seq_len, uint64_t *__restrict__ seq_start,
                                                          uint64_t *__restrict__ rec_start, uint64_t max_records,
-                                                         unsigned long long *__restrict__ res)
+                                                         unsigned long long *__restrict__ res, uint32_t *__restrict__ qual_len,
+                                                         uint64_t *__restrict__ qual_start)
 {
     const uint64_t nrec = *nlines_dev / 4; // complete 4-line records
     for (uint64_t r = (uint64_t)blockIdx.x * THREADS + threadIdx.x; r < nrec; r += (uint64_t)gridDim.x * THREADS) {
@@ -592,6 +594,10 @@ __global__ __launch_bounds__(THREADS) void records_kernel(const uint8_t *__restr
         code = 1;
     seq_len[r] = (uint32_t)(e1 - e0 - 1);
     seq_start[r] = e0 + 1;
+    if (QUAL) {
+        qual_len[r] = (uint32_t)(e3 - e2 - 1);
+        qual_start[r] = e2 + 1;
+    }
     if (rec_start && r < max_records)
         rec_start[r] = l0;
     if (code) // the first bad record wins; (record << 8 | code) orders by record
@@ -599,10 +605,11 @@ __global__ __launch_bounds__(THREADS) void records_kernel(const uint8_t *__restr
     }
 }
 
-// n_records, error code / line, and the trailing partial record
+// n_records, error code / line, and the trailing partial record (qual_offsets: NULL, or the quality offsets of the _qual call)
 __global__ void finish_kernel(const uint8_t *__restrict__ file, uint64_t nbytes, const uint64_t *__restrict__ line_end,
                               const uint64_t *__restrict__ nlines_dev, const uint64_t *__restrict__ offsets,
-                              uint64_t max_records, unsigned long long *__restrict__ res)
+                              uint64_t max_records, unsigned long long *__restrict__ res,
+                              const uint64_t *__restrict__ qual_offsets)
 {
     const uint64_t nlines = *nlines_dev;
     const uint64_t nrec = nlines / 4;
@@ -642,22 +649,36 @@ __global__ void finish_kernel(const uint8_t *__restrict__ file, uint64_t nbytes,
     res[R_LINE] = line;
     res[R_SEQBYTES] = offsets[n];
     res[R_NLINES] = nlines;
+    if (qual_offsets)
+        res[R_QUALBYTES] = qual_offsets[n];
 }
 
 // one wave per record (grid-stride): sequence bytes -> packed buffer, whole dwords
+// QUAL: the record's quality bytes in the same visit, and res[R_QUALDIFF] += the kept records whose two lengths differ (the
+// first bad record, and with it n, is known only here: after finish_kernel)
+template <bool QUAL>
 __global__ __launch_bounds__(THREADS) void gather_kernel(const uint8_t *__restrict__ file,
                                                         const uint64_t *__restrict__ seq_start,
                                                         const uint64_t *__restrict__ offsets,
-                                                        const unsigned long long *__restrict__ res,
-                                                        uint8_t *__restrict__ seqs)
+                                                        unsigned long long *__restrict__ res, uint8_t *__restrict__ seqs,
+                                                        const uint64_t *__restrict__ qual_start,
+                                                        const uint64_t *__restrict__ qual_offsets, uint8_t *__restrict__ quals)
 {
     const uint64_t n = res[R_NREC];
     const int lane = threadIdx.x & 63;
     const uint64_t wave = ((uint64_t)blockIdx.x * THREADS + threadIdx.x) >> 6, nwaves = (uint64_t)gridDim.x * (THREADS / 64);
+    uint64_t differ = 0; // of this wave's records, the same in every lane
     for (uint64_t r = wave; r < n; r += nwaves) {
-        const uint64_t dst = offsets[r];
-        group_copy<64>(seqs + dst, file + seq_start[r], offsets[r + 1] - dst, lane);
+        const uint64_t dst = offsets[r], len = offsets[r + 1] - dst;
+        group_copy<64>(seqs + dst, file + seq_start[r], len, lane);
+        if (QUAL) {
+            const uint64_t qdst = qual_offsets[r], qlen = qual_offsets[r + 1] - qdst;
+            group_copy<64>(quals + qdst, file + qual_start[r], qlen, lane);
+            differ += qlen != len ? 1u : 0u;
+        }
     }
+    if (QUAL && lane == 0 && differ)
+        atomicAdd(&res[R_QUALDIFF], (unsigned long long)differ);
 }
 
 // ---- FASTA ----------------------------------------------------------------------------------------
@@ -981,6 +1002,7 @@ struct Layout {
     uint64_t nblocks, max_lines;
     size_t off_counts, off_blockoff, off_lineend, off_seqlen, off_seqstart, off_res, off_scanpart, off_masks, total;
     size_t off_ishdr, off_hrank, off_dst, off_kind; // FASTA (per line)
+    size_t off_quallen, off_qualstart;              // FASTQ with qualities (per record)
 };
 
 static inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -1001,6 +1023,18 @@ static Layout layout(uint64_t nbytes)
     L.off_seqstart = o; o += al((L.max_lines / 4 + 1) * 8);
     L.total = o;
     L.off_ishdr = L.off_hrank = L.off_dst = L.off_kind = 0;
+    L.off_quallen = L.off_qualstart = 0;
+    return L;
+}
+
+// the _qual call keeps a quality length and start per record beside the sequence's
+static Layout layout_qual(uint64_t nbytes)
+{
+    Layout L = layout(nbytes);
+    size_t o = L.total;
+    L.off_quallen = o; o += al((L.max_lines / 4 + 1) * 4);
+    L.off_qualstart = o; o += al((L.max_lines / 4 + 1) * 8);
+    L.total = o;
     return L;
 }
 
@@ -1043,15 +1077,21 @@ extern "C" {
 
 size_t polyhip_fastq_workspace_bytes(uint64_t nbytes) { return fq::layout(nbytes).total; }
 
-int polyhip_fastq_pack_dev(const uint8_t *d_file, uint64_t nbytes, uint8_t *d_seqs, uint64_t *d_offsets,
-                           uint64_t *d_rec_start, uint64_t max_records, uint64_t *d_result, void *d_work,
-                           size_t work_bytes, polyhip_stream_t stream)
+} // extern "C"
+
+// the device side of polyhip_fastq_pack_dev (QUAL == false) and of polyhip_fastq_pack_qual: the same passes, the second
+// with a quality length and start per record, a second scan and the quality bytes gathered beside the sequences
+template <bool QUAL>
+static int fastq_pack_run(const char *who, const uint8_t *d_file, uint64_t nbytes, uint8_t *d_seqs, uint64_t *d_offsets,
+                          uint8_t *d_quals, uint64_t *d_qual_offsets, uint64_t *d_rec_start, uint64_t max_records,
+                          uint64_t *d_result, void *d_work, size_t work_bytes, polyhip_stream_t stream)
 {
-    PH_REQUIRE(d_result && d_offsets && d_work && (d_file || nbytes == 0) && (d_seqs || nbytes == 0),
-               "polyhip_fastq_pack: null pointer");
-    const fq::Layout L = fq::layout(nbytes);
-    PH_REQUIRE(work_bytes >= L.total, "polyhip_fastq_pack: workspace too small (%zu < %zu)", work_bytes, L.total);
-    PH_REQUIRE(L.nblocks < (1ull << 31), "polyhip_fastq_pack: file too large for one call");
+    PH_REQUIRE(d_result && d_offsets && d_work && (d_file || nbytes == 0) && (d_seqs || nbytes == 0) &&
+                   (!QUAL || (d_qual_offsets && (d_quals || nbytes == 0))),
+               "%s: null pointer", who);
+    const fq::Layout L = QUAL ? fq::layout_qual(nbytes) : fq::layout(nbytes);
+    PH_REQUIRE(work_bytes >= L.total, "%s: workspace too small (%zu < %zu)", who, work_bytes, L.total);
+    PH_REQUIRE(L.nblocks < (1ull << 31), "%s: file too large for one call", who);
     hipStream_t st = as_stream(stream);
     uint8_t *w = static_cast<uint8_t *>(d_work);
     unsigned long long *res = reinterpret_cast<unsigned long long *>(w + L.off_res);
@@ -1061,6 +1101,8 @@ int polyhip_fastq_pack_dev(const uint8_t *d_file, uint64_t nbytes, uint8_t *d_se
     uint64_t *line_end = reinterpret_cast<uint64_t *>(w + L.off_lineend);
     uint32_t *seq_len = reinterpret_cast<uint32_t *>(w + L.off_seqlen);
     uint64_t *seq_start = reinterpret_cast<uint64_t *>(w + L.off_seqstart);
+    uint32_t *qual_len = QUAL ? reinterpret_cast<uint32_t *>(w + L.off_quallen) : nullptr;
+    uint64_t *qual_start = QUAL ? reinterpret_cast<uint64_t *>(w + L.off_qualstart) : nullptr;
 
     PH_HIP(hipMemsetAsync(res, 0, fq::R_WORDS * 8, st));
     PH_HIP(hipMemsetAsync(res + fq::R_FIRSTBAD, 0xFF, 8, st));
@@ -1078,32 +1120,44 @@ int polyhip_fastq_pack_dev(const uint8_t *d_file, uint64_t nbytes, uint8_t *d_se
     // reference reads the third line without looking at it (fastq.go:182), so "@\nA\n\nI\n" parses.
     const uint64_t *nlines_dev = blockoff + L.nblocks;
     const uint64_t most = nbytes / 7 + 1;
-    hipLaunchKernelGGL(fq::records_kernel, dim3((unsigned)std::min<uint64_t>((most + fq::THREADS - 1) / fq::THREADS, 256ull * 16ull)), dim3(fq::THREADS), 0, st,
-                       d_file, line_end, nlines_dev, seq_len, seq_start, d_rec_start, max_records, res);
+    hipLaunchKernelGGL(fq::records_kernel<QUAL>, dim3((unsigned)std::min<uint64_t>((most + fq::THREADS - 1) / fq::THREADS, 256ull * 16ull)), dim3(fq::THREADS), 0, st,
+                       d_file, line_end, nlines_dev, seq_len, seq_start, d_rec_start, max_records, res, qual_len, qual_start);
     if (int rc = scan_u32(seq_len, 0, nlines_dev, 4, most, d_offsets, scanpart, st, max_records))
         return rc;
+    if (QUAL) // the same scan, the same cap: the partial sums of the first one are used up
+        if (int rc = scan_u32(qual_len, 0, nlines_dev, 4, most, d_qual_offsets, scanpart, st, max_records))
+            return rc;
     hipLaunchKernelGGL(fq::finish_kernel, dim3(1), dim3(1), 0, st, d_file, nbytes, line_end, nlines_dev, d_offsets,
-                       max_records, res);
-    hipLaunchKernelGGL(fq::gather_kernel, dim3((unsigned)std::min<uint64_t>(most, 256ull * 32ull)), dim3(fq::THREADS), 0, st,
-                       d_file, seq_start, d_offsets, res, d_seqs);
+                       max_records, res, QUAL ? d_qual_offsets : (const uint64_t *)nullptr);
+    hipLaunchKernelGGL(fq::gather_kernel<QUAL>, dim3((unsigned)std::min<uint64_t>(most, 256ull * 32ull)), dim3(fq::THREADS), 0, st,
+                       d_file, seq_start, d_offsets, res, d_seqs, qual_start, d_qual_offsets, d_quals);
     PH_HIP(hipGetLastError());
     PH_HIP(hipMemcpyAsync(d_result, res, 4 * 8, hipMemcpyDeviceToDevice, st));
+    if (QUAL)
+        PH_HIP(hipMemcpyAsync(d_result + 4, res + fq::R_QUALBYTES, 2 * 8, hipMemcpyDeviceToDevice, st));
     return POLYHIP_OK;
 }
 
-int polyhip_fastq_pack(const uint8_t *file, uint64_t nbytes, uint8_t *seqs, uint64_t *offsets, uint64_t *rec_start,
-                       uint64_t max_records, uint64_t *result)
+template <bool QUAL>
+static int fastq_pack_host(const char *who, const uint8_t *file, uint64_t nbytes, uint8_t *seqs, uint64_t *offsets, uint8_t *quals,
+                           uint64_t *qual_offsets, uint64_t *rec_start, uint64_t max_records, uint64_t *result)
 {
-    PH_REQUIRE(result && offsets && (file || nbytes == 0) && (seqs || nbytes == 0), "polyhip_fastq_pack: null pointer");
+    PH_REQUIRE(result && offsets && (file || nbytes == 0) && (seqs || nbytes == 0) && (!QUAL || (qual_offsets && (quals || nbytes == 0))),
+               "%s: null pointer", who);
     const uint64_t most = nbytes / 7 + 1;
-    DevBuf dfile, dseqs, doffs, drec, dres, dwork;
+    constexpr size_t RW = QUAL ? 6 : 4; // result words
+    DevBuf dfile, dseqs, doffs, dquals, dqoffs, drec, dres, dwork;
     PH_HIP(dfile.alloc(nbytes));
     PH_HIP(dseqs.alloc(nbytes));
     const uint64_t held = std::min(most, max_records); // the caller's offsets / rec_start hold this many records
     PH_HIP(doffs.alloc((held + 1) * 8));
+    if (QUAL) {
+        PH_HIP(dquals.alloc(nbytes));
+        PH_HIP(dqoffs.alloc((held + 1) * 8));
+    }
     PH_HIP(drec.alloc((held + 1) * 8));
-    PH_HIP(dres.alloc(4 * 8));
-    const size_t wb = polyhip_fastq_workspace_bytes(nbytes);
+    PH_HIP(dres.alloc(RW * 8));
+    const size_t wb = QUAL ? fq::layout_qual(nbytes).total : polyhip_fastq_workspace_bytes(nbytes);
     PH_HIP(dwork.alloc(wb));
     // the calling thread's own streams (host_pipeline.h), never the null stream: the parse is one pass over the whole
     // image, so there is nothing to overlap the upload with, but the two result copies travel side by side
@@ -1111,22 +1165,49 @@ int polyhip_fastq_pack(const uint8_t *file, uint64_t nbytes, uint8_t *seqs, uint
     PH_HIP(hs.init());
     if (nbytes)
         PH_HIP(hipMemcpyAsync(dfile.p, file, nbytes, hipMemcpyHostToDevice, hs.s[0]));
-    int rc = polyhip_fastq_pack_dev(dfile.as<uint8_t>(), nbytes, dseqs.as<uint8_t>(), doffs.as<uint64_t>(),
-                                    drec.as<uint64_t>(), max_records, dres.as<uint64_t>(), dwork.p, wb, hs.s[0]);
+    int rc = fastq_pack_run<QUAL>(who, dfile.as<uint8_t>(), nbytes, dseqs.as<uint8_t>(), doffs.as<uint64_t>(), dquals.as<uint8_t>(),
+                                  dqoffs.as<uint64_t>(), drec.as<uint64_t>(), max_records, dres.as<uint64_t>(), dwork.p, wb, hs.s[0]);
     if (rc != POLYHIP_OK) {
         (void)hs.sync_both();
         return rc;
     }
-    PH_HIP(hipMemcpyAsync(result, dres.p, 4 * 8, hipMemcpyDeviceToHost, hs.s[0]));
+    PH_HIP(hipMemcpyAsync(result, dres.p, RW * 8, hipMemcpyDeviceToHost, hs.s[0]));
     PH_HIP(hipStreamSynchronize(hs.s[0]));
     const uint64_t n = result[0];
     PH_HIP(hipMemcpyAsync(offsets, doffs.p, (n + 1) * 8, hipMemcpyDeviceToHost, hs.s[1]));
+    if (QUAL)
+        PH_HIP(hipMemcpyAsync(qual_offsets, dqoffs.p, (n + 1) * 8, hipMemcpyDeviceToHost, hs.s[1]));
     if (rec_start && n)
         PH_HIP(hipMemcpyAsync(rec_start, drec.p, n * 8, hipMemcpyDeviceToHost, hs.s[1]));
     if (result[3])
         PH_HIP(hipMemcpyAsync(seqs, dseqs.p, result[3], hipMemcpyDeviceToHost, hs.s[0]));
+    if (QUAL && result[4])
+        PH_HIP(hipMemcpyAsync(quals, dquals.p, result[4], hipMemcpyDeviceToHost, hs.s[0]));
     PH_HIP(hs.sync_both());
     return POLYHIP_OK;
+}
+
+extern "C" {
+
+int polyhip_fastq_pack_dev(const uint8_t *d_file, uint64_t nbytes, uint8_t *d_seqs, uint64_t *d_offsets,
+                           uint64_t *d_rec_start, uint64_t max_records, uint64_t *d_result, void *d_work,
+                           size_t work_bytes, polyhip_stream_t stream)
+{
+    return fastq_pack_run<false>("polyhip_fastq_pack", d_file, nbytes, d_seqs, d_offsets, nullptr, nullptr, d_rec_start, max_records,
+                                 d_result, d_work, work_bytes, stream);
+}
+
+int polyhip_fastq_pack(const uint8_t *file, uint64_t nbytes, uint8_t *seqs, uint64_t *offsets, uint64_t *rec_start,
+                       uint64_t max_records, uint64_t *result)
+{
+    return fastq_pack_host<false>("polyhip_fastq_pack", file, nbytes, seqs, offsets, nullptr, nullptr, rec_start, max_records, result);
+}
+
+int polyhip_fastq_pack_qual(const uint8_t *file, uint64_t nbytes, uint8_t *seqs, uint64_t *offsets, uint8_t *quals,
+                            uint64_t *qual_offsets, uint64_t *rec_start, uint64_t max_records, uint64_t *result)
+{
+    return fastq_pack_host<true>("polyhip_fastq_pack_qual", file, nbytes, seqs, offsets, quals, qual_offsets, rec_start, max_records,
+                                 result);
 }
 
 size_t polyhip_fasta_workspace_bytes(uint64_t nbytes) { return fq::layout_fasta(nbytes).total; }

@@ -2,8 +2,10 @@
 
 Mirrors the record semantics of io/fastq/fastq.go:84-216 ((*Parser).ParseNext / ParseN): a FASTQ image goes
 in, the packed (bytes, offsets) batch the hot-path kernels consume comes out -- parsed on the device
-(polyhip_fastq_pack*), no per-read host objects.  Identifiers / optionals / quality strings stay in the
-file image; ``rec_start`` lets the host slice them lazily.
+(polyhip_fastq_pack*), no per-read host objects.  Identifiers / optionals stay in the file image; ``rec_start`` lets
+the host slice them lazily.  The quality strings (the Quality field, fastq.go:199) are packed on the device too by the
+``*_qual`` calls (polyhip_fastq_pack_qual): bytes and offsets of their own, since the reference does not require a quality
+to be as long as its sequence; ``pileup.pileup_qual`` takes them as they come.
 """
 from __future__ import annotations
 
@@ -65,3 +67,35 @@ def pack_dev(file_t, seqs_t, offsets_t, rec_start_t, result_t, work_t, max_recor
         file_t.data_ptr(), nbytes, seqs_t.data_ptr(), offsets_t.data_ptr(),
         rec_start_t.data_ptr() if rec_start_t is not None else None, cap, result_t.data_ptr(), work_t.data_ptr(),
         work_t.numel() * work_t.element_size(), _lib.stream_ptr(stream)))
+
+
+def pack_qual(data, max_records: int | None = None, with_mismatch: bool = False):
+    """``pack`` that also packs the qualities: FASTQ bytes -> (seqs, offsets uint64[n+1], quals uint8, qual_offsets
+    uint64[n+1], rec_start uint64[n], error | None).  ``with_mismatch`` appends a seventh item, the call's result[5]: how
+    many of the kept records have a quality of another length than their sequence (``pileup.pileup_qual`` needs 0, and
+    checks it itself when it is handed ``offsets`` beside ``qual_offsets``)."""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8)
+    nbytes = len(buf)
+    most = nbytes // 7 + 1
+    cap = most if max_records is None else min(most, max_records)
+    seqs, quals = np.zeros(max(nbytes, 1), dtype=np.uint8), np.zeros(max(nbytes, 1), dtype=np.uint8)
+    offsets, qual_offsets = np.zeros(most + 2, dtype=np.uint64), np.zeros(most + 2, dtype=np.uint64)
+    rec = np.zeros(most + 1, dtype=np.uint64)
+    result = np.zeros(6, dtype=np.uint64)
+    _lib.check(_lib.lib().polyhip_fastq_pack_qual(buf.ctypes.data if nbytes else None, nbytes, seqs.ctypes.data, offsets.ctypes.data,
+                                                  quals.ctypes.data, qual_offsets.ctypes.data, rec.ctypes.data, cap,
+                                                  result.ctypes.data))
+    n, code, line, total, qtotal, mismatch = (int(x) for x in result)
+    err = FastqError(ERRORS[code].format(line=line)) if code else None
+    out = (seqs[:total], offsets[: n + 1], quals[:qtotal], qual_offsets[: n + 1], rec[:n], err)
+    return out + (mismatch,) if with_mismatch else out
+
+
+def qualities(data) -> list[bytes]:
+    """The Quality field of every record ParseAll would return (raises the parse error, if any, after them)."""
+    _, _, quals, qoffs, _, err = pack_qual(data)
+    out = [quals[int(qoffs[i]): int(qoffs[i + 1])].tobytes() for i in range(len(qoffs) - 1)]
+    if err is not None:
+        raise err
+    return out
+

@@ -2,8 +2,11 @@
 
 The definition is the comment above ``polyhip_pileup`` in include/polyhip.h and tests/pileup_oracle.py restates it on the
 CPU.  Everything is counted in HIP from the arrays a ``mapper.MapResult`` holds and the text the reads were mapped to;
-nothing is computed here.  Integer counts only: no base qualities, no inserted sequences (hence no VCF indel records), no
-samtools text rows, one text.
+nothing is computed here.  Integer counts only: no inserted sequences (hence no VCF indel records), no samtools text rows,
+one text.  ``pileup`` / ``pileup_packed`` / ``pileup_refs`` do not look at base qualities; the ``*_qual`` calls
+(polyhip_pileup_qual, restated in tests/pileup_qual_oracle.py) take the reads' quality strings as ``fastq.pack_qual`` packs
+them, count a base only when its quality reaches ``min_base_qual`` and add ``qsum``, the sum of the counted qualities per
+base and strand.
 """
 from __future__ import annotations
 
@@ -111,6 +114,43 @@ def pileup_packed(flags, ref_start, ref_end, alnA, alnB, aln_off, ref, mapq=None
     return Pileup(counts, consensus, sites[:int(nsites.value)], err, int(nsites.value), lo, int(rc))
 
 
+def _joined(result):
+    """the strings of a MapResult as polyhip_pileup takes them: alnA, alnB back to back and their offsets"""
+    a, b = b"".join(result.alignA), b"".join(result.alignB)
+    off = np.zeros(len(result.alignA) + 1, np.uint64)
+    off[1:] = np.cumsum([len(s) for s in result.alignA], dtype=np.uint64)
+    return np.frombuffer(a, np.uint8), np.frombuffer(b, np.uint8), off
+
+
+def _on_contig(who: str, result, refs, contig: int, region):
+    """one contig of a RefSet as a region of the set's concatenated text -> (flags, ref_start, ref_end, region, base, lo):
+    every entry moved to ``ref_start + starts[rid]``, entries of other contigs passed as unmapped"""
+    if result.alignA is None or result.alignB is None:
+        raise ValueError(f"pileup.{who}: the MapResult holds no strings")
+    if result.rid is None:
+        raise ValueError(f"pileup.{who}: the MapResult holds no contigs (it is not the result of a refs call)")
+    c = int(contig)
+    if not 0 <= c < len(refs):
+        raise ValueError(f"pileup.{who}: contig {c} of {len(refs)}")
+    base, length = int(refs.starts[c]), int(refs.lengths[c])
+    lo, hi = (0, length) if region is None else (int(region[0]), int(region[1]))
+    if not 0 <= lo <= hi <= length:
+        raise ValueError(f"pileup.{who}: region [{lo}, {hi}) is not inside the contig of {length} bytes")
+    here = np.asarray(result.rid) == c
+    shift = refs.starts[np.asarray(result.rid, dtype=np.int64)]
+    flags = np.where(here, result.flags, 0).astype(np.uint32)
+    return (flags, (result.ref_start + shift).astype(np.uint32), (result.ref_end + shift).astype(np.uint32), (base + lo, base + hi), base,
+            lo)
+
+
+def _local(out, base: int, lo: int):
+    """a pileup of the concatenation back in the contig's own positions"""
+    out.region_lo = lo
+    if out.sites is not None:
+        out.sites["pos"] -= np.uint32(base)
+    return out
+
+
 def pileup(result, ref, records=None, region=None, min_mapq: int = 0, min_depth: int = 1, min_alt_count: int = 1,
            min_alt_permille: int = 0, site_capacity: int | None = None) -> Pileup:
     """The pileup of a ``mapper.MapResult`` that holds its strings on the text ``ref`` it was mapped to.  ``records``: the
@@ -118,14 +158,11 @@ def pileup(result, ref, records=None, region=None, min_mapq: int = 0, min_depth:
     be 0)."""
     if result.alignA is None or result.alignB is None:
         raise ValueError("pileup.pileup: the MapResult holds no strings")
-    a, b = b"".join(result.alignA), b"".join(result.alignB)
-    off = np.zeros(len(result.alignA) + 1, np.uint64)
-    off[1:] = np.cumsum([len(s) for s in result.alignA], dtype=np.uint64)
+    a, b, off = _joined(result)
     if isinstance(ref, str):
         ref = ref.encode("latin-1")
-    return pileup_packed(result.flags, result.ref_start, result.ref_end, np.frombuffer(a, np.uint8), np.frombuffer(b, np.uint8), off,
-                         ref, None if records is None else records.mapq, region, min_mapq, min_depth, min_alt_count,
-                         min_alt_permille, site_capacity)
+    return pileup_packed(result.flags, result.ref_start, result.ref_end, a, b, off, ref, None if records is None else records.mapq,
+                         region, min_mapq, min_depth, min_alt_count, min_alt_permille, site_capacity)
 
 
 def pileup_refs(result, refs, contig: int, records=None, region=None, min_mapq: int = 0, min_depth: int = 1,
@@ -136,28 +173,125 @@ def pileup_refs(result, refs, contig: int, records=None, region=None, min_mapq: 
     to ``ref_start + starts[rid]`` and the region to ``[starts[contig] + lo, starts[contig] + hi)``; entries of other contigs
     are passed as unmapped.  No alignment crosses a contig, so nothing else is needed.  The Pileup that comes back is local
     to the contig: ``region_lo`` and the sites' ``pos`` are positions in it."""
+    flags, ref_start, ref_end, where, base, lo = _on_contig("pileup_refs", result, refs, contig, region)
+    a, b, off = _joined(result)
+    out = pileup_packed(flags, ref_start, ref_end, a, b, off, refs.text(), None if records is None else records.mapq, where, min_mapq,
+                        min_depth, min_alt_count, min_alt_permille, site_capacity)
+    return _local(out, base, lo)
+
+
+# ---- with base qualities (polyhip_pileup_qual) ----------------------------------------------------------------------------------
+QSUM_PLANES = 8
+
+
+class _CQualParams(C.Structure):
+    _fields_ = [("base", _CParams), ("min_base_qual", C.c_uint32), ("qual_offset", C.c_uint32)]
+
+
+class _CQualInfo(C.Structure):
+    _fields_ = _CInfo._fields_ + [("filtered_bases", C.c_uint64)]
+
+
+def last_qual_info() -> dict:
+    """polyhip_pileup_qual_last_info: what the calling thread's last ``*_qual`` call did"""
+    info = _CQualInfo()
+    _lib.check(_lib.lib().polyhip_pileup_qual_last_info(C.byref(info)))
+    return {name: int(getattr(info, name)) for name, _ in _CQualInfo._fields_}
+
+
+@dataclass
+class PileupQual(Pileup):
+    """``Pileup`` of the bases whose quality reached ``min_base_qual``, plus ``qsum[4 * strand + k, p - region_lo]``: the sum of
+    the qualities of the counted bases k = 0..3 (A, C, G, T) at p.  Deleted bases and the events are not filtered."""
+    qsum: np.ndarray | None = None
+
+    last_info = staticmethod(last_qual_info)
+
+
+def pileup_qual_packed(flags, ref_start, ref_end, read_start, alnA, alnB, aln_off, qual, qual_off, ref, mapq=None, region=None,
+                       min_mapq: int = 0, min_depth: int = 1, min_alt_count: int = 1, min_alt_permille: int = 0,
+                       site_capacity: int | None = None, min_base_qual: int = 0, qual_offset: int = 33) -> PileupQual:
+    """polyhip_pileup_qual on packed arrays: ``pileup_packed`` plus ``read_start`` (of the mapper's result), the quality
+    strings ``qual`` / ``qual_off`` of the reads as sequenced, one per entry, and the two quality settings."""
+    n = len(flags)
+    flags, ref_start, ref_end, read_start = (np.ascontiguousarray(x, dtype=np.uint32) for x in (flags, ref_start, ref_end, read_start))
+    alnA, alnB, qual = (np.ascontiguousarray(x, dtype=np.uint8) for x in (alnA, alnB, qual))
+    aln_off, qual_off = (np.ascontiguousarray(x, dtype=np.uint64) for x in (aln_off, qual_off))
+    ref = np.ascontiguousarray(np.frombuffer(ref, np.uint8) if isinstance(ref, (bytes, bytearray)) else ref, dtype=np.uint8)
+    if mapq is not None:
+        mapq = np.ascontiguousarray(mapq, dtype=np.uint8)
+        if len(mapq) != n:
+            raise ValueError("pileup_qual_packed: the arrays hold different numbers of entries")
+    if not (len(ref_start) == len(ref_end) == len(read_start) == n and len(aln_off) == len(qual_off) == n + 1):
+        raise ValueError("pileup_qual_packed: the arrays hold different numbers of entries")
+    if n and (int(aln_off[n]) > min(len(alnA), len(alnB)) or int(qual_off[n]) > len(qual)):
+        raise ValueError("pileup_qual_packed: the offsets reach beyond the strings")
+    lo, hi = (0, len(ref)) if region is None else (int(region[0]), int(region[1]))
+    p = _CQualParams(_CParams(lo, hi, int(min_mapq), int(min_depth), int(min_alt_count), int(min_alt_permille)), int(min_base_qual),
+                     int(qual_offset))
+    L = max(hi - lo, 0) if hi <= len(ref) else 0         # a region the library refuses: it says so, nothing is sized by it
+    fixed = site_capacity is not None
+    cap = int(site_capacity) if fixed else L // 64 + 1024
+    counts, qsum, consensus = np.zeros((CHANNELS, L), np.uint32), np.zeros((QSUM_PLANES, L), np.uint32), np.zeros(L, np.uint8)
+    err, nsites = np.zeros(n, np.uint32), C.c_uint64(0)
+    ref_buf = ref if len(ref) else np.zeros(1, np.uint8)       # ref is always required, an empty text too
+    sites = None
+    rc = _lib.OK
+    for _ in range(2):
+        sites = np.zeros(max(cap, 1), SITE_DTYPE)
+        rc = _lib.lib().polyhip_pileup_qual(C.byref(p), n, flags.ctypes.data, None if mapq is None else mapq.ctypes.data,
+                                            ref_start.ctypes.data, ref_end.ctypes.data, read_start.ctypes.data, alnA.ctypes.data,
+                                            alnB.ctypes.data, aln_off.ctypes.data, qual.ctypes.data, qual_off.ctypes.data,
+                                            ref_buf.ctypes.data, len(ref), counts.ctypes.data, qsum.ctypes.data, consensus.ctypes.data,
+                                            C.byref(nsites), sites.ctypes.data, cap, err.ctypes.data)
+        if rc == _lib.ERR_INVALID and _sites_short():       # nsites says what the sites need
+            if fixed:
+                return PileupQual(counts, consensus, None, err, int(nsites.value), lo, int(rc), qsum)
+            cap = int(nsites.value)
+            continue
+        _lib.check(rc)
+        break
+    return PileupQual(counts, consensus, sites[:int(nsites.value)], err, int(nsites.value), lo, int(rc), qsum)
+
+
+def _same_lengths(who: str, read_offsets, qual_offsets):
+    """a quality longer than its read raises no err in the library (it reads as a clip): caught here when the caller hands
+    the reads' offsets in"""
+    if read_offsets is None:
+        return
+    r, q = np.asarray(read_offsets, dtype=np.uint64), np.asarray(qual_offsets, dtype=np.uint64)
+    if len(r) != len(q) or (np.diff(r) != np.diff(q)).any():
+        raise ValueError(f"pileup.{who}: some quality string is not as long as its read (fastq.pack_qual's mismatch count is not 0)")
+
+
+def pileup_qual(result, ref, quals, qual_offsets, records=None, region=None, min_mapq: int = 0, min_depth: int = 1,
+                min_alt_count: int = 1, min_alt_permille: int = 0, site_capacity: int | None = None, min_base_qual: int = 0,
+                qual_offset: int = 33, read_offsets=None) -> PileupQual:
+    """``pileup`` with the base qualities: ``quals`` / ``qual_offsets`` as ``fastq.pack_qual`` returns them for the reads the
+    result was mapped from (every quality as long as its read), in the result's entry order -- for a paired result the
+    mates' strings interleaved, 2i and 2i + 1.  ``read_offsets``: the offsets of those reads (``fastq.pack_qual``'s
+    ``offsets``); when given, a quality of another length than its read is a ValueError instead of bases silently paired
+    with the wrong bytes."""
     if result.alignA is None or result.alignB is None:
-        raise ValueError("pileup.pileup_refs: the MapResult holds no strings")
-    if result.rid is None:
-        raise ValueError("pileup.pileup_refs: the MapResult holds no contigs (it is not the result of a refs call)")
-    c = int(contig)
-    if not 0 <= c < len(refs):
-        raise ValueError(f"pileup.pileup_refs: contig {c} of {len(refs)}")
-    base, length = int(refs.starts[c]), int(refs.lengths[c])
-    lo, hi = (0, length) if region is None else (int(region[0]), int(region[1]))
-    if not 0 <= lo <= hi <= length:
-        raise ValueError(f"pileup.pileup_refs: region [{lo}, {hi}) is not inside the contig of {length} bytes")
-    a, b = b"".join(result.alignA), b"".join(result.alignB)
-    off = np.zeros(len(result.alignA) + 1, np.uint64)
-    off[1:] = np.cumsum([len(s) for s in result.alignA], dtype=np.uint64)
-    ref = refs.text()
-    here = np.asarray(result.rid) == c
-    shift = refs.starts[np.asarray(result.rid, dtype=np.int64)]
-    flags = np.where(here, result.flags, 0).astype(np.uint32)
-    out = pileup_packed(flags, (result.ref_start + shift).astype(np.uint32), (result.ref_end + shift).astype(np.uint32),
-                        np.frombuffer(a, np.uint8), np.frombuffer(b, np.uint8), off, ref, None if records is None else records.mapq,
-                        (base + lo, base + hi), min_mapq, min_depth, min_alt_count, min_alt_permille, site_capacity)
-    out.region_lo = lo
-    if out.sites is not None:
-        out.sites["pos"] -= np.uint32(base)
-    return out
+        raise ValueError("pileup.pileup_qual: the MapResult holds no strings")
+    _same_lengths("pileup_qual", read_offsets, qual_offsets)
+    a, b, off = _joined(result)
+    if isinstance(ref, str):
+        ref = ref.encode("latin-1")
+    return pileup_qual_packed(result.flags, result.ref_start, result.ref_end, result.read_start, a, b, off, quals, qual_offsets, ref,
+                              None if records is None else records.mapq, region, min_mapq, min_depth, min_alt_count, min_alt_permille,
+                              site_capacity, min_base_qual, qual_offset)
+
+
+def pileup_qual_refs(result, refs, contig: int, quals, qual_offsets, records=None, region=None, min_mapq: int = 0, min_depth: int = 1,
+                     min_alt_count: int = 1, min_alt_permille: int = 0, site_capacity: int | None = None, min_base_qual: int = 0,
+                     qual_offset: int = 33, read_offsets=None) -> PileupQual:
+    """``pileup_refs`` with the base qualities: one contig of a ``refs.RefSet``, moved to the set's concatenated text and back
+    exactly as ``pileup_refs`` does it.  ``read_offsets`` as in ``pileup_qual``."""
+    flags, ref_start, ref_end, where, base, lo = _on_contig("pileup_qual_refs", result, refs, contig, region)
+    _same_lengths("pileup_qual_refs", read_offsets, qual_offsets)
+    a, b, off = _joined(result)
+    out = pileup_qual_packed(flags, ref_start, ref_end, result.read_start, a, b, off, quals, qual_offsets, refs.text(),
+                             None if records is None else records.mapq, where, min_mapq, min_depth, min_alt_count, min_alt_permille,
+                             site_capacity, min_base_qual, qual_offset)
+    return _local(out, base, lo)
