@@ -1345,6 +1345,77 @@ int polyhip_pileup_qual(const polyhip_pileup_qual_params *params, uint64_t n, co
                         uint64_t site_capacity, uint32_t *err);
 int polyhip_pileup_qual_last_info(polyhip_pileup_qual_info *info);
 
+/* ---- duplicate marking and coordinate order of the mapper's output (no counterpart in the reference) ---- */
+/*
+ * polyhip_mark_duplicates marks, among the n entries that polyhip_map_reads, polyhip_map_reads_affine, polyhip_map_pairs or
+ * their _refs forms returned, the copies of one template molecule: entries (or pairs) whose unclipped 5' ends coincide.  It
+ * is a pass over those arrays: it places nothing and needs neither a text nor an index.  Nothing is removed; the caller
+ * clears flags bit 0 of the entries with dup = 1 before a pileup, or writes 0x400 into their SAM FLAG.
+ *  err[i], the first that applies, for entries with flags bit 0 (mapped) only; an unmapped entry gets 0 and its other arrays
+ *   are not judged:  2 = read_start > read_end, or read_end > read_len, or ref_start > ref_end;  6 = (weight_mode 1) the
+ *   length of the quality string, qualOff[i + 1] - qualOff[i], differs from read_len[i];  7 = (weight_mode 1) a byte of the
+ *   quality string is below qual_offset or above qual_offset + 93.
+ *  Candidate: flags bit 0 is set and err[i] == 0.
+ *  Weight: w[i] = weight[i] with weight_mode 0 (0 when weight == NULL); with weight_mode 1 the sum of Q = byte - qual_offset
+ *   over the WHOLE quality string of the entry, clipped parts included, counting only Q >= min_weight_qual; it is computed
+ *   on the device.  weight_out (may be NULL) receives w[i], and 0 for entries that are not candidates.
+ *  End key: with s = flags bit 1 (reverse) and in signed 64-bit integers, u = ref_start - read_start on the forward strand
+ *   and u = ref_end - 1 + (read_len - read_end) on the reverse strand: the text position of the read's 5' end with the clips
+ *   added back (coordinates are those of the oriented read, as the mapper reports them; u may be negative).  E(i) = (rid[i],
+ *   u, s), compared lexicographically; rid == NULL means 0 everywhere.
+ *  Fragments: with paired == 0 every candidate; with paired == 1 a candidate whose mate i ^ 1 is not a candidate.
+ *  Pairs: with paired == 1, pair p = entries 2p, 2p + 1 when both are candidates.  Its lo mate is the one with the smaller
+ *   (E, index), the other its hi mate, and its key is (E_lo, E_hi): which mate was read 1 is NOT part of the key (Picard's
+ *   convention: the orientation is that of the leftmost end).  W(p) = w[2p] + w[2p + 1] in uint64.
+ *  Pair sets: all pairs with equal keys.  The representative is the pair of greatest W, ties to the lowest p.  Every other
+ *   pair of the set is a duplicate: both its mates get dup = 1, rep[lo mate] = the representative's lo mate and rep[hi mate]
+ *   = its hi mate.
+ *  End sets: all candidates with equal E, pair mates included whether or not their pair is a duplicate.  Ordered by (is a
+ *   fragment, w descending, index ascending), the first element is the head.  Every fragment of the set other than the head
+ *   gets dup = 1 and rep = the head, so a fragment always loses to any pair mate at the same end (as in Picard and
+ *   samtools) and among fragments alone the greatest weight wins.  Pair mates are not changed by end sets.
+ *  Every other entry gets dup = 0 and rep = i.
+ * All comparisons are on integers and ties go by index, so the result does not depend on the order in which the device
+ * gets to the entries.
+ * Errors, in this order, all before anything that depends on n is allocated: a NULL params (POLYHIP_ERR_INVALID); paired >
+ * 1, weight_mode > 1, min_weight_qual > 93 or qual_offset > 162 (_INVALID, naming the field); paired != 0 with an odd n
+ * (_INVALID); n >= 2^32 (POLYHIP_ERR_UNSUPPORTED: the sort's values are uint32); with n > 0 a NULL array that is needed
+ * (_INVALID: flags, ref_start, ref_end, read_start, read_end, read_len, dup, rep and err always; rid, weight and weight_out
+ * never; qualOff with weight_mode 1, and qual unless qualOff[n] == qualOff[0]); with weight_mode 1 qualOff not ascending
+ * (_INVALID), then some read_len[i] * 93 >= 2^32 (_UNSUPPORTED: a weight is uint32).  n == 0 is an empty, successful call.
+ * Host pointers only, no stream: the call copies the arrays in (of qual only [qualOff[0], qualOff[n])), runs on the calling
+ * thread's current device and copies the results out; the device list does not apply.
+ * polyhip_dedup_last_info: the calling thread's last call: entries = n; candidates; bad = entries with err != 0; pairs and
+ * fragments = the pairs and the fragment entries; dup_pairs = duplicate pairs (not mates); dup_fragments = duplicate
+ * fragment entries; pair_sets and end_sets = the numbers of distinct keys.
+ *
+ * polyhip_coord_order: order[0..n) is the stable permutation that puts the entries into SAM's coordinate order.  An entry
+ * is live when sam_flag[i] (of polyhip_aln_records) lacks 0x4; its place is (rid[i], ref_start[i]).  With paired != 0 an
+ * entry that is not live and has a live mate i ^ 1 takes the mate's place, as a SAM writer gives it the mate's RNAME and
+ * POS.  Every other entry is unplaced and sorts after all placed ones.  Ties, and the unplaced entries, go in index order.
+ * rid == NULL means 0.  Errors, in this order: paired > 1 (_INVALID); paired != 0 with an odd n (_INVALID); n >= 2^32
+ * (_UNSUPPORTED); with n > 0 a NULL sam_flag, ref_start or order (_INVALID).  n == 0 is an empty, successful call.  The
+ * calling convention is polyhip_mark_duplicates'.
+ */
+typedef struct polyhip_dedup_params {
+    uint32_t paired;           /* 0: every entry is a read of its own; 1: mates in the order 2i, 2i + 1 */
+    uint32_t weight_mode;      /* 0: weight[] is the caller's (NULL = all 0); 1: computed from qual */
+    uint32_t min_weight_qual;  /* weight_mode 1: a base adds Q to the weight only if Q >= this; 0..93 (Picard uses 15) */
+    uint32_t qual_offset;      /* as polyhip_pileup_qual: <= 162 */
+} polyhip_dedup_params;
+typedef struct polyhip_dedup_info {
+    uint64_t entries, candidates, bad, pairs, fragments, dup_pairs, dup_fragments, pair_sets, end_sets;
+} polyhip_dedup_info;
+int polyhip_mark_duplicates(const polyhip_dedup_params *params, uint64_t n, const uint32_t *flags,
+                            const uint32_t *rid, const uint32_t *ref_start, const uint32_t *ref_end,
+                            const uint32_t *read_start, const uint32_t *read_end,
+                            const uint32_t *read_len, const uint32_t *weight, const uint8_t *qual,
+                            const uint64_t *qualOff, uint32_t *weight_out, uint8_t *dup,
+                            uint32_t *rep, uint32_t *err);
+int polyhip_dedup_last_info(polyhip_dedup_info *info);
+int polyhip_coord_order(uint64_t n, uint32_t paired, const uint32_t *sam_flag, const uint32_t *rid,
+                        const uint32_t *ref_start, uint32_t *order);
+
 /* ---- R1: the path's one collective -- all-gather of per-rank sketches (RCCL over xGMI) ---- */
 /*
  * For hosts without torch.distributed (the Go/cgo drop-in); one process per GPU.  RCCL is

@@ -70,12 +70,24 @@ def _sites_short() -> bool:
     return b"the sites need" in _lib.lib().polyhip_last_error()
 
 
+def _without(flags, dup):
+    """the flags with bit 0 (mapped) cleared, in a copy, where ``dup`` is set: the pileup then leaves the duplicates out"""
+    if dup is None:
+        return flags
+    flags, dup = np.asarray(flags, dtype=np.uint32), np.asarray(dup)
+    if len(dup) != len(flags):
+        raise ValueError("pileup: dup holds another number of entries than the result")
+    return np.where(dup != 0, flags & ~np.uint32(1), flags).astype(np.uint32)
+
+
 def pileup_packed(flags, ref_start, ref_end, alnA, alnB, aln_off, ref, mapq=None, region=None, min_mapq: int = 0, min_depth: int = 1,
-                  min_alt_count: int = 1, min_alt_permille: int = 0, site_capacity: int | None = None) -> Pileup:
+                  min_alt_count: int = 1, min_alt_permille: int = 0, site_capacity: int | None = None, dup=None) -> Pileup:
     """polyhip_pileup on packed arrays.  ``region``: (lo, hi) text positions, the whole text by default.  The site capacity
     defaults to a guess; a call that needs more is run again with the exact size -- unless a capacity was given, in which
-    case the result carries ``status`` = ERR_INVALID, ``nsites``, and no ``sites``."""
+    case the result carries ``status`` = ERR_INVALID, ``nsites``, and no ``sites``.  ``dup``: ``dedup.Duplicates.dup``; its
+    entries are passed as unmapped."""
     n = len(flags)
+    flags = _without(flags, dup)
     flags, ref_start, ref_end = (np.ascontiguousarray(x, dtype=np.uint32) for x in (flags, ref_start, ref_end))
     alnA, alnB = (np.ascontiguousarray(x, dtype=np.uint8) for x in (alnA, alnB))
     aln_off = np.ascontiguousarray(aln_off, dtype=np.uint64)
@@ -152,7 +164,7 @@ def _local(out, base: int, lo: int):
 
 
 def pileup(result, ref, records=None, region=None, min_mapq: int = 0, min_depth: int = 1, min_alt_count: int = 1,
-           min_alt_permille: int = 0, site_capacity: int | None = None) -> Pileup:
+           min_alt_permille: int = 0, site_capacity: int | None = None, dup=None) -> Pileup:
     """The pileup of a ``mapper.MapResult`` that holds its strings on the text ``ref`` it was mapped to.  ``records``: the
     ``sam.AlnRecords`` of the same result; its ``mapq`` is what ``min_mapq`` is compared with (without one, ``min_mapq`` must
     be 0)."""
@@ -162,11 +174,11 @@ def pileup(result, ref, records=None, region=None, min_mapq: int = 0, min_depth:
     if isinstance(ref, str):
         ref = ref.encode("latin-1")
     return pileup_packed(result.flags, result.ref_start, result.ref_end, a, b, off, ref, None if records is None else records.mapq,
-                         region, min_mapq, min_depth, min_alt_count, min_alt_permille, site_capacity)
+                         region, min_mapq, min_depth, min_alt_count, min_alt_permille, site_capacity, dup)
 
 
 def pileup_refs(result, refs, contig: int, records=None, region=None, min_mapq: int = 0, min_depth: int = 1,
-                min_alt_count: int = 1, min_alt_permille: int = 0, site_capacity: int | None = None) -> Pileup:
+                min_alt_count: int = 1, min_alt_permille: int = 0, site_capacity: int | None = None, dup=None) -> Pileup:
     """The pileup of one contig of a ``refs.RefSet`` from the result of ``mapper.map_reads_refs_packed`` /
     ``map_pairs_refs_packed`` on that set.  ``region``: (lo, hi) inside the contig, the whole contig by default.
     polyhip_pileup runs on the set's concatenated text (``refs.text()``, read back from the index) with every entry moved
@@ -176,7 +188,7 @@ def pileup_refs(result, refs, contig: int, records=None, region=None, min_mapq: 
     flags, ref_start, ref_end, where, base, lo = _on_contig("pileup_refs", result, refs, contig, region)
     a, b, off = _joined(result)
     out = pileup_packed(flags, ref_start, ref_end, a, b, off, refs.text(), None if records is None else records.mapq, where, min_mapq,
-                        min_depth, min_alt_count, min_alt_permille, site_capacity)
+                        min_depth, min_alt_count, min_alt_permille, site_capacity, dup)
     return _local(out, base, lo)
 
 
@@ -210,10 +222,11 @@ class PileupQual(Pileup):
 
 def pileup_qual_packed(flags, ref_start, ref_end, read_start, alnA, alnB, aln_off, qual, qual_off, ref, mapq=None, region=None,
                        min_mapq: int = 0, min_depth: int = 1, min_alt_count: int = 1, min_alt_permille: int = 0,
-                       site_capacity: int | None = None, min_base_qual: int = 0, qual_offset: int = 33) -> PileupQual:
+                       site_capacity: int | None = None, min_base_qual: int = 0, qual_offset: int = 33, dup=None) -> PileupQual:
     """polyhip_pileup_qual on packed arrays: ``pileup_packed`` plus ``read_start`` (of the mapper's result), the quality
     strings ``qual`` / ``qual_off`` of the reads as sequenced, one per entry, and the two quality settings."""
     n = len(flags)
+    flags = _without(flags, dup)
     flags, ref_start, ref_end, read_start = (np.ascontiguousarray(x, dtype=np.uint32) for x in (flags, ref_start, ref_end, read_start))
     alnA, alnB, qual = (np.ascontiguousarray(x, dtype=np.uint8) for x in (alnA, alnB, qual))
     aln_off, qual_off = (np.ascontiguousarray(x, dtype=np.uint64) for x in (aln_off, qual_off))
@@ -266,7 +279,7 @@ def _same_lengths(who: str, read_offsets, qual_offsets):
 
 def pileup_qual(result, ref, quals, qual_offsets, records=None, region=None, min_mapq: int = 0, min_depth: int = 1,
                 min_alt_count: int = 1, min_alt_permille: int = 0, site_capacity: int | None = None, min_base_qual: int = 0,
-                qual_offset: int = 33, read_offsets=None) -> PileupQual:
+                qual_offset: int = 33, read_offsets=None, dup=None) -> PileupQual:
     """``pileup`` with the base qualities: ``quals`` / ``qual_offsets`` as ``fastq.pack_qual`` returns them for the reads the
     result was mapped from (every quality as long as its read), in the result's entry order -- for a paired result the
     mates' strings interleaved, 2i and 2i + 1.  ``read_offsets``: the offsets of those reads (``fastq.pack_qual``'s
@@ -280,12 +293,12 @@ def pileup_qual(result, ref, quals, qual_offsets, records=None, region=None, min
         ref = ref.encode("latin-1")
     return pileup_qual_packed(result.flags, result.ref_start, result.ref_end, result.read_start, a, b, off, quals, qual_offsets, ref,
                               None if records is None else records.mapq, region, min_mapq, min_depth, min_alt_count, min_alt_permille,
-                              site_capacity, min_base_qual, qual_offset)
+                              site_capacity, min_base_qual, qual_offset, dup)
 
 
 def pileup_qual_refs(result, refs, contig: int, quals, qual_offsets, records=None, region=None, min_mapq: int = 0, min_depth: int = 1,
                      min_alt_count: int = 1, min_alt_permille: int = 0, site_capacity: int | None = None, min_base_qual: int = 0,
-                     qual_offset: int = 33, read_offsets=None) -> PileupQual:
+                     qual_offset: int = 33, read_offsets=None, dup=None) -> PileupQual:
     """``pileup_refs`` with the base qualities: one contig of a ``refs.RefSet``, moved to the set's concatenated text and back
     exactly as ``pileup_refs`` does it.  ``read_offsets`` as in ``pileup_qual``."""
     flags, ref_start, ref_end, where, base, lo = _on_contig("pileup_qual_refs", result, refs, contig, region)
@@ -293,5 +306,5 @@ def pileup_qual_refs(result, refs, contig: int, quals, qual_offsets, records=Non
     a, b, off = _joined(result)
     out = pileup_qual_packed(flags, ref_start, ref_end, result.read_start, a, b, off, quals, qual_offsets, refs.text(),
                              None if records is None else records.mapq, where, min_mapq, min_depth, min_alt_count, min_alt_permille,
-                             site_capacity, min_base_qual, qual_offset)
+                             site_capacity, min_base_qual, qual_offset, dup)
     return _local(out, base, lo)

@@ -20,6 +20,7 @@ from .pcr import _revcomp
 CIGAR_OPS = "MIDNSHP=X"
 FLAG_PAIRED, FLAG_PROPER, FLAG_UNMAPPED, FLAG_MATE_UNMAPPED, FLAG_REVERSE, FLAG_MATE_REVERSE, FLAG_FIRST, FLAG_LAST = \
     0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40, 0x80
+FLAG_DUPLICATE = 0x400
 
 
 class _CParams(C.Structure):
@@ -126,19 +127,36 @@ def _text(x) -> str:
     return x if isinstance(x, str) else bytes(x).decode("latin-1")
 
 
-def write(fh, ref_name: str, ref_len: int, names, reads, quals, result, records: AlnRecords, paired: bool = False) -> None:
+def _so(order) -> str:
+    return "unsorted" if order is None else "coordinate"
+
+
+def _entries(n: int, order):
+    """the entries in the order they are written: the result's, or ``order`` (a permutation of all of them)"""
+    if order is None:
+        return range(n)
+    order = [int(i) for i in order]
+    if sorted(order) != list(range(n)):
+        raise ValueError("sam.write: order is not a permutation of the entries")
+    return order
+
+
+def write(fh, ref_name: str, ref_len: int, names, reads, quals, result, records: AlnRecords, paired: bool = False, order=None,
+          dup=None) -> None:
     """SAM text on ``fh`` (a text file): an @HD and an @SQ line, then one line of 11 fields per entry, with NM:i, MD:Z and AS:i
     on the live ones.  ``names``, ``reads`` and ``quals`` (or None: '*') have one item per entry, ``str`` or ``bytes``; for
     pairs that is the result's order 2i, 2i + 1, and ``records`` was made with ``paired=True``.  One reference only: RNAME is
     ``ref_name``.  A live entry on the reverse strand is written as the mapper placed it: SEQ is the reverse complement
     (bytes the complement table lacks become N), QUAL is reversed.  An entry that is not live is written unmapped; with
     ``paired`` it takes RNAME / POS of a live mate.  RNEXT is '=', PNEXT the mate's POS and TLEN +/- ``result.tlen`` (plus on
-    the mate with the smaller ref_start, ties to mate 1) when the mate is live; TLEN is 0 unless both are."""
+    the mate with the smaller ref_start, ties to mate 1) when the mate is live; TLEN is 0 unless both are.  ``order``: the
+    permutation of ``dedup.coord_order``; the header then says SO:coordinate and the lines go out in that order.  ``dup``:
+    ``dedup.Duplicates.dup``; 0x400 is set in the FLAG of its entries."""
     n = len(records.sam_flag)
-    fh.write(f"@HD\tVN:1.6\tSO:unsorted\n@SQ\tSN:{ref_name}\tLN:{int(ref_len)}\n")
+    fh.write(f"@HD\tVN:1.6\tSO:{_so(order)}\n@SQ\tSN:{ref_name}\tLN:{int(ref_len)}\n")
     live = (records.sam_flag & FLAG_UNMAPPED) == 0
-    for i in range(n):
-        flag = int(records.sam_flag[i])
+    for i in _entries(n, order):
+        flag = int(records.sam_flag[i]) | (FLAG_DUPLICATE if dup is not None and dup[i] else 0)
         rname, pos, mapq, cigar = "*", 0, 0, "*"
         if live[i]:
             rname, pos, mapq, cigar = ref_name, int(result.ref_start[i]) + 1, int(records.mapq[i]), records.cigar_string(i)
@@ -163,19 +181,19 @@ def write(fh, ref_name: str, ref_len: int, names, reads, quals, result, records:
         fh.write("\t".join(fields) + "\n")
 
 
-def write_refs(fh, refs, names, reads, quals, result, records: AlnRecords, paired: bool = False) -> None:
+def write_refs(fh, refs, names, reads, quals, result, records: AlnRecords, paired: bool = False, order=None, dup=None) -> None:
     """``write`` for the result of ``mapper.map_reads_refs_packed`` / ``map_pairs_refs_packed`` on the ``refs.RefSet`` it was
     mapped to: one @SQ line per contig, in the set's order; RNAME is the name of ``result.rid[i]``'s contig and POS a position
     in it.  With ``paired``: RNEXT is '=' when the live mate is on the same contig (an entry that is not live takes its live
     mate's RNAME and POS, so '=' too), else the mate's contig name; TLEN is 0 unless both mates are live on one contig.
-    Everything else is ``write``'s."""
+    Everything else is ``write``'s, ``order`` and ``dup`` included."""
     n = len(records.sam_flag)
-    fh.write("@HD\tVN:1.6\tSO:unsorted\n")
+    fh.write(f"@HD\tVN:1.6\tSO:{_so(order)}\n")
     for name, length in zip(refs.names, refs.lengths):
         fh.write(f"@SQ\tSN:{name}\tLN:{int(length)}\n")
     live = (records.sam_flag & FLAG_UNMAPPED) == 0
-    for i in range(n):
-        flag = int(records.sam_flag[i])
+    for i in _entries(n, order):
+        flag = int(records.sam_flag[i]) | (FLAG_DUPLICATE if dup is not None and dup[i] else 0)
         rname, pos, mapq, cigar = "*", 0, 0, "*"
         if live[i]:
             rname, pos, mapq, cigar = refs.names[int(result.rid[i])], int(result.ref_start[i]) + 1, int(records.mapq[i]), \
