@@ -207,3 +207,115 @@ func LastPileupQualInfo() (PileupQualInfo, error) {
 		Bad: uint64(ci.bad), Columns: uint64(ci.columns), EdgeEvents: uint64(ci.edge_events), Sites: uint64(ci.sites)},
 		FilteredBases: uint64(ci.filtered_bases)}, err
 }
+
+// PileupRowsParams is polyhip_pileup_rows_params: the region, the origin column 2 counts from (PosOrigin <= RegionLo; column
+// 2 prints p - PosOrigin + 1), the minimum mapping quality, the Phred offset of the input qualities and whether positions
+// without a read get a row.
+type PileupRowsParams struct {
+	RegionLo, RegionHi, PosOrigin uint64
+	MinMapq, QualOffset           uint32
+	AllPositions                  bool
+}
+
+// PileupRowsInfo is polyhip_pileup_rows_info.  MaxRowBytes above 65536 means pileup.Parse of the fork refuses the longest row.
+type PileupRowsInfo struct {
+	Entries, Used, SkippedMapq, Bad, Columns, Tokens, Rows, TextBytes, DroppedEvents, MaxRowBytes uint64
+}
+
+// PileupRowsResult: Text holds the rows of the region in ascending position, each "name \t pos \t ref \t depth \t tokens \t
+// qualities \n"; the row of position p is Text[RowOff[p-RegionLo]:RowOff[p-RegionLo+1]]; Errs one value per entry.
+type PileupRowsResult struct {
+	Text   []byte
+	RowOff []uint64
+	Errs   []uint32
+}
+
+// PileupRows writes what the entries of a MapResult say about each position of the text ref as six-column pileup rows, the
+// text that pileup.Parse reads.  mapq: the Mapq of AlnRecords (nil: p.MinMapq must be 0 and the byte behind '^' is '~').
+// quals / qualOff: as in PileupQual, or nil for rows without qualities.  order: the permutation of CoordOrder, or nil for
+// entry order.  textCap: bytes of the text buffer; a call that outgrows it runs once more with the size the library reports.
+func PileupRows(r *MapResult, mapq []uint8, quals []byte, qualOff []uint64, ref []byte, order []uint32, name string, p PileupRowsParams,
+	textCap int) (*PileupRowsResult, error) {
+	n := len(r.Flags)
+	if len(r.AlnOff) != n+1 || len(r.RefStart) != n || len(r.RefEnd) != n || (mapq != nil && len(mapq) != n) ||
+		(order != nil && len(order) != n) || (quals != nil && (len(qualOff) != n+1 || len(r.ReadStart) != n)) {
+		return nil, fmt.Errorf("polyhip.PileupRows: the arrays hold different numbers of entries")
+	}
+	if p.RegionLo > p.RegionHi || p.RegionHi > uint64(len(ref)) {
+		return nil, fmt.Errorf("polyhip.PileupRows: the region [%d, %d) is not inside the text of %d bytes", p.RegionLo, p.RegionHi, len(ref))
+	}
+	if len(name) == 0 {
+		return nil, fmt.Errorf("polyhip.PileupRows: the name is empty")
+	}
+	var cp C.polyhip_pileup_rows_params
+	cp.region_lo, cp.region_hi, cp.pos_origin = C.uint64_t(p.RegionLo), C.uint64_t(p.RegionHi), C.uint64_t(p.PosOrigin)
+	cp.min_mapq, cp.qual_offset = C.uint32_t(p.MinMapq), C.uint32_t(p.QualOffset)
+	if p.AllPositions {
+		cp.all_positions = 1
+	}
+	pad32 := func(s []uint32) []uint32 { // an empty batch still needs &s[0]
+		if len(s) == 0 {
+			return []uint32{0}
+		}
+		return s
+	}
+	padB := func(s []byte) []byte {
+		if len(s) == 0 {
+			return []byte{0}
+		}
+		return s
+	}
+	flags, refStart, refEnd := pad32(r.Flags), pad32(r.RefStart), pad32(r.RefEnd)
+	alnA, alnB, text, nameB := padB(r.AlignA), padB(r.AlignB), padB(ref), []byte(name)
+	var mq, qp *C.uint8_t // nil: no mapq; nil: no qualities
+	var rsp, op *C.uint32_t
+	var qop *C.uint64_t
+	if len(mapq) > 0 {
+		mq = (*C.uint8_t)(unsafe.Pointer(&mapq[0]))
+	}
+	if quals != nil && n > 0 {
+		qual := padB(quals)
+		qp, qop = (*C.uint8_t)(unsafe.Pointer(&qual[0])), (*C.uint64_t)(unsafe.Pointer(&qualOff[0]))
+		rsp = (*C.uint32_t)(unsafe.Pointer(&r.ReadStart[0]))
+	}
+	if len(order) > 0 {
+		op = (*C.uint32_t)(unsafe.Pointer(&order[0]))
+	}
+	L := int(p.RegionHi - p.RegionLo)
+	out := &PileupRowsResult{RowOff: make([]uint64, L+1), Errs: make([]uint32, n+1)}
+	var ntext C.uint64_t
+	var err error
+	for attempt := 0; attempt < 2; attempt++ {
+		out.Text = make([]byte, textCap+1)
+		err = call(func() C.int {
+			return C.polyhip_pileup_rows((*C.polyhip_pileup_rows_params)(unsafe.Pointer(&cp)), C.uint64_t(n),
+				(*C.uint32_t)(unsafe.Pointer(&flags[0])), (*C.uint8_t)(unsafe.Pointer(mq)),
+				(*C.uint32_t)(unsafe.Pointer(&refStart[0])), (*C.uint32_t)(unsafe.Pointer(&refEnd[0])),
+				(*C.uint32_t)(unsafe.Pointer(rsp)),
+				(*C.uint8_t)(unsafe.Pointer(&alnA[0])), (*C.uint8_t)(unsafe.Pointer(&alnB[0])),
+				(*C.uint64_t)(unsafe.Pointer(&r.AlnOff[0])), (*C.uint8_t)(unsafe.Pointer(qp)),
+				(*C.uint64_t)(unsafe.Pointer(qop)), (*C.uint8_t)(unsafe.Pointer(&text[0])), C.uint64_t(len(ref)),
+				(*C.uint32_t)(unsafe.Pointer(op)), (*C.uint8_t)(unsafe.Pointer(&nameB[0])), C.uint64_t(len(nameB)),
+				(*C.uint64_t)(unsafe.Pointer(&ntext)), (*C.uint8_t)(unsafe.Pointer(&out.Text[0])), C.uint64_t(textCap),
+				(*C.uint64_t)(unsafe.Pointer(&out.RowOff[0])), (*C.uint32_t)(unsafe.Pointer(&out.Errs[0])))
+		})
+		if err == nil || uint64(ntext) <= uint64(textCap) {
+			break
+		}
+		textCap = int(ntext)
+	}
+	if err != nil {
+		return nil, err
+	}
+	out.Text, out.Errs = out.Text[:ntext], out.Errs[:n]
+	return out, nil
+}
+
+// LastPileupRowsInfo must run on the OS thread that made the call (runtime.LockOSThread around both).
+func LastPileupRowsInfo() (PileupRowsInfo, error) {
+	var ci C.polyhip_pileup_rows_info
+	err := call(func() C.int { return C.polyhip_pileup_rows_last_info((*C.polyhip_pileup_rows_info)(unsafe.Pointer(&ci))) })
+	return PileupRowsInfo{Entries: uint64(ci.entries), Used: uint64(ci.used), SkippedMapq: uint64(ci.skipped_mapq), Bad: uint64(ci.bad),
+		Columns: uint64(ci.columns), Tokens: uint64(ci.tokens), Rows: uint64(ci.rows), TextBytes: uint64(ci.text_bytes),
+		DroppedEvents: uint64(ci.dropped_events), MaxRowBytes: uint64(ci.max_row_bytes)}, err
+}

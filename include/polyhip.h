@@ -1221,7 +1221,7 @@ int polyhip_aln_records(const polyhip_aln_records_params *params, uint64_t n,
                         uint32_t *err);
 int polyhip_aln_records_last_info(polyhip_aln_records_info *info);
 
-/* ---- pileup of the mapper's output: per-position counts, consensus, variant sites (integer counts only; no text rows) ---- */
+/* ---- pileup of the mapper's output: per-position counts, consensus, variant sites; polyhip_pileup_rows: the text rows ---- */
 /*
  * polyhip_pileup asks what the n entries that polyhip_map_reads, polyhip_map_reads_affine or polyhip_map_pairs returned say
  * about each position of the text region [region_lo, region_hi), L = region_hi - region_lo.  It is a pass over those
@@ -1344,6 +1344,83 @@ int polyhip_pileup_qual(const polyhip_pileup_qual_params *params, uint64_t n, co
                         uint8_t *consensus, uint64_t *nsites, polyhip_pileup_site *sites,
                         uint64_t site_capacity, uint32_t *err);
 int polyhip_pileup_qual_last_info(polyhip_pileup_qual_info *info);
+
+/*
+ * polyhip_pileup_rows writes what the same entries say about each position of [region_lo, region_hi) as the text rows of the
+ * six-column pileup format: one row per position, one token and one quality byte per read that covers it, the inserted and
+ * deleted bytes spelled out.  It takes the arrays of polyhip_pileup_qual plus the order of the reads and the sequence name.
+ *  Column classes, text positions, the strand, skipped entries, err values 4, 1, 2, 3, 5 and "used" are polyhip_pileup's, word
+ *   for word.  With qual != NULL, err values 6 and 7 and the quality index of a column (x, y, Q) are polyhip_pileup_qual's;
+ *   with qual == NULL neither applies and qualOff and read_start are not read.  Only used entries contribute: the whole
+ *   entry is judged before anything of it is emitted.
+ *  order: order[r] is the entry at rank r, as polyhip_coord_order returns it, a permutation of 0..n-1; NULL is entry order,
+ *   order[r] = r.
+ *  Tokens: a used entry has one token at every column with b != '-' whose position p lies in the region; the tokens at one
+ *   position ascend by rank r.  With s the strand, fold upper-casing ASCII letters, cls the base class table of the counts
+ *   and letter(x) = "ACGTN"[cls(x)], or "acgtn"[cls(x)] when s is set, a token is made of these parts, in this order:
+ *    1. '^' and the byte min(mapq[i], 93) + 33, if this is the entry's first column with b != '-' (a NULL mapq reads as 255, so
+ *       the byte is '~');
+ *    2. one byte for the column: a base column gives '.' (',' when s is set) if fold(a) == fold(b), else letter(a); a D column
+ *       gives '*';
+ *    3. for every maximal run of I or of D columns whose anchor is this column, in column order: an I run gives '+', the run
+ *       length in decimal and letter(alnA[c]) for each of its columns; a D run gives '-', the run length in decimal and
+ *       letter(alnB[c]) for each of its columns.  The anchor is that of count channels 6 and 7: the last column with b != '-'
+ *       before the run.  So an I run and the D run behind it share one token (".+2AC-1G"), and a run behind a D column hangs
+ *       on a '*' ("*+1T");
+ *    4. '$', if this is the entry's last column with b != '-'.
+ *   A run with no column with b != '-' before it, that is a run that opens the entry, has no token to hang on: it is dropped
+ *   and counted in info.dropped_events, whatever the region (the D columns of such a run still have their '*' tokens).  A
+ *   token outside the region is dropped with the runs it carries.
+ *  Quality byte of a token: a base column gives Q + 33; a D column gives the Q of the read base at index min(x, the index of
+ *   the entry's last aligned read base), that is the next read base or, when none follows, the last one, plus 33; an entry
+ *   without any read base gives '!'.  With qual == NULL every token gives '~'.  The output is offset 33 whatever qual_offset
+ *   the input has.
+ *  Row of position p with d tokens:  name \t (p - pos_origin + 1) \t R \t d \t the tokens \t their quality bytes \n,  tokens and
+ *   quality bytes in the same order, R = ref[p] if it is in 0x21..0x7e and 'N' otherwise, both numbers in decimal.  With
+ *   all_positions == 0 rows with d == 0 are not written; with all_positions == 1 they read  name \t pos \t R \t 0 \t * \t * \n.
+ *   Rows ascend by p.  pos_origin <= region_lo lets a contig of a polyhip_refs set print its own positions.
+ *  There is no minimum base quality here: a row shows every read and d equals the depth of polyhip_pileup (the sum of its
+ *   channels 0..5 over both strands) on the same arrays and min_mapq.  Filtering by base quality stays with
+ *   polyhip_pileup_qual.
+ *  Outputs: *ntext = the bytes of all rows, always filled.  row_off (optional, L + 1 values): the row of position p is
+ *   text[row_off[p - region_lo] .. row_off[p - region_lo + 1]), empty where no row is written.  err[n] as above.  Capacity is
+ *   that of the sites of polyhip_pileup: if *ntext exceeds text_capacity nothing is written to text and the call fails with
+ *   POLYHIP_ERR_INVALID naming the size needed, after err, row_off and *ntext have been filled; text == NULL with a capacity
+ *   of 0 asks for the size only.  No device buffer for the text is allocated before that check.  The bytes are the same
+ *   from run to run: no atomic decides where a byte goes or which read comes first.
+ * Errors, in this order: what polyhip_pileup checks on the region fields, in its order (NULL params, region_lo, region_hi);
+ * pos_origin > region_lo, all_positions > 1, qual_offset > 162 (_INVALID, naming the field);  name == NULL, name_len == 0 or a
+ * name byte outside 0x21..0x7e (_INVALID);  n >= 2^32 (POLYHIP_ERR_UNSUPPORTED: order is uint32);  min_mapq > 0 with mapq ==
+ * NULL;  a NULL array that is needed (_INVALID: ref and ntext always, text unless text_capacity == 0; with n > 0 flags,
+ * ref_start, ref_end, alnOff and err, with qual != NULL also read_start and qualOff; alnA and alnB may be NULL when alnOff[n]
+ * == alnOff[0]; mapq, qual, order and row_off may be NULL);  alnOff or, with qual != NULL, qualOff not ascending (_INVALID);
+ * order not a permutation of 0..n-1 (_INVALID, naming order: checked on the device before anything is written);  more than
+ * 2^32 - 1 tokens (_UNSUPPORTED: the caller splits the region; err has been filled).  n == 0 and L == 0 are successful
+ * calls.  Host pointers only, no stream, and nothing that depends on n or on the region is allocated before the argument
+ * checks, as polyhip_pileup.
+ * polyhip_pileup_rows_last_info: the calling thread's last call: entries, used, skipped_mapq, bad, columns as
+ * polyhip_pileup_info; tokens = the tokens of all rows; rows = the rows written; text_bytes = *ntext; dropped_events as
+ * above; max_row_bytes = the longest row, newline included (the reference's parser refuses a line above 65536 bytes).
+ */
+typedef struct polyhip_pileup_rows_params {
+    uint64_t region_lo, region_hi; /* text positions [lo, hi); L = hi - lo */
+    uint64_t pos_origin;           /* column 2 prints p - pos_origin + 1; pos_origin <= region_lo */
+    uint32_t min_mapq;             /* entries with mapq[i] < min_mapq are skipped; > 0 needs mapq != NULL */
+    uint32_t qual_offset;          /* Phred offset of the input quality bytes, 33 for FASTQ; <= 162 */
+    uint32_t all_positions;        /* 0: only rows with a token; 1: every position of the region */
+    uint32_t pad;
+} polyhip_pileup_rows_params;
+typedef struct polyhip_pileup_rows_info {
+    uint64_t entries, used, skipped_mapq, bad, columns, tokens, rows, text_bytes, dropped_events, max_row_bytes;
+} polyhip_pileup_rows_info;
+int polyhip_pileup_rows(const polyhip_pileup_rows_params *params, uint64_t n, const uint32_t *flags,
+                        const uint8_t *mapq, const uint32_t *ref_start, const uint32_t *ref_end,
+                        const uint32_t *read_start, const uint8_t *alnA, const uint8_t *alnB,
+                        const uint64_t *alnOff, const uint8_t *qual, const uint64_t *qualOff,
+                        const uint8_t *ref, uint64_t ref_len, const uint32_t *order,
+                        const uint8_t *name, uint64_t name_len, uint64_t *ntext, uint8_t *text,
+                        uint64_t text_capacity, uint64_t *row_off, uint32_t *err);
+int polyhip_pileup_rows_last_info(polyhip_pileup_rows_info *info);
 
 /* ---- duplicate marking and coordinate order of the mapper's output (no counterpart in the reference) ---- */
 /*

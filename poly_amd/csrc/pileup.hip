@@ -2,7 +2,8 @@
 // the variant sites.  The definition is the comment above polyhip_pileup in include/polyhip.h; tests/pileup_oracle.py restates
 // it in plain Python.
 //
-//   walk_kernel<false>  one wave per entry, 64 columns per step: err of the entry (the whole entry is judged before any add)
+//   walk_kernel<false>  (pileup_walk.h) one wave per entry, 64 columns per step: err of the entry (the whole entry is judged
+//                       before any add)
 //   walk_kernel<true>   the same walk over the used entries: one 32-bit integer atomic add per counted column or event
 //   call_kernel<false>  (pileup_call.h) one lane per position: the consensus byte and the number of sites (uint64, for the scan)
 //   scan_excl           site offsets; the total comes back to the host with counts, consensus and err
@@ -16,101 +17,10 @@
 #include "device_prims.h"
 #include "host_pipeline.h"
 #include "pileup_call.h"
+#include "pileup_walk.h"
 
 namespace polyhip {
 namespace {
-
-// ADD == false: err[i] is written, info[USED, SKIPPED, BAD, COLUMNS] are added to, counts is not touched.
-// ADD == true: err[i] is read, the used entries add to counts, info[EDGE] is added to.
-template <bool ADD>
-__global__ __launch_bounds__(BT) void walk_kernel(uint64_t n, uint32_t min_mapq, uint64_t lo, uint64_t L, uint64_t ref_len,
-                                                  const uint32_t *__restrict__ flags, const uint8_t *__restrict__ mapq,
-                                                  const uint32_t *__restrict__ ref_start, const uint32_t *__restrict__ ref_end,
-                                                  const uint8_t *__restrict__ alnA, const uint8_t *__restrict__ alnB,
-                                                  const uint64_t *__restrict__ alnOff, const uint8_t *__restrict__ ref, uint32_t *err,
-                                                  uint32_t *counts, unsigned long long *info)
-{
-    const int lane = threadIdx.x & 63;
-    const uint64_t off0 = n ? alnOff[0] : 0; // the device copy of the strings starts at the first entry's columns
-    uint64_t n_used = 0, n_skipped = 0, n_bad = 0, n_cols = 0, n_edge = 0; // of this wave's entries, the same in every lane
-    for (uint64_t i = (uint64_t)blockIdx.x * PU_WAVES + (threadIdx.x >> 6); i < n; i += (uint64_t)gridDim.x * PU_WAVES) {
-        const uint32_t f = flags[i];
-        const bool mapped = f & 1u;
-        const bool skipped = mapped && min_mapq > 0 && mapq[i] < min_mapq; // min_mapq > 0 comes with a mapq array
-        const uint64_t ncol = alnOff[i + 1] - alnOff[i];
-        if (!ADD && (!mapped || skipped || ncol > POLYHIP_ALN_MAX_COLUMNS)) {
-            const uint32_t e = mapped && !skipped ? 4u : 0u;
-            if (lane == 0)
-                err[i] = e;
-            n_skipped += skipped ? 1u : 0u;
-            n_bad += e ? 1u : 0u;
-            continue;
-        }
-        if (ADD && (!mapped || skipped || err[i] != 0))
-            continue;
-        const uint32_t ncols = (uint32_t)ncol;
-        const uint64_t rs = ref_start[i];
-        const uint8_t *a = alnA + (alnOff[i] - off0), *b = alnB + (alnOff[i] - off0);
-        const uint32_t strand = f & 2u ? CH_STRAND : 0u;
-        uint64_t tbase = rs;   // text position of the next column with b != '-'
-        uint32_t carry = 0;    // the column before this step: bit 0 it was I, bit 1 it was D
-        bool invalid = false, differs = false;
-        for (uint32_t base = 0; base < ncols; base += 64) {
-            const uint32_t c = base + lane;
-            const bool v = c < ncols;
-            const uint32_t ca = v ? a[c] : 0u, cb = v ? b[c] : 0u;
-            const bool ga = ca == '-', gb = cb == '-';
-            const uint64_t mV = __ballot(v);
-            if (!ADD && __ballot(v && ga && gb)) {
-                invalid = true;
-                break;
-            }
-            const uint64_t mD = __ballot(v && ga), mI = __ballot(v && gb), mT = mV & ~mI;
-            // a column with b != '-' sits at p; a run that starts at this lane is anchored at p - 1
-            const uint64_t p = tbase + (uint64_t)__popcll(mT & lanes_below(lane));
-            if (!ADD) {
-                if (__ballot(v && !gb && (p >= ref_len || cb != ref[p])))
-                    differs = true;
-            } else {
-                const uint64_t sI = mI & ~(mI << 1 | (carry & 1u)), sD = mD & ~(mD << 1 | (carry >> 1 & 1u));
-                bool edge = false;
-                if (v && !gb && p - lo < L) // p < lo wraps to a value above L
-                    atomicAdd(&counts[(strand + (ga ? (uint32_t)CH_DEL : base_class(ca))) * L + (p - lo)], 1u);
-                if ((sI | sD) >> lane & 1ull) {
-                    if (p == 0)
-                        edge = true;
-                    else if (p - 1 - lo < L)
-                        atomicAdd(&counts[(strand + (gb ? (uint32_t)CH_INS_EVENT : (uint32_t)CH_DEL_EVENT)) * L + (p - 1 - lo)], 1u);
-                }
-                n_edge += (uint64_t)__popcll(__ballot(edge));
-            }
-            const int nv = __popcll(mV);
-            carry = (uint32_t)(mI >> (nv - 1) & 1ull) | (uint32_t)(mD >> (nv - 1) & 1ull) << 1;
-            tbase += (uint64_t)__popcll(mT);
-        }
-        if (!ADD) {
-            const uint64_t re = ref_end[i];
-            const uint32_t e = invalid ? 1u : (tbase != re || re > ref_len) ? 2u : ncols == 0 ? 3u : differs ? 5u : 0u;
-            if (lane == 0)
-                err[i] = e;
-            n_bad += e ? 1u : 0u;
-            n_used += e ? 0u : 1u;
-            n_cols += e ? 0u : ncol;
-        }
-    }
-    if (lane == 0) {
-        if (n_used) {
-            atomicAdd(&info[INFO_USED], (unsigned long long)n_used);
-            atomicAdd(&info[INFO_COLUMNS], (unsigned long long)n_cols);
-        }
-        if (n_skipped)
-            atomicAdd(&info[INFO_SKIPPED], (unsigned long long)n_skipped);
-        if (n_bad)
-            atomicAdd(&info[INFO_BAD], (unsigned long long)n_bad);
-        if (n_edge)
-            atomicAdd(&info[INFO_EDGE], (unsigned long long)n_edge);
-    }
-}
 
 thread_local polyhip_pileup_info t_info{};
 

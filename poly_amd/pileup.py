@@ -2,8 +2,10 @@
 
 The definition is the comment above ``polyhip_pileup`` in include/polyhip.h and tests/pileup_oracle.py restates it on the
 CPU.  Everything is counted in HIP from the arrays a ``mapper.MapResult`` holds and the text the reads were mapped to;
-nothing is computed here.  Integer counts only: no inserted sequences (hence no VCF indel records), no samtools text rows,
-one text.  ``pileup`` / ``pileup_packed`` / ``pileup_refs`` do not look at base qualities; the ``*_qual`` calls
+nothing is computed here.  The counts are integers and say how many reads show an insertion, not what was inserted; the
+inserted and deleted bytes are in the text rows of ``rows`` / ``rows_packed`` / ``rows_refs`` (polyhip_pileup_rows, restated
+in tests/pileup_rows_oracle.py), the six-column pileup format that ``pileup_text`` parses.  No VCF records; one text.
+``pileup`` / ``pileup_packed`` / ``pileup_refs`` do not look at base qualities; the ``*_qual`` calls
 (polyhip_pileup_qual, restated in tests/pileup_qual_oracle.py) take the reads' quality strings as ``fastq.pack_qual`` packs
 them, count a base only when its quality reaches ``min_base_qual`` and add ``qsum``, the sum of the counted qualities per
 base and strand.
@@ -308,3 +310,169 @@ def pileup_qual_refs(result, refs, contig: int, quals, qual_offsets, records=Non
                              None if records is None else records.mapq, where, min_mapq, min_depth, min_alt_count, min_alt_permille,
                              site_capacity, min_base_qual, qual_offset, dup)
     return _local(out, base, lo)
+
+
+# ---- as text rows (polyhip_pileup_rows) -------------------------------------------------------------------------------------------
+class _CRowsParams(C.Structure):
+    _fields_ = [("region_lo", C.c_uint64), ("region_hi", C.c_uint64), ("pos_origin", C.c_uint64), ("min_mapq", C.c_uint32),
+                ("qual_offset", C.c_uint32), ("all_positions", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class _CRowsInfo(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("entries", "used", "skipped_mapq", "bad", "columns", "tokens", "rows", "text_bytes",
+                                           "dropped_events", "max_row_bytes")]
+
+
+def last_rows_info() -> dict:
+    """polyhip_pileup_rows_last_info: what the calling thread's last ``rows*`` call did.  ``max_row_bytes`` above
+    ``pileup_text.MAX_LINE_SIZE`` means the reference's parser refuses the longest row."""
+    info = _CRowsInfo()
+    _lib.check(_lib.lib().polyhip_pileup_rows_last_info(C.byref(info)))
+    return {name: int(getattr(info, name)) for name, _ in _CRowsInfo._fields_}
+
+
+@dataclass
+class PileupRows:
+    """``text``: the rows of the region as one uint8 array, ascending position, each ``name \\t pos \\t ref \\t depth \\t tokens \\t
+    qualities \\n``.  ``row_off``: L + 1 offsets, the row of position p is ``text[row_off[p - region_lo]:row_off[p - region_lo + 1]]``
+    (empty where no row is written).  ``status``: OK, or ERR_INVALID when a text capacity that the caller fixed was short
+    (``ntext`` then says what is needed and ``text`` is None)."""
+    text: np.ndarray | None
+    row_off: np.ndarray
+    err: np.ndarray
+    nrows: int = 0
+    status: int = 0
+    region_lo: int = 0
+    ntext: int = 0
+
+    def row(self, p: int) -> bytes:
+        """the row of text position p (in the positions ``region_lo`` counts in), b"" where none was written"""
+        j = int(p) - self.region_lo
+        if not 0 <= j < len(self.row_off) - 1:
+            raise IndexError(f"PileupRows.row: position {p} is outside the region")
+        if self.text is None:
+            raise ValueError("PileupRows.row: the call delivered no text")
+        return self.text[int(self.row_off[j]):int(self.row_off[j + 1])].tobytes()
+
+    def tobytes(self) -> bytes:
+        return b"" if self.text is None else self.text.tobytes()
+
+    def parse(self) -> list:
+        """the rows as ``pileup_text.Pileup`` records"""
+        from . import pileup_text
+        return pileup_text.parse(self.tobytes())
+
+    last_info = staticmethod(last_rows_info)
+
+
+def _text_short() -> bool:
+    return b"the text needs" in _lib.lib().polyhip_last_error()
+
+
+def rows_packed(flags, ref_start, ref_end, alnA, alnB, aln_off, ref, name, mapq=None, read_start=None, qual=None, qual_off=None,
+                order=None, region=None, pos_origin: int = 0, min_mapq: int = 0, qual_offset: int = 33, all_positions: bool = False,
+                text_capacity: int | None = None, dup=None) -> PileupRows:
+    """polyhip_pileup_rows on packed arrays.  ``name``: the sequence name of column 1.  ``qual`` / ``qual_off`` / ``read_start``:
+    as in ``pileup_qual_packed``, or all None for rows without qualities ('~' everywhere).  ``order``: the permutation of
+    ``dedup.coord_order``; None is entry order.  ``pos_origin``: column 2 prints ``p - pos_origin + 1``.  The text capacity
+    defaults to a guess; a call that needs more is run again with the exact size -- unless a capacity was given, in which
+    case the result carries ``status`` = ERR_INVALID, ``ntext``, and no ``text``.  ``dup``: as in ``pileup_packed``."""
+    n = len(flags)
+    flags = _without(flags, dup)
+    flags, ref_start, ref_end = (np.ascontiguousarray(x, dtype=np.uint32) for x in (flags, ref_start, ref_end))
+    alnA, alnB = (np.ascontiguousarray(x, dtype=np.uint8) for x in (alnA, alnB))
+    aln_off = np.ascontiguousarray(aln_off, dtype=np.uint64)
+    ref = np.ascontiguousarray(np.frombuffer(ref, np.uint8) if isinstance(ref, (bytes, bytearray)) else ref, dtype=np.uint8)
+    if isinstance(name, str):
+        name = name.encode("latin-1")
+    name = np.frombuffer(bytes(name), np.uint8)
+    if not (len(ref_start) == len(ref_end) == n and len(aln_off) == n + 1):
+        raise ValueError("rows_packed: the arrays hold different numbers of entries")
+    if n and int(aln_off[n]) > min(len(alnA), len(alnB)):
+        raise ValueError("rows_packed: the offsets reach beyond the strings")
+    if mapq is not None:
+        mapq = np.ascontiguousarray(mapq, dtype=np.uint8)
+        if len(mapq) != n:
+            raise ValueError("rows_packed: the arrays hold different numbers of entries")
+    if qual is not None:
+        if read_start is None or qual_off is None:
+            raise ValueError("rows_packed: qual comes with read_start and qual_off")
+        qual, read_start = np.ascontiguousarray(qual, dtype=np.uint8), np.ascontiguousarray(read_start, dtype=np.uint32)
+        qual_off = np.ascontiguousarray(qual_off, dtype=np.uint64)
+        if len(read_start) != n or len(qual_off) != n + 1:
+            raise ValueError("rows_packed: the arrays hold different numbers of entries")
+        if n and int(qual_off[n]) > len(qual):
+            raise ValueError("rows_packed: the offsets reach beyond the strings")
+        if len(qual) == 0:
+            qual = np.zeros(1, np.uint8)       # a non-NULL pointer: the qualities are given, and empty
+    if order is not None:
+        order = np.ascontiguousarray(order, dtype=np.uint32)
+        if len(order) != n:
+            raise ValueError("rows_packed: order holds another number of entries than the result")
+        if n == 0:
+            order = None
+    lo, hi = (0, len(ref)) if region is None else (int(region[0]), int(region[1]))
+    p = _CRowsParams(lo, hi, int(pos_origin), int(min_mapq), int(qual_offset), int(all_positions), 0)
+    L = max(hi - lo, 0) if hi <= len(ref) else 0         # a region the library refuses: it says so, nothing is sized by it
+    nbytes = int(aln_off[n] - aln_off[0]) if n else 0
+    fixed = text_capacity is not None
+    cap = int(text_capacity) if fixed else 2 * nbytes + (L if all_positions else min(L, nbytes)) * (len(name) + 16) + 1024
+    row_off, err, ntext = np.zeros(L + 1, np.uint64), np.zeros(n, np.uint32), C.c_uint64(0)
+    ref_buf = ref if len(ref) else np.zeros(1, np.uint8)       # ref is always required, an empty text too
+    ptr = lambda a: None if a is None else a.ctypes.data       # noqa: E731
+    text = None
+    rc = _lib.OK
+    for _ in range(2):
+        text = np.zeros(max(cap, 1), np.uint8)
+        rc = _lib.lib().polyhip_pileup_rows(C.byref(p), n, flags.ctypes.data, ptr(mapq), ref_start.ctypes.data, ref_end.ctypes.data,
+                                            ptr(read_start) if qual is not None else None, alnA.ctypes.data, alnB.ctypes.data,
+                                            aln_off.ctypes.data, ptr(qual), ptr(qual_off) if qual is not None else None,
+                                            ref_buf.ctypes.data, len(ref), ptr(order), name.ctypes.data if len(name) else None, len(name),
+                                            C.byref(ntext), text.ctypes.data, cap, row_off.ctypes.data, err.ctypes.data)
+        if rc == _lib.ERR_INVALID and _text_short():        # ntext says what the text needs
+            if fixed:
+                return PileupRows(None, row_off, err, last_rows_info()["rows"], int(rc), lo, int(ntext.value))
+            cap = int(ntext.value)
+            continue
+        _lib.check(rc)
+        break
+    return PileupRows(text[:int(ntext.value)], row_off, err, last_rows_info()["rows"], int(rc), lo, int(ntext.value))
+
+
+def _rows_quals(who: str, quals, qual_offsets, read_offsets, result):
+    if quals is None:
+        return None, None, None
+    if qual_offsets is None:
+        raise ValueError(f"pileup.{who}: quals comes with qual_offsets")
+    _same_lengths(who, read_offsets, qual_offsets)
+    return result.read_start, quals, qual_offsets
+
+
+def rows(result, ref, name, quals=None, qual_offsets=None, records=None, region=None, min_mapq: int = 0, order=None, dup=None,
+         all_positions: bool = False, read_offsets=None, qual_offset: int = 33, text_capacity: int | None = None) -> PileupRows:
+    """The pileup rows of a ``mapper.MapResult`` that holds its strings on the text ``ref``, named ``name`` in column 1.
+    ``records``: the ``sam.AlnRecords`` of the result; its ``mapq`` feeds both ``min_mapq`` and the byte behind '^' (without
+    one that byte is '~').  ``quals`` / ``qual_offsets`` / ``read_offsets`` and ``dup`` as in ``pileup_qual``; ``order``: the
+    permutation ``dedup.coord_order`` returns, which gives the reads of a row the order samtools would print them in."""
+    if result.alignA is None or result.alignB is None:
+        raise ValueError("pileup.rows: the MapResult holds no strings")
+    read_start, quals, qual_offsets = _rows_quals("rows", quals, qual_offsets, read_offsets, result)
+    a, b, off = _joined(result)
+    if isinstance(ref, str):
+        ref = ref.encode("latin-1")
+    return rows_packed(result.flags, result.ref_start, result.ref_end, a, b, off, ref, name, None if records is None else records.mapq,
+                       read_start, quals, qual_offsets, order, region, 0, min_mapq, qual_offset, all_positions, text_capacity, dup)
+
+
+def rows_refs(result, refs, contig: int, name, quals=None, qual_offsets=None, records=None, region=None, min_mapq: int = 0, order=None,
+              dup=None, all_positions: bool = False, read_offsets=None, qual_offset: int = 33,
+              text_capacity: int | None = None) -> PileupRows:
+    """``rows`` for one contig of a ``refs.RefSet``, moved to the set's concatenated text exactly as ``pileup_refs`` does it, with
+    ``pos_origin`` at the contig's start: column 2 and ``region_lo`` are positions in the contig."""
+    flags, ref_start, ref_end, where, base, lo = _on_contig("rows_refs", result, refs, contig, region)
+    read_start, quals, qual_offsets = _rows_quals("rows_refs", quals, qual_offsets, read_offsets, result)
+    a, b, off = _joined(result)
+    out = rows_packed(flags, ref_start, ref_end, a, b, off, refs.text(), name, None if records is None else records.mapq, read_start,
+                      quals, qual_offsets, order, where, base, min_mapq, qual_offset, all_positions, text_capacity, dup)
+    out.region_lo = lo
+    return out
