@@ -1493,6 +1493,85 @@ int polyhip_dedup_last_info(polyhip_dedup_info *info);
 int polyhip_coord_order(uint64_t n, uint32_t paired, const uint32_t *sam_flag, const uint32_t *rid,
                         const uint32_t *ref_start, uint32_t *order);
 
+/* ---- read trimming: quality ends, 3' adapters, mate overlap (no counterpart in the reference) ---- */
+/*
+ * polyhip_trim_reads cuts low-quality ends and 3' adapters off a packed batch of reads before it is mapped; the reference's
+ * io/fastq only parses.  Reads (reads, off) as the mappers take them, qualities (qual, qual_off) as polyhip_fastq_pack_qual
+ * gives them, or both NULL.  Adapters: nadapters (0..255) strings of 1..64 bytes of upper-case ACGT, packed as (adapters,
+ * adapter_off[nadapters + 1]).  Entry i in is entry i out: no read is removed, an emptied read has length 0 in the output, so
+ * pairs, rec_start and every later stage keep their indices (the mappers report a read shorter than seed_len as unmapped).
+ * Per read r of m bytes, with start a and end b of what is kept:
+ *  1. Judging, of the whole read before anything else looks at it.  err[i] = 1 if qualities are given and the length of the
+ *   quality string differs from m; else 2 if one of its bytes is below qual_offset or above qual_offset + 93
+ *   (polyhip_pileup_qual's range); else 0.  A read with err != 0 gets start = end = 0, flags = 0, is empty in the output
+ *   and takes no part in anything below.
+ *  2. Quality ends (BWA's rule), Q_k = qual[k] - qual_offset, both walks on the read as it came.  3' end, when min_qual_3p >
+ *   0: for k = m - 1, m - 2, ... the sum s += min_qual_3p - Q_k starting from 0; the walk stops before the first k at which
+ *   s < 0.  b = the k at which s first reached its greatest value, if that value is > 0 (strictly: of equal sums the largest
+ *   k), else b = m.  5' end, when min_qual_5p > 0: the mirror image over k = 0, 1, ...; a = one past the k of the first
+ *   greatest positive sum, else a = 0.  If a >= b then a = b = 0.  After that flags bit 0 is set iff b < m and bit 1 iff a >
+ *   0; later steps do not clear them.
+ *  3. 3' adapters, on r[a, b).  For adapter t of p bytes and a start s in [a, b), L = min(p, b - s).  s qualifies iff L >=
+ *   min_overlap and 100 * mism <= adapter_err_pct * L, where mism counts the k < L with upper(r[s + k]) != t[k]; a read byte
+ *   that is not one of ACGTacgt is a mismatch.  A whole adapter inside the read and a prefix of it at the read's end are
+ *   both this rule.  The hit is the smallest qualifying s over all adapters, a tie goes to the lowest adapter index.  Then b
+ *   = s, flags bit 2 is set and bits 8..15 hold the adapter's index.
+ *  4. Length.  If b - a < min_len the read comes out empty and flags bit 3 is set; start and end keep a and b.
+ *  5. Output.  start[i] = a, end[i] = b.  out_off has nreads + 1 entries and starts at 0; out_reads holds r[a, b) of every
+ *   read that is not empty, back to back, the bytes as they were (no case change); out_qual the same slices of the quality
+ *   strings under the same offsets.  out_reads and out_qual hold off[nreads] - off[0] bytes: there is no capacity argument.
+ * polyhip_trim_pairs: mate 1 of pair i is read i of (reads1, off1, qual1, qual_off1), mate 2 read i of the second batch;
+ * entry 2i of start / end / flags / err is mate 1 and entry 2i + 1 mate 2, as in polyhip_map_pairs, and each mate has an
+ * output batch of its own.  Steps 1-3 run on each mate by itself.  Then, before step 4:
+ *  P. Mate overlap, only when pair_min_overlap > 0, both mates have err == 0 and neither has flags bit 2.  An insert of I <
+ *   m bases is read from both ends and runs into the adapter after I bytes, so for I in [pair_min_overlap, min(m1, m2)], on
+ *   the mates as they came and from their first bytes: I qualifies iff 100 * mism <= pair_err_pct * I, where mism counts the
+ *   k < I with upper(r1[k]) != comp(upper(r2[I - 1 - k])); comp is A<->T, C<->G, any other byte is a mismatch.  The greatest
+ *   qualifying I wins.  On a mate with b > I: b = I, flags bit 4 is set, and if a >= b then a = b = 0.  The work of this
+ *   step grows with m1 * m2.
+ * Every decision is integer arithmetic and no atomic decides an output byte: the same call gives the same bytes.
+ * Errors, in this order, all before anything is allocated: a NULL params (POLYHIP_ERR_INVALID); qual_offset > 162,
+ * min_qual_5p > 93, min_qual_3p > 93, adapter_err_pct > 100, min_overlap == 0 or pair_err_pct > 100 (_INVALID, naming the
+ * field); nadapters > 255 (_INVALID); with nadapters > 0 a NULL adapters or adapter_off, then an adapter that is empty, longer
+ * than 64 bytes or holds a byte outside ACGT (_INVALID, naming the adapter's index); a cut-off > 0 with qual == NULL
+ * (_INVALID); qual and qual_off not both given or both NULL, or in polyhip_trim_pairs given for one mate only (_INVALID);
+ * out_qual given without qual or the other way round (_INVALID); a NULL start, end, flags, err, out_reads or out_off, or with
+ * nreads > 0 a NULL reads or off (_INVALID); offsets that decrease (_INVALID); a read of 2^24 bytes or more
+ * (POLYHIP_ERR_UNSUPPORTED: the running sums are 32-bit).  nreads == 0 is an empty, successful call that writes out_off[0] =
+ * 0.  Host pointers only, no stream: the call copies the batch in (of the bytes only [off[0], off[nreads])), runs on the
+ * calling thread's current device and copies the results out; the device list does not apply.
+ * polyhip_trim_last_info: the calling thread's last call: reads = the entries (2 * npairs for pairs); bytes_in and bytes_out
+ * = sequence bytes taken and kept; cut_3p, cut_5p, adapter_hits, overlap_cut, too_short = entries with flags bit 0, 1, 2, 4,
+ * 3; bad = entries with err != 0.
+ */
+typedef struct polyhip_trim_params {
+    uint32_t qual_offset;       /* Phred offset, 33 for FASTQ; <= 162 */
+    uint32_t min_qual_5p;       /* quality cut-off at the 5' end, 0 = off; <= 93 */
+    uint32_t min_qual_3p;       /* quality cut-off at the 3' end, 0 = off; <= 93 */
+    uint32_t adapter_err_pct;   /* mismatches allowed per 100 compared bytes, 0..100 */
+    uint32_t min_overlap;       /* fewest adapter bytes that count as a hit, >= 1 */
+    uint32_t min_len;           /* a shorter read comes out empty */
+    uint32_t pair_min_overlap;  /* polyhip_trim_pairs: shortest insert looked for, 0 = off */
+    uint32_t pair_err_pct;      /* 0..100 */
+} polyhip_trim_params;
+typedef struct polyhip_trim_info {
+    uint64_t reads, bytes_in, bytes_out, cut_3p, cut_5p, adapter_hits, overlap_cut, too_short, bad;
+} polyhip_trim_info;
+int polyhip_trim_reads(const polyhip_trim_params *params, const uint8_t *adapters,
+                       const uint32_t *adapter_off, uint32_t nadapters, const uint8_t *reads,
+                       const uint64_t *off, const uint8_t *qual, const uint64_t *qual_off,
+                       uint64_t nreads, uint32_t *start, uint32_t *end, uint32_t *flags, uint32_t *err,
+                       uint8_t *out_reads, uint8_t *out_qual, uint64_t *out_off);
+int polyhip_trim_pairs(const polyhip_trim_params *params, const uint8_t *adapters,
+                       const uint32_t *adapter_off, uint32_t nadapters, const uint8_t *reads1,
+                       const uint64_t *off1, const uint8_t *qual1, const uint64_t *qual_off1,
+                       const uint8_t *reads2, const uint64_t *off2, const uint8_t *qual2,
+                       const uint64_t *qual_off2, uint64_t npairs, uint32_t *start, uint32_t *end,
+                       uint32_t *flags, uint32_t *err, uint8_t *out_reads1, uint8_t *out_qual1,
+                       uint64_t *out_off1, uint8_t *out_reads2, uint8_t *out_qual2,
+                       uint64_t *out_off2);
+int polyhip_trim_last_info(polyhip_trim_info *info);
+
 /* ---- R1: the path's one collective -- all-gather of per-rank sketches (RCCL over xGMI) ---- */
 /*
  * For hosts without torch.distributed (the Go/cgo drop-in); one process per GPU.  RCCL is
