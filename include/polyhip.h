@@ -1422,6 +1422,101 @@ int polyhip_pileup_rows(const polyhip_pileup_rows_params *params, uint64_t n, co
                         uint64_t text_capacity, uint64_t *row_off, uint32_t *err);
 int polyhip_pileup_rows_last_info(polyhip_pileup_rows_info *info);
 
+/* ---- variant calls from the mapped reads: alleles, left-aligned indels, the records of a VCF (no counterpart in the reference) ---- */
+/*
+ * polyhip_call_variants groups what the same entries say into alleles -- position, kind, length, bytes -- and returns one
+ * record per allele that passes the pileup's thresholds: what polyhip_pileup_qual's sites leave open (what was inserted, how
+ * many bases are gone, two insertions behind one position, one indel written at several columns of a repeat).  Where this
+ * comment is silent, polyhip_pileup_qual's definition holds unchanged.
+ *  Inputs: the arrays of polyhip_pileup_qual, in its order; in place of its outputs stand the outputs below.  qual may be
+ *   NULL: qualOff and read_start are then not read, min_base_qual must be 0, every base counts with Q = 0, err 6 and 7 do
+ *   not apply and every qsum field is 0 (the walk is polyhip_pileup's).  A non-NULL qual means qualities, empty or not.
+ *  params: base as polyhip_pileup_qual_params;  left_align: 0 or not 0;  hom_permille: 0..1000;  max_indel: 1..
+ *   POLYHIP_VAR_MAX_INDEL, 0 means POLYHIP_VAR_MAX_INDEL;  pad must be 0.
+ *  Entries: err values 1..7, "used", skipped entries and the depth are exactly the pileup's: the call computes the 16 count
+ *   planes (and with qualities the 8 qsum planes) on the device, filtered by min_base_qual, and does not return them.  The
+ *   depth at p is the sum of the filtered planes k = 0..5 over both strands.
+ *  fold(x) is x - 32 for 'a'..'z', else x.  All byte comparisons below are on folded bytes and the allele bytes that come out
+ *   are folded.
+ *  Events are those of the pileup's channels 6 and 7, of used entries only: a maximal run of I columns (kind 2) or of D
+ *   columns (kind 3) that starts at column c0 of its entry (counted from the entry's first column) and is l columns long,
+ *   anchored at p0 = the position of the last column with b != '-' before it, ref_start - 1 if there is none.  An event is
+ *   judged in this order, the first that applies:
+ *    1. l > max_indel: dropped, counted in info.long_events.
+ *    2. left alignment, with left_align != 0.  x is the entry's a string for an insertion, its b string for a deletion.
+ *       Step t = 0, 1, ... succeeds when column c0 - 1 - t exists in the entry, is a match column (a != '-', b != '-' and
+ *       fold(a) == fold(b)) and fold(x[c0 - 1 - t]) == fold(x[c0 + l - 1 - t]).  k = the number of consecutive steps that
+ *       succeed from t = 0 (the crossed columns are base columns, so both strings are contiguous there).  If k == c0 -- the
+ *       walk reached the entry's first column, or c0 == 0 -- the read does not show where the repeat begins: the event is
+ *       dropped and counted in info.open_events.  Else the anchor becomes p0 - k, kind and length stay, and an insertion's
+ *       allele is fold(a[c0 - k .. c0 - k + l)).  With left_align == 0: k = 0, nothing is open, an insertion's allele is
+ *       fold(a[c0 .. c0 + l)).
+ *    3. an anchor of -1: dropped, counted in info.edge_events.
+ *    4. everything else is kept and counted in info.events (and in info.shifted_events when k > 0), whatever the region;
+ *       a kept event whose anchor is outside the region is then dropped silently.
+ *  Alleles: two kept events of the region are the same allele when anchor and kind are equal and, for a deletion, the length,
+ *   for an insertion the length and all allele bytes.  count = its events, count_fwd = those of strand 0.
+ *   site_events(p, kind) = the sum of count over all alleles of that kind at p, before any threshold.
+ *  Records (polyhip_variant), ascending pos; within a position SNV to A, C, G, T, then the insertion alleles by (length, then
+ *   bytes as unsigned, lexicographic), then the deletion alleles by length.  Only positions with depth >= max(min_depth, 1)
+ *   have records.  An allele passes by the pileup's rule on its own count: count >= max(min_alt_count, 1) and count * 1000
+ *   >= min_alt_permille * depth (uint64).
+ *    SNV (kind 1): exactly polyhip_pileup_qual's SNV sites (pos, depth, count, count_fwd, ref, alt); ref_count = the two-strand
+ *     count of the class of ref[p], 0 for class "other"; qsum = the two-strand qsum of the alt base; allele_len = 1,
+ *     allele_off = 0.
+ *    INS (kind 2): alt = 0, ref = ref[p] raw, allele_len = l, allele_off = where the l folded bytes stand in `alleles`: the pool
+ *     holds the bytes of the passing insertions back to back in record order and nothing else.  qsum = 0;  ref_count = depth
+ *     - min(depth, site_events(p, 2)).
+ *    DEL (kind 3): alt = 0, ref = ref[p] raw, allele_len = l: the deleted text is ref[p + 1 .. p + l].  allele_off = 0, qsum = 0,
+ *     ref_count = depth - min(depth, site_events(p, 3)).
+ *    gt = 2 when count * 1000 >= hom_permille * depth (uint64), else 1.
+ *  Capacity: *nvariants and *nallele_bytes are always filled.  If *nvariants exceeds variant_capacity or *nallele_bytes
+ *   exceeds allele_capacity nothing is written to either output and the call fails with POLYHIP_ERR_INVALID naming the first
+ *   of the two that is short and the size needed ("the variants need ...", "the alleles need ..."), after err has been filled.
+ *   NULL with a capacity of 0 asks for the size only.  No output-sized device buffer is allocated before that check.
+ *  The records and the pool are the same from run to run: grouping is an exact stable sort by (pos, kind, length) and the
+ *   allele bytes, no hash; no atomic decides where a record or a byte goes; every sum is of integers.
+ * Errors, in this order: polyhip_pileup_qual's checks on params, in its order (NULL params, region_lo, region_hi,
+ * min_alt_permille, min_base_qual, qual_offset);  hom_permille > 1000, max_indel > POLYHIP_VAR_MAX_INDEL, pad != 0 (_INVALID,
+ * naming the field);  qual == NULL with min_base_qual > 0 (_INVALID);  with qualities n * 93 >= 2^32, without n >= 2^32
+ * (POLYHIP_ERR_UNSUPPORTED);  min_mapq > 0 with mapq == NULL;  a NULL array that is needed (_INVALID: ref, nvariants and
+ * nallele_bytes always, variants and alleles unless their capacity is 0; with n > 0 flags, ref_start, ref_end, alnOff and err,
+ * with qual != NULL also read_start and qualOff; alnA and alnB may be NULL when alnOff[n] == alnOff[0]);  alnOff or, with qual
+ * != NULL, qualOff not ascending (_INVALID);  more than 2^32 - 1 kept events in the region (_UNSUPPORTED: the caller splits
+ * the region; err has been filled).  n == 0 and L == 0 are successful calls.  Host pointers only, no stream; nothing that
+ * depends on n or on the region is allocated before the argument checks.
+ * polyhip_call_variants_last_info: the calling thread's last call: entries, used, skipped_mapq, bad, columns as
+ * polyhip_pileup_info; edge_events as above; sites = *nvariants; filtered_bases as polyhip_pileup_qual_info (0 without
+ * qualities); events, long_events, open_events, shifted_events as above; alleles = the distinct alleles in the region before
+ * the thresholds; allele_bytes = *nallele_bytes.
+ */
+#define POLYHIP_VAR_MAX_INDEL 255u
+typedef struct polyhip_variants_params {
+    polyhip_pileup_qual_params base;
+    uint32_t left_align;      /* not 0: indels are moved to the leftmost column their read allows */
+    uint32_t hom_permille;    /* gt = 2 when count * 1000 >= hom_permille * depth; 0..1000 */
+    uint32_t max_indel;       /* longer runs are dropped; 1..POLYHIP_VAR_MAX_INDEL, 0 means POLYHIP_VAR_MAX_INDEL */
+    uint32_t pad;             /* 0 */
+} polyhip_variants_params;
+typedef struct polyhip_variant {
+    uint64_t allele_off;
+    uint32_t pos, depth, count, count_fwd, ref_count, qsum, allele_len;
+    uint8_t kind, ref, alt, gt;
+} polyhip_variant;
+typedef struct polyhip_variants_info {
+    uint64_t entries, used, skipped_mapq, bad, columns, edge_events, sites;   /* as polyhip_pileup_info */
+    uint64_t filtered_bases, events, long_events, open_events, shifted_events, alleles, allele_bytes;
+} polyhip_variants_info;
+int polyhip_call_variants(const polyhip_variants_params *params, uint64_t n, const uint32_t *flags,
+                          const uint8_t *mapq, const uint32_t *ref_start, const uint32_t *ref_end,
+                          const uint32_t *read_start, const uint8_t *alnA, const uint8_t *alnB,
+                          const uint64_t *alnOff, const uint8_t *qual, const uint64_t *qualOff,
+                          const uint8_t *ref, uint64_t ref_len, uint64_t *nvariants,
+                          polyhip_variant *variants, uint64_t variant_capacity,
+                          uint64_t *nallele_bytes, uint8_t *alleles, uint64_t allele_capacity,
+                          uint32_t *err);
+int polyhip_call_variants_last_info(polyhip_variants_info *info);
+
 /* ---- duplicate marking and coordinate order of the mapper's output (no counterpart in the reference) ---- */
 /*
  * polyhip_mark_duplicates marks, among the n entries that polyhip_map_reads, polyhip_map_reads_affine, polyhip_map_pairs or

@@ -166,6 +166,9 @@ SIGNATURES = {
     "polyhip_pileup_rows": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64,
                                       _vp, _vp]),
     "polyhip_pileup_rows_last_info": (C.c_int, [_vp]),
+    "polyhip_call_variants": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64,
+                                        _vp]),
+    "polyhip_call_variants_last_info": (C.c_int, [_vp]),
     "polyhip_mark_duplicates": (C.c_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "polyhip_dedup_last_info": (C.c_int, [_vp]),
     "polyhip_coord_order": (C.c_int, [_u64, _u32, _vp, _vp, _vp, _vp]),

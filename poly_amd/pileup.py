@@ -4,7 +4,8 @@ The definition is the comment above ``polyhip_pileup`` in include/polyhip.h and 
 CPU.  Everything is counted in HIP from the arrays a ``mapper.MapResult`` holds and the text the reads were mapped to;
 nothing is computed here.  The counts are integers and say how many reads show an insertion, not what was inserted; the
 inserted and deleted bytes are in the text rows of ``rows`` / ``rows_packed`` / ``rows_refs`` (polyhip_pileup_rows, restated
-in tests/pileup_rows_oracle.py), the six-column pileup format that ``pileup_text`` parses.  No VCF records; one text.
+in tests/pileup_rows_oracle.py), the six-column pileup format that ``pileup_text`` parses.  The alleles themselves and the records
+of a VCF are ``poly_amd.variants`` (polyhip_call_variants) and ``poly_amd.vcf``.  One text.
 ``pileup`` / ``pileup_packed`` / ``pileup_refs`` do not look at base qualities; the ``*_qual`` calls
 (polyhip_pileup_qual, restated in tests/pileup_qual_oracle.py) take the reads' quality strings as ``fastq.pack_qual`` packs
 them, count a base only when its quality reaches ``min_base_qual`` and add ``qsum``, the sum of the counted qualities per
