@@ -1667,6 +1667,87 @@ int polyhip_trim_pairs(const polyhip_trim_params *params, const uint8_t *adapter
                        uint64_t *out_off2);
 int polyhip_trim_last_info(polyhip_trim_info *info);
 
+/* ---- demultiplexing: pooled reads split by inline 5' barcodes (no counterpart in the reference) ---- */
+/*
+ * polyhip_demux_reads finds the inline barcode at the 5' end of every read of a packed batch, and hands the batch back grouped
+ * by sample: sample k is a contiguous run of reads of the output batch, which goes to polyhip_trim_reads and the mappers as it
+ * is (they take offsets that do not start at 0).  Reads (reads, off) and qualities (qual, qual_off) as polyhip_trim_reads takes
+ * them.  A barcode set: nbarcodes (1..4096) strings of 4..64 bytes of upper-case ACGT, the lengths may differ, packed as
+ * (barcodes, barcode_off[nbarcodes + 1]).  0xFFFFFFFF is "none" below.  Per read r of m bytes:
+ *  1. Judging.  err[i] = 1 if qualities are given and the length of the quality string differs from m, else 0; the quality
+ *   bytes are not interpreted.  A read with err != 0 has barcode = bstart = mism = none and flags = 0, is unassigned and is
+ *   empty in the output.
+ *  2. Distance to barcode t of p bytes.  For every start s in [0, max_shift] with s + p <= m: the number of k < p with
+ *   upper(r[s + k]) != t[k]; a read byte that is not one of ACGTacgt is a mismatch.  d_t is the smallest of these numbers and
+ *   s_t the smallest s that has it; d_t is none if no start fits.
+ *  3. Choice.  t1 is the barcode with the smallest d, the lowest index among equals; d2 the smallest d over all t != t1, none
+ *   if there is no such barcode or none of them fits.  No hit (flags bit 0): d_t1 is none or > max_mismatches.  Ambiguous
+ *   (flags bit 1): a hit, d2 is not none and d2 - d_t1 < min_margin.  Otherwise the read has a barcode: barcode[i] = t1,
+ *   bstart[i] = s_t1, mism[i] = d_t1.  With bit 0 or bit 1 set the three are none.
+ *  4. Sample.  polyhip_demux_reads: sample[i] = barcode[i], and nsamples must equal nbarcodes; the read is assigned iff it has
+ *   a barcode.  polyhip_demux_pairs: mate 1 of pair i is read i of (reads1, off1, qual1, qual_off1) and is judged against set
+ *   1, mate 2 is read i of the second batch and is judged against set 2 when nbarcodes2 > 0; entries 2i and 2i + 1 of barcode
+ *   / bstart / mism / flags / err are mate 1 and mate 2, as in polyhip_map_pairs.  A mate that is not judged against a set
+ *   has barcode = bstart = mism = none and flags = 0; its err is judged all the same.  The pair is assigned iff neither mate
+ *   has err != 0, every judged mate has a barcode and the sample is not none.  With nbarcodes2 == 0 the sample is b1 and
+ *   nsamples must equal nbarcodes1; otherwise it is pair_sample[b1 * nbarcodes2 + b2], and a table value of 0xFFFFFFFF sets
+ *   flags bit 2 on both entries (which keep barcode, bstart and mism).  sample[i] of an unassigned read or pair is none.
+ *  5. Clip.  On an entry that has a barcode, whose read or pair is assigned, and with clip != 0: a = min(m, bstart + p +
+ *   clip_extra).  Otherwise a = 0, except that an entry with err != 0 comes out empty.  The entry comes out as r[a, m) with
+ *   the same slice of its quality string, the bytes as they were.
+ *  6. Grouping.  Group g = sample if assigned, else nsamples.  order is the stable permutation by g: input order within a
+ *   group, the unassigned last.  sample_start[k], k = 0..nsamples + 1, is the number of reads (pairs) with g < k.  Output
+ *   read j is input read order[j]: sample k is the sub-batch out_off[sample_start[k] .. sample_start[k + 1]] (one entry more
+ *   than reads, as every offset array), the unassigned are sample nsamples.  out_off has n + 1 entries and starts at 0;
+ *   out_reads and out_qual hold off[n] - off[0] bytes: there is no capacity argument.  In polyhip_demux_pairs both mates'
+ *   batches use the same order.
+ * Every decision is integer arithmetic and no atomic decides an output byte: the same call gives the same bytes.
+ * Errors, in this order, all before anything is allocated: a NULL params (POLYHIP_ERR_INVALID); max_shift > 63,
+ * max_mismatches > 64, clip > 1, clip_extra >= 2^24, nsamples == 0 or > 65536 (_INVALID, naming the field); nbarcodes == 0 or
+ * > 4096, in polyhip_demux_pairs nbarcodes1 likewise and nbarcodes2 > 4096 (_INVALID); a NULL barcodes or barcode_off of a set
+ * that is not empty, then a barcode shorter than 4 or longer than 64 bytes or with a byte outside ACGT (_INVALID, naming the
+ * set and the barcode's index); an nsamples that differs from nbarcodes (nbarcodes1 when nbarcodes2 == 0) (_INVALID); with
+ * nbarcodes2 > 0 a NULL pair_sample, then an entry that is neither below nsamples nor 0xFFFFFFFF (_INVALID, naming the entry);
+ * qual, qual_off and out_qual not all given or all NULL, or in polyhip_demux_pairs given for one mate only (_INVALID); a NULL
+ * barcode, bstart, mism, flags, err, sample, order, sample_start, out_reads or out_off, or with n > 0 a NULL reads or off
+ * (_INVALID); offsets that decrease (_INVALID); a read of 2^24 bytes or more, or 2^32 reads or more (POLYHIP_ERR_UNSUPPORTED).
+ * n == 0 is an empty, successful call that writes out_off[0] = 0 and zeroes every sample_start.  Host pointers only, no
+ * stream: the call copies the batch in, runs on the calling thread's current device and copies the results out; the device
+ * list does not apply.
+ * polyhip_demux_last_info: the calling thread's last call: reads = the entries (2 * npairs for pairs); assigned = entries of
+ * assigned reads or pairs; exact = entries that have a barcode with mism == 0; no_barcode, ambiguous, not_in_sheet = entries
+ * with flags bit 0, 1, 2; bad = entries with err != 0; bytes_in and bytes_out = sequence bytes taken and written.
+ */
+typedef struct polyhip_demux_params {
+    uint32_t max_shift;       /* a barcode may start at byte 0..max_shift of its read; <= 63 */
+    uint32_t max_mismatches;  /* <= 64 */
+    uint32_t min_margin;      /* the best barcode must beat every other by this many mismatches; 0: ties to the lowest index */
+    uint32_t clip;            /* 0 / 1: cut the barcode and what precedes it */
+    uint32_t clip_extra;      /* further bytes cut after the barcode (a linker), < 2^24 */
+    uint32_t nsamples;        /* groups of the output, 1..65536 */
+} polyhip_demux_params;
+typedef struct polyhip_demux_info {
+    uint64_t reads, assigned, exact, no_barcode, ambiguous, not_in_sheet, bad, bytes_in, bytes_out;
+} polyhip_demux_info;
+int polyhip_demux_reads(const polyhip_demux_params *params, const uint8_t *barcodes,
+                        const uint32_t *barcode_off, uint32_t nbarcodes, const uint8_t *reads,
+                        const uint64_t *off, const uint8_t *qual, const uint64_t *qual_off,
+                        uint64_t nreads, uint32_t *barcode, uint32_t *bstart, uint32_t *mism,
+                        uint32_t *flags, uint32_t *err, uint32_t *sample, uint32_t *order,
+                        uint64_t *sample_start, uint8_t *out_reads, uint8_t *out_qual,
+                        uint64_t *out_off);
+int polyhip_demux_pairs(const polyhip_demux_params *params, const uint8_t *barcodes1,
+                        const uint32_t *barcode_off1, uint32_t nbarcodes1, const uint8_t *barcodes2,
+                        const uint32_t *barcode_off2, uint32_t nbarcodes2, const uint32_t *pair_sample,
+                        const uint8_t *reads1, const uint64_t *off1, const uint8_t *qual1,
+                        const uint64_t *qual_off1, const uint8_t *reads2, const uint64_t *off2,
+                        const uint8_t *qual2, const uint64_t *qual_off2, uint64_t npairs,
+                        uint32_t *barcode, uint32_t *bstart, uint32_t *mism, uint32_t *flags,
+                        uint32_t *err, uint32_t *sample, uint32_t *order, uint64_t *sample_start,
+                        uint8_t *out_reads1, uint8_t *out_qual1, uint64_t *out_off1,
+                        uint8_t *out_reads2, uint8_t *out_qual2, uint64_t *out_off2);
+int polyhip_demux_last_info(polyhip_demux_info *info);
+
 /* ---- R1: the path's one collective -- all-gather of per-rank sketches (RCCL over xGMI) ---- */
 /*
  * For hosts without torch.distributed (the Go/cgo drop-in); one process per GPU.  RCCL is

@@ -176,6 +176,11 @@ SIGNATURES = {
     "polyhip_trim_pairs": (C.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _vp, _vp, _vp, _vp]),
     "polyhip_trim_last_info": (C.c_int, [_vp]),
+    "polyhip_demux_reads": (C.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _vp]),
+    "polyhip_demux_pairs": (C.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "polyhip_demux_last_info": (C.c_int, [_vp]),
     "polyhip_comm_unique_id": (C.c_int, [_vp]),
     "polyhip_comm_init_rank": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "polyhip_comm_destroy": (C.c_int, [_vp]),

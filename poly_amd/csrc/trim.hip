@@ -17,8 +17,8 @@
 //   finish_kernel   a lane per entry: step 4 (min_len), the kept length for the scan, the info counters
 //   scan_excl       (device_prims.h) the kept lengths -> out_off, per mate
 //   gather_kernel   one wave per read: r[a, b) and the same slice of its quality string to their places
-#include "device_prims.h"
 #include "host_pipeline.h"
+#include "read_batch.h"
 
 namespace polyhip {
 namespace {
@@ -33,18 +33,6 @@ struct Knobs {
     uint32_t qual_offset, min_qual_5p, min_qual_3p, adapter_err_pct, min_overlap, nadapters;
 };
 
-// one batch of reads on the device; the copies of the bytes start at the first read's (off[0], qual_off[0])
-struct DevBatch {
-    const uint8_t *reads, *qual; // qual == nullptr: no qualities
-    const uint64_t *off, *qual_off;
-};
-
-// the upper-case letter of one of ACGTacgt, 0 for every other byte
-__device__ __forceinline__ uint32_t base_code(uint32_t c)
-{
-    const uint32_t u = c & ~0x20u;
-    return (u == 'A' || u == 'C' || u == 'G' || u == 'T') ? u : 0u;
-}
 // the complement's letter, 0xFF for every other byte: never equal to a base_code
 __device__ __forceinline__ uint32_t complement_code(uint32_t c)
 {
@@ -225,14 +213,6 @@ __global__ __launch_bounds__(BT) void pair_kernel(uint64_t npairs, uint32_t pair
     }
 }
 
-// a wave's count into the block's counter in LDS
-__device__ __forceinline__ void add_info(uint32_t *s_info, int which, uint32_t mine)
-{
-    const uint32_t all = (uint32_t)__builtin_amdgcn_readlane((int)dpp_incl_scan(mine), 63);
-    if ((threadIdx.x & 63) == 0 && all)
-        atomicAdd(&s_info[which], all);
-}
-
 // Step 4, the kept length of every entry where the scan wants it (pairs: mate 1's n + 1 slots, then mate 2's), the counters
 __global__ __launch_bounds__(BT) void finish_kernel(uint64_t entries, uint32_t stride, uint64_t n, uint32_t min_len,
                                                     const uint32_t *__restrict__ start, const uint32_t *__restrict__ end,
@@ -296,16 +276,6 @@ __global__ __launch_bounds__(BT) void gather_kernel(uint64_t n, DevBatch in, uin
         }
     }
 }
-
-// one batch as the caller hands it over
-struct HostBatch {
-    const uint8_t *reads;
-    const uint64_t *off;
-    const uint8_t *qual;
-    const uint64_t *qual_off;
-    uint8_t *out_reads, *out_qual;
-    uint64_t *out_off;
-};
 
 thread_local polyhip_trim_info t_info{};
 
