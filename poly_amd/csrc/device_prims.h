@@ -1,6 +1,7 @@
 // device_prims.h -- general device primitives of the string units (bwt.hip, bwt_mismatch.hip, map_reads.hip, refs.hip,
-// aln_records.hip, pileup.hip): the exclusive scans and the LSD radix sort of (uint64 key, uint32 value), the wave and block
-// helpers their own kernels call, and the host helpers around a launch (grids, workspaces, the device of a handle).
+// aln_records.hip, pileup.hip, pileup_walk.hip, pileup_rows.hip, variants.hip): the exclusive scans and the LSD radix sort
+// of (uint64 key, uint32 value), the wave and block helpers their own kernels call, and the host helpers around a launch
+// (grids, workspaces, the device of a handle).
 // scan_excl and radix_sort are compiled once, in device_prims.hip: the library is built without relocatable device code, so
 // a kernel is launched from the unit that defines it.  Everything else here is inline.
 #pragma once

@@ -1,6 +1,6 @@
-// pileup_call.h -- what polyhip_pileup (pileup.hip) and polyhip_pileup_qual (pileup_qual.hip) share: the channels, the base
-// classes and the pass that turns the 16 count planes into the consensus and the sites.  Each unit compiles its own copy
-// (internal linkage); the walks that fill the counts stay with their units.
+// pileup_call.h -- the pileup family's channels, info words and base classes (pileup_walk.hip fills the count planes with
+// them; pileup_rows.hip and variants.hip read them), and the pass that turns the 16 count planes into the consensus and the
+// sites for polyhip_pileup and polyhip_pileup_qual (pileup.hip, which alone instantiates it; internal linkage).
 #pragma once
 #include "device_prims.h"
 

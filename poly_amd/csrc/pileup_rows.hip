@@ -3,12 +3,12 @@
 // include/polyhip.h; tests/pileup_rows_oracle.py restates it in plain Python.
 //
 //   order_kernel          one lane per rank: order[r] < n and seen once, else a flag (the host refuses before anything is written)
-//   walk_kernel<false> /  (pileup_walk.h) err of every entry, exactly as polyhip_pileup (qual == NULL) or polyhip_pileup_qual
-//   walk_qual_kernel<false>  (qual != NULL) judge it
+//   walk_entries          (pileup_walk.h) err of every entry, exactly as polyhip_pileup (qual == NULL) or polyhip_pileup_qual
+//                         (qual != NULL) judge it: the judging walk alone
 //   count_kernel          one lane per rank: the tokens of the entry at that rank, |[ref_start, ref_end) ∩ region| for a used
 //                         entry (every column with b != '-' is one token, so no walk is needed), and its dropped leading runs
 //   scan_excl<uint64>     the first item of every rank; the total goes to the host (more than 2^32 - 1 is refused)
-//   item_kernel           one wave per rank, 64 columns per step, the pileup's walk: the lane of a column with b != '-' in the
+//   item_kernel           one wave per rank, 64 columns per step, the pileup's walk (ColumnWalk): the lane of a column with b != '-' in the
 //                         region writes item base[r] + (p - first position): key p - lo, entry, column, the token's byte length
 //                         and its quality byte, and adds one to depth[p - lo] (an integer histogram)
 //   radix_sort            the items by key, bits_for(L - 1) bits.  The sort is stable and the items stand in rank order, so
@@ -59,27 +59,6 @@ __device__ __forceinline__ uint8_t *put_dec(uint8_t *dst, uint64_t v, uint32_t n
 }
 
 __device__ __forceinline__ uint8_t letter(uint32_t c, bool reverse) { return (uint8_t)(reverse ? "acgtn" : "ACGTN")[base_class(c)]; }
-__device__ __forceinline__ uint32_t fold(uint32_t c) { return c >= 'a' && c <= 'z' ? c - 32u : c; }
-
-struct Entries {
-    uint64_t n;
-    uint32_t min_mapq;
-    const uint32_t *flags;
-    const uint8_t *mapq; // may be null
-    const uint32_t *ref_start, *ref_end, *read_start;
-    const uint8_t *alnA, *alnB;
-    const uint64_t *alnOff;
-    const uint8_t *qual; // null: no qualities
-    const uint64_t *qualOff;
-    const uint32_t *err;
-    const uint32_t *order; // null: entry order
-};
-
-__device__ __forceinline__ bool entry_used(const Entries &E, uint64_t i)
-{
-    const uint32_t f = E.flags[i];
-    return (f & 1u) && !(E.min_mapq > 0 && E.mapq[i] < E.min_mapq) && E.err[i] == 0;
-}
 
 __global__ __launch_bounds__(BT) void order_kernel(uint64_t n, const uint32_t *__restrict__ order, uint32_t *seen, uint32_t *flag)
 {
@@ -169,15 +148,13 @@ __global__ __launch_bounds__(BT) void item_kernel(Entries E, uint32_t qbase, uin
             no_read_base = nA == 0;
             last = abase + nA - 1;
         }
-        uint64_t tbase = rs;
+        ColumnWalk S(rs, abase);
         for (uint32_t base = 0; base < ncols; base += 64) {
+            S.load(a, b, base, ncols, lane);
             const uint32_t c = base + lane;
-            const bool v = c < ncols;
-            const uint32_t ca = v ? a[c] : 0u, cb = v ? b[c] : 0u;
-            const bool ga = ca == '-', gb = cb == '-';
-            const uint64_t mV = __ballot(v), mD = __ballot(v && ga), mI = __ballot(v && gb), mT = mV & ~mI, mA = mV & ~mD;
-            const uint64_t p = tbase + (uint64_t)__popcll(mT & lanes_below(lane));
-            if (v && !gb && p - lo < L) { // p < lo wraps to a value above L
+            const bool ga = S.ga;
+            const uint64_t p = S.p;
+            if (S.v && !S.gb && p - lo < L) { // p < lo wraps to a value above L
                 const uint64_t t = t0 + (p - from);
                 uint32_t nI, nD;
                 runs_behind(a, b, c, ncols, ga, nI, nD);
@@ -185,7 +162,7 @@ __global__ __launch_bounds__(BT) void item_kernel(Entries E, uint32_t qbase, uin
                                        (p + 1 == re ? 1u : 0u);
                 uint8_t quality = (uint8_t)(MAPQ_TOP + OUT_OFFSET); // '~'
                 if (q) { // err[i] == 0: every index below is inside the entry's string, every byte in qbase .. qbase + 93
-                    uint64_t x = abase + (uint64_t)__popcll(mA & lanes_below(lane));
+                    uint64_t x = S.x(lane);
                     if (ga)
                         x = std::min(x, last);
                     quality = ga && no_read_base ? (uint8_t)OUT_OFFSET : (uint8_t)((uint32_t)q[reverse ? m - 1 - x : x] - qbase + OUT_OFFSET);
@@ -198,9 +175,8 @@ __global__ __launch_bounds__(BT) void item_kernel(Entries E, uint32_t qbase, uin
                 qb[t] = quality;
                 atomicAdd(&depth[p - lo], 1u);
             }
-            tbase += (uint64_t)__popcll(mT);
-            abase += (uint64_t)__popcll(mA);
-            if (tbase >= lo + L) // the rest of the entry lies behind the region
+            S.advance();
+            if (S.tbase >= lo + L) // the rest of the entry lies behind the region
                 break;
         }
     }
@@ -341,14 +317,13 @@ int polyhip_pileup_rows(const polyhip_pileup_rows_params *params, uint64_t n, co
 {
     const char *who = "polyhip_pileup_rows";
     PH_REQUIRE(params, "%s: null params", who);
-    PH_REQUIRE(params->region_lo <= params->region_hi, "%s: region_lo = %llu is above region_hi = %llu", who,
-               (unsigned long long)params->region_lo, (unsigned long long)params->region_hi);
-    PH_REQUIRE(params->region_hi <= ref_len, "%s: region_hi = %llu is above ref_len = %llu", who, (unsigned long long)params->region_hi,
-               (unsigned long long)ref_len);
+    if (int rc = check_region(who, params->region_lo, params->region_hi, ref_len))
+        return rc;
     PH_REQUIRE(params->pos_origin <= params->region_lo, "%s: pos_origin = %llu is above region_lo = %llu", who,
                (unsigned long long)params->pos_origin, (unsigned long long)params->region_lo);
     PH_REQUIRE(params->all_positions <= 1, "%s: all_positions = %u, it is 0 or 1", who, params->all_positions);
-    PH_REQUIRE(params->qual_offset <= 255u - MAX_Q, "%s: qual_offset = %u, it is 0 to %u", who, params->qual_offset, 255u - MAX_Q);
+    if (int rc = check_qual_offset(who, params->qual_offset))
+        return rc;
     PH_REQUIRE(name && name_len, "%s: the name is null or empty", who);
     for (uint64_t k = 0; k < name_len; ++k)
         PH_REQUIRE(name[k] >= 0x21 && name[k] <= 0x7e, "%s: byte %llu of the name is 0x%02x, outside 0x21..0x7e", who, (unsigned long long)k,
@@ -358,72 +333,40 @@ int polyhip_pileup_rows(const polyhip_pileup_rows_params *params, uint64_t n, co
     PH_REQUIRE(params->min_mapq == 0 || mapq, "%s: min_mapq = %u needs mapq, which is null", who, params->min_mapq);
     const uint64_t lo = params->region_lo, L = params->region_hi - params->region_lo;
     PH_REQUIRE(ref && ntext && (text || text_capacity == 0), "%s: null argument", who);
-    PH_REQUIRE(n == 0 || (flags && ref_start && ref_end && alnOff && err && (!qual || (read_start && qualOff)) &&
-                          ((alnA && alnB) || alnOff[n] == alnOff[0])),
-               "%s: null argument", who);
-    for (uint64_t i = 0; i < n; ++i)
-        PH_REQUIRE(alnOff[i + 1] >= alnOff[i] && (!qual || qualOff[i + 1] >= qualOff[i]), "%s: offsets are not ascending", who);
+    const Entries H{n, params->min_mapq, flags, mapq, ref_start, ref_end, read_start, alnA, alnB, alnOff, qual, qualOff, err, order};
+    if (int rc = check_entries(who, H, qual != nullptr))
+        return rc;
     const bool with_q = qual != nullptr && n > 0;
-    const uint64_t nbytes = n ? alnOff[n] - alnOff[0] : 0, qbytes = with_q ? qualOff[n] - qualOff[0] : 0;
     t_rinfo = polyhip_pileup_rows_info{};
 
     HostStreams &hs = host_streams();
     PH_HIP(hs.init());
     hipStream_t st = hs.s[0];
     Arena w;
-    const size_t o_flags = w.reserve(n * 4), o_mapq = w.reserve(mapq ? n : 0), o_rs = w.reserve(n * 4), o_re = w.reserve(n * 4),
-                 o_qs = w.reserve(with_q ? n * 4 : 0), o_a = w.reserve(nbytes), o_b = w.reserve(nbytes), o_off = w.reserve((n + 1) * 8),
-                 o_q = w.reserve(qbytes), o_qoff = w.reserve(with_q ? (n + 1) * 8 : 0), o_ref = w.reserve(ref_len), o_err = w.reserve(n * 4),
-                 o_order = w.reserve(order ? n * 4 : 0), o_seen = w.reserve(order ? n * 4 : 0), o_name = w.reserve(name_len),
+    const EntryStage stage(w, H, ref_len, mapq != nullptr, with_q); // mapq whenever it is given: the tokens print it
+    const size_t o_order = w.reserve(order ? n * 4 : 0), o_seen = w.reserve(order ? n * 4 : 0), o_name = w.reserve(name_len),
                  o_cnt = w.reserve((n + 1) * 8), o_info = w.reserve((RINFO_WORDS + 1) * sizeof(unsigned long long)),
                  o_scan = w.reserve(scan_scratch_bytes<uint64_t>(n));
     PH_HIP(w.buf.alloc(w.used));
     SyncOnExit sync(st);
-    const struct {
-        size_t at;
-        const void *src;
-        size_t bytes;
-    } in[] = {{o_flags, flags, n * 4}, {o_mapq, mapq, mapq ? n : 0}, {o_rs, ref_start, n * 4}, {o_re, ref_end, n * 4},
-              {o_qs, read_start, with_q ? n * 4 : 0}, {o_a, nbytes ? alnA + alnOff[0] : nullptr, nbytes},
-              {o_b, nbytes ? alnB + alnOff[0] : nullptr, nbytes}, {o_off, alnOff, n ? (n + 1) * 8 : 0},
-              {o_q, qbytes ? qual + qualOff[0] : nullptr, qbytes}, {o_qoff, qualOff, with_q ? (n + 1) * 8 : 0}, {o_ref, ref, ref_len},
-              {o_order, order, order ? n * 4 : 0}, {o_name, name, name_len}};
-    for (const auto &x : in)
-        if (x.bytes)
-            PH_HIP(hipMemcpyAsync(w.at<uint8_t>(x.at), x.src, x.bytes, hipMemcpyHostToDevice, st));
+    Entries E;
+    PH_HIP(stage.upload(w, ref, st, E));
+    if (order && n) {
+        PH_HIP(hipMemcpyAsync(w.at<uint8_t>(o_order), order, n * 4, hipMemcpyHostToDevice, st));
+        E.order = w.at<uint32_t>(o_order);
+    }
+    PH_HIP(hipMemcpyAsync(w.at<uint8_t>(o_name), name, name_len, hipMemcpyHostToDevice, st));
     // the info words and, behind them, the word the order check raises
     PH_HIP(hipMemsetAsync(w.at<uint8_t>(o_info), 0, (RINFO_WORDS + 1) * sizeof(unsigned long long), st));
     unsigned long long *d_info = w.at<unsigned long long>(o_info);
     uint32_t *d_flag = reinterpret_cast<uint32_t *>(d_info + RINFO_WORDS);
-    Entries E{n,
-              params->min_mapq,
-              w.at<uint32_t>(o_flags),
-              mapq ? w.at<uint8_t>(o_mapq) : nullptr,
-              w.at<uint32_t>(o_rs),
-              w.at<uint32_t>(o_re),
-              w.at<uint32_t>(o_qs),
-              w.at<uint8_t>(o_a),
-              w.at<uint8_t>(o_b),
-              w.at<uint64_t>(o_off),
-              with_q ? w.at<uint8_t>(o_q) : nullptr,
-              w.at<uint64_t>(o_qoff),
-              w.at<uint32_t>(o_err),
-              order && n ? w.at<uint32_t>(o_order) : nullptr};
     if (n) {
         if (order) {
             PH_HIP(hipMemsetAsync(w.at<uint8_t>(o_seen), 0, n * 4, st));
             hipLaunchKernelGGL(order_kernel, dim3(grid_for(n)), dim3(BT), 0, st, n, w.at<uint32_t>(o_order), w.at<uint32_t>(o_seen), d_flag);
             PH_HIP(hipGetLastError());
         }
-        const unsigned wgrid = grid_for(n, PU_WAVES, PU_MAX_BLOCKS);
-        if (with_q)
-            hipLaunchKernelGGL(walk_qual_kernel<false>, dim3(wgrid), dim3(BT), 0, st, n, params->min_mapq, 0u, params->qual_offset, lo, L, ref_len,
-                               E.flags, E.mapq, E.ref_start, E.ref_end, E.read_start, E.alnA, E.alnB, E.alnOff, E.qual, E.qualOff,
-                               w.at<uint8_t>(o_ref), w.at<uint32_t>(o_err), (uint32_t *)nullptr, (uint32_t *)nullptr, d_info);
-        else
-            hipLaunchKernelGGL(walk_kernel<false>, dim3(wgrid), dim3(BT), 0, st, n, params->min_mapq, lo, L, ref_len, E.flags, E.mapq, E.ref_start,
-                               E.ref_end, E.alnA, E.alnB, E.alnOff, w.at<uint8_t>(o_ref), w.at<uint32_t>(o_err), (uint32_t *)nullptr, d_info);
-        PH_HIP(hipGetLastError());
+        PH_HIP(walk_entries(E, WalkArgs{lo, L, ref_len, stage.ref(w), 0u, params->qual_offset, nullptr, nullptr, d_info}, false, with_q, st));
         hipLaunchKernelGGL(count_kernel, dim3(grid_for(n)), dim3(BT), 0, st, E, lo, L, w.at<uint64_t>(o_cnt), d_info);
         PH_HIP(hipGetLastError());
     }
@@ -436,7 +379,7 @@ int polyhip_pileup_rows(const polyhip_pileup_rows_params *params, uint64_t n, co
     PH_REQUIRE((uint32_t)info[RINFO_WORDS] == 0, "%s: order is not a permutation of 0..%llu", who, (unsigned long long)(n ? n - 1 : 0));
     *ntext = 0;
     if (n) {
-        PH_HIP(hipMemcpyAsync(err, w.at<uint8_t>(o_err), n * 4, hipMemcpyDeviceToHost, st));
+        PH_HIP(hipMemcpyAsync(err, E.err, n * 4, hipMemcpyDeviceToHost, st));
         PH_HIP(hipStreamSynchronize(st));
     }
     t_rinfo.entries = n;
@@ -505,7 +448,7 @@ int polyhip_pileup_rows(const polyhip_pileup_rows_params *params, uint64_t n, co
     DevBuf dtext;
     PH_HIP(dtext.alloc(total));
     SyncOnExit sync_text(st);
-    hipLaunchKernelGGL(header_kernel, dim3(lgrid), dim3(BT), 0, st, S, x.at<uint64_t>(o_row), w.at<uint8_t>(o_name), w.at<uint8_t>(o_ref),
+    hipLaunchKernelGGL(header_kernel, dim3(lgrid), dim3(BT), 0, st, S, x.at<uint64_t>(o_row), w.at<uint8_t>(o_name), stage.ref(w),
                        dtext.as<uint8_t>());
     PH_HIP(hipGetLastError());
     if (N) {

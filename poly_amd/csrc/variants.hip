@@ -2,10 +2,10 @@
 // left-aligned first, counted per strand, put to the pileup's thresholds and merged with the SNV records.  The definition is
 // the comment above polyhip_call_variants in include/polyhip.h; tests/variants_oracle.py restates it in plain Python.
 //
-//   walk_kernel / walk_qual_kernel  (pileup_walk.h, unchanged) err of every entry, then the 16 count planes and, with qualities,
-//                         the 8 qsum planes, on the device only
+//   walk_entries          (pileup_walk.h) err of every entry, then the 16 count planes and, with qualities, the 8 qsum planes,
+//                         on the device only
 //   snv_kernel<false>     one lane per position: the depth and the number of SNV records of the position
-//   event_kernel<false>   one wave per used entry, 64 columns per step, the pileup's walk with its run-start masks sI, sD.  For
+//   event_kernel<false>   one wave per used entry, 64 columns per step, the pileup's walk (ColumnWalk) with its run-start masks.  For
 //                         every run the wave finds its length (ballots over 64 columns at a time, the first column of another
 //                         class from the complement mask) and its shift k (ballots over 64 steps t at a time, the first failing
 //                         step from the complement mask; a shift longer than 64 goes round again), and judges it: long, open,
@@ -44,25 +44,6 @@ namespace {
 enum : int { VINFO_EVENTS = QINFO_WORDS, VINFO_LONG, VINFO_OPEN, VINFO_EDGE, VINFO_SHIFTED, VINFO_MAXINS, VINFO_WORDS };
 constexpr int KEY_LOW_BITS = 9; // length (8 bits, 1..255), kind (1 bit: 0 insertion, 1 deletion); the position above them
 constexpr uint32_t COL_REVERSE = 1u << 31; // columns stay below 2^28
-
-__device__ __forceinline__ uint32_t fold(uint32_t c) { return c >= 'a' && c <= 'z' ? c - 32u : c; }
-
-struct Entries {
-    uint64_t n;
-    uint32_t min_mapq;
-    const uint32_t *flags;
-    const uint8_t *mapq; // may be null
-    const uint32_t *ref_start;
-    const uint8_t *alnA, *alnB;
-    const uint64_t *alnOff;
-    const uint32_t *err;
-};
-
-__device__ __forceinline__ bool entry_used(const Entries &E, uint64_t i)
-{
-    const uint32_t f = E.flags[i];
-    return (f & 1u) && !(E.min_mapq > 0 && E.mapq[i] < E.min_mapq) && E.err[i] == 0;
-}
 
 // EMIT == false: depth[j] and nsnv[j] (L + 1 slots for the scan) are written.
 // EMIT == true: nsnv (now the offsets) is read and the position's SNV records are written behind the passing alleles of the
@@ -152,23 +133,16 @@ __global__ __launch_bounds__(BT) void event_kernel(Entries E, uint32_t left_alig
         const uint32_t ncols = (uint32_t)(E.alnOff[i + 1] - E.alnOff[i]);
         const uint8_t *a = E.alnA + (E.alnOff[i] - off0), *b = E.alnB + (E.alnOff[i] - off0);
         const uint32_t reverse = E.flags[i] & 2u ? COL_REVERSE : 0u;
-        uint64_t tbase = E.ref_start[i]; // text position of the next column with b != '-'
-        uint32_t carry = 0;              // the column before this step: bit 0 it was I, bit 1 it was D
-        uint64_t slot = 0;               // the entry's items so far
+        ColumnWalk S(E.ref_start[i], 0);
+        uint64_t slot = 0; // the entry's items so far
         for (uint32_t base = 0; base < ncols; base += 64) {
-            const uint32_t c = base + lane;
-            const bool v = c < ncols;
-            const uint32_t ca = v ? a[c] : 0u, cb = v ? b[c] : 0u;
-            const bool ga = ca == '-', gb = cb == '-';
-            const uint64_t mV = __ballot(v), mD = __ballot(v && ga), mI = __ballot(v && gb), mT = mV & ~mI;
-            // a column with b != '-' sits at p; a run that starts at this lane is anchored at p - 1
-            const uint64_t p = tbase + (uint64_t)__popcll(mT & lanes_below(lane));
-            const uint64_t sI = mI & ~(mI << 1 | (carry & 1u)), sD = mD & ~(mD << 1 | (carry >> 1 & 1u));
+            S.load(a, b, base, ncols, lane);
+            const uint64_t sI = S.sI(), sD = S.sD();
             for (uint64_t starts = sI | sD; starts; starts &= starts - 1) { // the wave takes the step's runs one after the other
                 const int e = __ffsll((unsigned long long)starts) - 1;
                 const bool ins = sI >> e & 1ull;
                 const uint32_t c0 = base + (uint32_t)e;
-                const uint64_t pe = __shfl(p, e, 64);
+                const uint64_t pe = __shfl(S.p, e, 64);
                 uint32_t l = 0; // the run's columns: the first column of another class ends it
                 for (uint32_t o = 0;; o += 64) {
                     const uint32_t cc = c0 + o + lane;
@@ -230,9 +204,7 @@ __global__ __launch_bounds__(BT) void event_kernel(Entries E, uint32_t left_alig
                     ++slot;
                 }
             }
-            const int nv = __popcll(mV);
-            carry = (uint32_t)(mI >> (nv - 1) & 1ull) | (uint32_t)(mD >> (nv - 1) & 1ull) << 1;
-            tbase += (uint64_t)__popcll(mT);
+            S.advance();
         }
         if (!EMIT && lane == 0)
             cnt[i] = slot;
@@ -408,13 +380,11 @@ int polyhip_call_variants(const polyhip_variants_params *params, uint64_t n, con
     PH_REQUIRE(params, "%s: null params", who);
     const polyhip_pileup_qual_params &pq = params->base;
     const polyhip_pileup_params &pb = pq.base;
-    PH_REQUIRE(pb.region_lo <= pb.region_hi, "%s: region_lo = %llu is above region_hi = %llu", who, (unsigned long long)pb.region_lo,
-               (unsigned long long)pb.region_hi);
-    PH_REQUIRE(pb.region_hi <= ref_len, "%s: region_hi = %llu is above ref_len = %llu", who, (unsigned long long)pb.region_hi,
-               (unsigned long long)ref_len);
+    if (int rc = check_region(who, pb.region_lo, pb.region_hi, ref_len))
+        return rc;
     PH_REQUIRE(pb.min_alt_permille <= 1000, "%s: min_alt_permille = %u, it is 0 to 1000", who, pb.min_alt_permille);
-    PH_REQUIRE(pq.min_base_qual <= MAX_Q, "%s: min_base_qual = %u, it is 0 to %u", who, pq.min_base_qual, MAX_Q);
-    PH_REQUIRE(pq.qual_offset <= 255u - MAX_Q, "%s: qual_offset = %u, it is 0 to %u", who, pq.qual_offset, 255u - MAX_Q);
+    if (int rc = check_qual_params(who, pq.min_base_qual, pq.qual_offset))
+        return rc;
     PH_REQUIRE(params->hom_permille <= 1000, "%s: hom_permille = %u, it is 0 to 1000", who, params->hom_permille);
     PH_REQUIRE(params->max_indel <= POLYHIP_VAR_MAX_INDEL, "%s: max_indel = %u, it is 0 to %u", who, params->max_indel, POLYHIP_VAR_MAX_INDEL);
     PH_REQUIRE(params->pad == 0, "%s: pad = %u, it is 0", who, params->pad);
@@ -427,13 +397,9 @@ int polyhip_call_variants(const polyhip_variants_params *params, uint64_t n, con
     const uint64_t lo = pb.region_lo, L = pb.region_hi - pb.region_lo;
     PH_REQUIRE(ref && nvariants && nallele_bytes && (variants || variant_capacity == 0) && (alleles || allele_capacity == 0), "%s: null argument",
                who);
-    PH_REQUIRE(n == 0 || (flags && ref_start && ref_end && alnOff && err && (!with_q || (read_start && qualOff)) &&
-                          ((alnA && alnB) || alnOff[n] == alnOff[0])),
-               "%s: null argument", who);
-    for (uint64_t i = 0; i < n; ++i)
-        PH_REQUIRE(alnOff[i + 1] >= alnOff[i] && (!with_q || qualOff[i + 1] >= qualOff[i]), "%s: offsets are not ascending", who);
-    const uint64_t nbytes = n ? alnOff[n] - alnOff[0] : 0, qbytes = with_q && n ? qualOff[n] - qualOff[0] : 0;
-    const bool by_mapq = pb.min_mapq > 0;
+    const Entries H{n, pb.min_mapq, flags, mapq, ref_start, ref_end, read_start, alnA, alnB, alnOff, qual, qualOff, err, nullptr};
+    if (int rc = check_entries(who, H, with_q))
+        return rc;
     const uint32_t max_indel = params->max_indel ? params->max_indel : POLYHIP_VAR_MAX_INDEL;
     t_vinfo = polyhip_variants_info{};
     *nvariants = 0;
@@ -443,26 +409,15 @@ int polyhip_call_variants(const polyhip_variants_params *params, uint64_t n, con
     PH_HIP(hs.init());
     hipStream_t st = hs.s[0];
     Arena w;
-    const size_t o_flags = w.reserve(n * 4), o_mapq = w.reserve(by_mapq ? n : 0), o_rs = w.reserve(n * 4), o_re = w.reserve(n * 4),
-                 o_qs = w.reserve(with_q ? n * 4 : 0), o_a = w.reserve(nbytes), o_b = w.reserve(nbytes), o_off = w.reserve((n + 1) * 8),
-                 o_q = w.reserve(qbytes), o_qoff = w.reserve(with_q ? (n + 1) * 8 : 0), o_ref = w.reserve(ref_len), o_err = w.reserve(n * 4),
-                 o_counts = w.reserve(POLYHIP_PILEUP_CHANNELS * L * 4), o_qsum = w.reserve(with_q ? POLYHIP_PILEUP_QSUM_PLANES * L * 4 : 0),
+    const EntryStage stage(w, H, ref_len, pb.min_mapq > 0, with_q);
+    const size_t o_counts = w.reserve(POLYHIP_PILEUP_CHANNELS * L * 4), o_qsum = w.reserve(with_q ? POLYHIP_PILEUP_QSUM_PLANES * L * 4 : 0),
                  o_depth = w.reserve(L * 4), o_nsnv = w.reserve((L + 1) * 8), o_cnt = w.reserve((n + 1) * 8),
                  o_info = w.reserve(VINFO_WORDS * sizeof(unsigned long long)),
                  o_scan = w.reserve(std::max(scan_scratch_bytes<uint64_t>(L), scan_scratch_bytes<uint64_t>(n)));
     PH_HIP(w.buf.alloc(w.used));
     SyncOnExit sync(st);
-    const struct {
-        size_t at;
-        const void *src;
-        size_t bytes;
-    } in[] = {{o_flags, flags, n * 4}, {o_mapq, mapq, by_mapq ? n : 0}, {o_rs, ref_start, n * 4}, {o_re, ref_end, n * 4},
-              {o_qs, read_start, with_q ? n * 4 : 0}, {o_a, nbytes ? alnA + alnOff[0] : nullptr, nbytes},
-              {o_b, nbytes ? alnB + alnOff[0] : nullptr, nbytes}, {o_off, alnOff, n ? (n + 1) * 8 : 0},
-              {o_q, qbytes ? qual + qualOff[0] : nullptr, qbytes}, {o_qoff, qualOff, with_q && n ? (n + 1) * 8 : 0}, {o_ref, ref, ref_len}};
-    for (const auto &x : in)
-        if (x.bytes)
-            PH_HIP(hipMemcpyAsync(w.at<uint8_t>(x.at), x.src, x.bytes, hipMemcpyHostToDevice, st));
+    Entries E;
+    PH_HIP(stage.upload(w, ref, st, E));
     unsigned long long *d_info = w.at<unsigned long long>(o_info);
     PH_HIP(hipMemsetAsync(d_info, 0, VINFO_WORDS * sizeof(unsigned long long), st));
     if (L) {
@@ -472,32 +427,12 @@ int polyhip_call_variants(const polyhip_variants_params *params, uint64_t n, con
     }
     uint32_t *d_counts = w.at<uint32_t>(o_counts), *d_qsum = with_q ? w.at<uint32_t>(o_qsum) : nullptr, *d_depth = w.at<uint32_t>(o_depth);
     uint64_t *d_nsnv = w.at<uint64_t>(o_nsnv), *d_cnt = w.at<uint64_t>(o_cnt);
-    const uint8_t *d_ref = w.at<uint8_t>(o_ref);
-    const Entries E{n,
-                    pb.min_mapq,
-                    w.at<uint32_t>(o_flags),
-                    by_mapq ? w.at<uint8_t>(o_mapq) : nullptr,
-                    w.at<uint32_t>(o_rs),
-                    w.at<uint8_t>(o_a),
-                    w.at<uint8_t>(o_b),
-                    w.at<uint64_t>(o_off),
-                    w.at<uint32_t>(o_err)};
+    const uint8_t *d_ref = stage.ref(w);
     const unsigned wgrid = grid_for(n, PU_WAVES, PU_MAX_BLOCKS);
-    if (n) {
-        auto walk = [&](auto plain, auto quality) {
-            if (with_q)
-                hipLaunchKernelGGL(quality, dim3(wgrid), dim3(BT), 0, st, n, pb.min_mapq, pq.min_base_qual, pq.qual_offset, lo, L, ref_len, E.flags,
-                                   E.mapq, E.ref_start, w.at<uint32_t>(o_re), w.at<uint32_t>(o_qs), E.alnA, E.alnB, E.alnOff, w.at<uint8_t>(o_q),
-                                   w.at<uint64_t>(o_qoff), d_ref, w.at<uint32_t>(o_err), d_counts, d_qsum, d_info);
-            else
-                hipLaunchKernelGGL(plain, dim3(wgrid), dim3(BT), 0, st, n, pb.min_mapq, lo, L, ref_len, E.flags, E.mapq, E.ref_start,
-                                   w.at<uint32_t>(o_re), E.alnA, E.alnB, E.alnOff, d_ref, w.at<uint32_t>(o_err), d_counts, d_info);
-            return hipGetLastError();
-        };
-        PH_HIP(walk(walk_kernel<false>, walk_qual_kernel<false>));
-        // with L == 0 no add lands anywhere, but the filtered bases are still counted
-        PH_HIP(walk(walk_kernel<true>, walk_qual_kernel<true>));
-    }
+    const WalkArgs W{lo, L, ref_len, d_ref, pq.min_base_qual, pq.qual_offset, d_counts, d_qsum, d_info};
+    PH_HIP(walk_entries(E, W, false, with_q, st));
+    // with L == 0 no add lands anywhere, but the filtered bases are still counted
+    PH_HIP(walk_entries(E, W, true, with_q, st));
     const uint32_t min_depth = std::max(pb.min_depth, 1u), min_count = std::max(pb.min_alt_count, 1u);
     const unsigned lgrid = grid_for(L, BT, 1u << 20);
     if (L) {
@@ -516,7 +451,7 @@ int polyhip_call_variants(const polyhip_variants_params *params, uint64_t n, con
     unsigned long long info[VINFO_WORDS];
     uint64_t N = 0, nsnv = 0;
     if (n)
-        PH_HIP(hipMemcpyAsync(err, w.at<uint8_t>(o_err), n * 4, hipMemcpyDeviceToHost, st));
+        PH_HIP(hipMemcpyAsync(err, E.err, n * 4, hipMemcpyDeviceToHost, st));
     PH_HIP(hipMemcpyAsync(info, d_info, sizeof info, hipMemcpyDeviceToHost, st));
     PH_HIP(hipMemcpyAsync(&N, d_cnt + n, sizeof N, hipMemcpyDeviceToHost, st));
     PH_HIP(hipMemcpyAsync(&nsnv, d_nsnv + L, sizeof nsnv, hipMemcpyDeviceToHost, st));

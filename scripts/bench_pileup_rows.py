@@ -35,7 +35,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 
-ROWS_KERNELS = ("order_kernel", "walk_kernel", "walk_qual_kernel", "count_kernel", "item_kernel", "gather_kernel", "rowsize_kernel",
+ROWS_KERNELS = ("order_kernel", "walk_kernel", "count_kernel", "item_kernel", "gather_kernel", "rowsize_kernel",
                 "header_kernel", "token_kernel", "radix_hist_kernel", "radix_scatter_kernel")      # and the scan_* kernels
 
 

@@ -38,7 +38,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 
-VARIANTS_KERNELS = ("walk_kernel", "walk_qual_kernel", "snv_kernel", "event_kernel", "wordkey_kernel", "mainkey_kernel", "head_kernel",
+VARIANTS_KERNELS = ("walk_kernel", "snv_kernel", "event_kernel", "wordkey_kernel", "mainkey_kernel", "head_kernel",
                     "start_kernel", "allele_kernel", "radix_hist_kernel", "radix_scatter_kernel")      # and the scan_* kernels
 SPACING = 2000
 
