@@ -1748,6 +1748,76 @@ int polyhip_demux_pairs(const polyhip_demux_params *params, const uint8_t *barco
                         uint8_t *out_reads2, uint8_t *out_qual2, uint64_t *out_off2);
 int polyhip_demux_last_info(polyhip_demux_info *info);
 
+/* ---- primer dimers: which primers of a pool bind each other (no counterpart in the reference) ---- */
+/*
+ * A ranking screen for the ungapped Watson-Crick duplexes two primers can form, scored by nearest-neighbour stacking alone.
+ * There is NO initiation term, no terminal-AT term, no dangling end, no loop and no mismatch term: the numbers rank pairs of
+ * one pool against each other, they are not a Tm and not a free energy of the duplex.
+ * Bytes.  ASCII lower case is folded to upper case.  A, C, G, T have the codes 0..3; every other byte, U and N among them, has
+ *   code 4 and pairs with nothing.
+ * Stack table.  stack_dg[16], int32 in cal/mol, entry 4 * code(a) + code(b) for the dinucleotide ab read 5'->3' on x; every
+ *   entry lies in [-30000, 0].  polyhip_primer_stack_dg(temp_mK, out) fills it from the library's nearest-neighbour table
+ *   (SantaLucia 1998, the 16 (dH, dS) pairs polyhip_santalucia_* use) in integers: H10 = 10 * dH, S10 = 10 * dS, num = H10 *
+ *   1,000,000 - temp_mK * S10 in int64, the entry is num / 10,000 rounded half away from zero: sign(num) * ((|num| + 5000) /
+ *   10000).  temp_mK is the temperature in millikelvin and must lie in [273150, 338000] (above 338028 the TA entry turns
+ *   positive); anything else is POLYHIP_ERR_INVALID.  The table is symmetric under reverse complement, which makes dg_any(x,
+ *   y) == dg_any(y, x).
+ * Duplex of the ordered pair (x, y), x of m and y of n bytes, 1 <= m, n <= 64.  The shift s runs over -(n - 1) .. m - 1.  At
+ *   shift s position i of x faces y[n - 1 - (i - s)] when 0 <= i - s <= n - 1: the antiparallel arrangement, x's 3' end on the
+ *   right and y's 3' end on the left.  Position i is paired iff code(x[i]) < 4 and code(y[n - 1 - (i - s)]) == 3 - code(x[i]).
+ *   A run is a maximal interval [i0, i1] of consecutive paired positions at one shift, pairs = i1 - i0 + 1, dg(run) = the sum
+ *   over i = i0 .. i1 - 1 of stack_dg[4 * code(x[i]) + code(x[i + 1])].  A run of one pair has no stack and is no candidate.
+ * Per pair.  dg_any is the smallest dg over the runs of two or more pairs at all shifts, and with it go shift = s + (n - 1)
+ *   (so >= 0), pos = i0 and pairs; among equal dg the smallest s wins, then the smallest i0.  Without such a run dg_any = 0 and
+ *   shift = pos = pairs = 0.  dg_end is the same minimum over the runs with i1 = m - 1 only -- x's 3' base is paired, the runs
+ *   a polymerase can extend --, with its shift and pairs (pos = m - pairs).  dg_end(y, x), the other primer's 3' end, is the
+ *   transposed pair's.
+ * Primer errors.  err = 1 for an empty primer, 2 for one longer than 64 bytes, else 0.  A pair with a bad primer has dg_any =
+ *   dg_end = 0 in the matrix; in the screen a bad y is never a partner and never counted, and a bad x has no partner and
+ *   counts nothing.
+ * Primers are packed like reads: primer i of X is X[offX[i] .. offX[i + 1]).  Pool mode: Y == NULL, offY == NULL and ny == 0
+ * mean Y = X (errY may then be NULL); any other combination of a missing Y, offY or ny is refused.
+ * polyhip_primer_dimer_matrix: dg_any and dg_end are row-major nx x ny; either may be NULL, not both.  nx * ny > 2^30 is
+ *   POLYHIP_ERR_UNSUPPORTED: the caller tiles.
+ * polyhip_primer_dimer_screen: per x, over the valid y: the partner is the j with the smallest dg, the smallest j among
+ *   equals, and 0xFFFFFFFF when that dg is 0 (shift, pos and pairs are then 0); otherwise shift, pos and pairs are those of
+ *   the pair (x, partner).  any_count / end_count: the valid y with dg_any <= any_threshold / dg_end <= end_threshold; both
+ *   thresholds are <= 0.  In pool mode the pair of a primer with itself counts like any other.  Every output has nx entries
+ *   (errY ny).  The call never holds nx x ny values: ny < 2^32 - 1 is the only limit (else POLYHIP_ERR_UNSUPPORTED).  The only
+ *   atomics are an integer minimum of (dg, j) and integer sums: the result depends neither on the order of the launches nor
+ *   on how the work is cut, and the same call gives the same bytes.
+ * Errors, in this order, all before anything is allocated: a NULL params or stack_dg (POLYHIP_ERR_INVALID); a table entry
+ * outside [-30000, 0] (_INVALID, naming the entry); any_threshold > 0, then end_threshold > 0 (_INVALID, naming the field);
+ * Y, offY and ny neither all given nor all missing (_INVALID); a NULL output -- the screen's arrays; both planes of the
+ * matrix; errX; errY outside pool mode -- or with nx > 0 a NULL X or offX (_INVALID); offsets that decrease (_INVALID, offX
+ * before offY); the size limit (_UNSUPPORTED).  nx == 0 is an empty, successful call that writes nothing.  Host pointers only,
+ * no stream: the calls copy the primers in, run on the calling thread's current device and copy the results out; the device
+ * list does not apply.
+ * polyhip_primer_dimer_last_info: the calling thread's last matrix or screen call: primers = nx + ny (nx in pool mode); bad =
+ * those with err != 0; pairs = valid x times valid y; shifts = the sum of m + n - 1 over these pairs; launches = kernels
+ * started.
+ */
+typedef struct polyhip_dimer_params {
+    int32_t stack_dg[16];   /* cal/mol, each in [-30000, 0] */
+    int32_t any_threshold;  /* any_count: the y with dg_any <= this; <= 0 */
+    int32_t end_threshold;  /* end_count: the y with dg_end <= this; <= 0 */
+} polyhip_dimer_params;
+typedef struct polyhip_dimer_info {
+    uint64_t primers, bad, pairs, shifts, launches;
+} polyhip_dimer_info;
+int polyhip_primer_stack_dg(uint32_t temp_mK, int32_t out[16]);
+int polyhip_primer_dimer_matrix(const int32_t stack_dg[16], const uint8_t *X, const uint64_t *offX,
+                                uint64_t nx, const uint8_t *Y, const uint64_t *offY, uint64_t ny,
+                                int32_t *dg_any, int32_t *dg_end, uint32_t *errX, uint32_t *errY);
+int polyhip_primer_dimer_screen(const polyhip_dimer_params *params, const uint8_t *X,
+                                const uint64_t *offX, uint64_t nx, const uint8_t *Y,
+                                const uint64_t *offY, uint64_t ny, int32_t *any_dg,
+                                uint32_t *any_partner, uint32_t *any_shift, uint32_t *any_pos,
+                                uint32_t *any_pairs, int32_t *end_dg, uint32_t *end_partner,
+                                uint32_t *end_shift, uint32_t *end_pairs, uint32_t *any_count,
+                                uint32_t *end_count, uint32_t *errX, uint32_t *errY);
+int polyhip_primer_dimer_last_info(polyhip_dimer_info *info);
+
 /* ---- R1: the path's one collective -- all-gather of per-rank sketches (RCCL over xGMI) ---- */
 /*
  * For hosts without torch.distributed (the Go/cgo drop-in); one process per GPU.  RCCL is

@@ -181,6 +181,11 @@ SIGNATURES = {
     "polyhip_demux_pairs": (C.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp,
                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "polyhip_demux_last_info": (C.c_int, [_vp]),
+    "polyhip_primer_stack_dg": (C.c_int, [_u32, _vp]),
+    "polyhip_primer_dimer_matrix": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "polyhip_primer_dimer_screen": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                              _vp, _vp]),
+    "polyhip_primer_dimer_last_info": (C.c_int, [_vp]),
     "polyhip_comm_unique_id": (C.c_int, [_vp]),
     "polyhip_comm_init_rank": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "polyhip_comm_destroy": (C.c_int, [_vp]),
